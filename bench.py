@@ -19,8 +19,12 @@ Every rank runs the step on its own arrays (independent objects, no data-path co
 scaling) and the value is the whole-job aggregate.  The reduce path (C4, RCCL all-reduce of the per-shard partial) is
 reported under "extra".
 
-Extra objects on the JSON line: "roofline" (dominant kernel, HIP-event timed inside this run) and
-"cpu_baseline" (the oracle = C++ restatement of the reference's algorithm, on this host's cores).
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR: after the timed steps, the two arrays the last timed step computed (B and C, Float64, 8 MiB each) are
+written to DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+--full: everything else, after the headline: bit-exact checks of the outputs against torch, "roofline" (dominant kernel,
+HIP-event timed inside this run), the other forms of the step, "step_same_destination", "extra" (the secondary workloads)
+and "cpu_baseline" (the oracle = C++ restatement of the reference's algorithm, on this host's cores).
 """
 import argparse
 import json
@@ -194,7 +198,8 @@ def cpu_baseline(S, budget_s=24.0, full=True):
 
 # The shape of the JSON line, in one place: --dry (the CPU test of the N-rank path) prints it, the real run asserts it.
 LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_replay", "closing_device_sync_us", "higher_is_better", "scaling", "degraded",
-             "vs_baseline", "dtype", "data", "rehearsal", "config", "frac_of_hbm_peak", "step_same_destination", "roofline")
+             "vs_baseline", "dtype", "data", "rehearsal", "config", "frac_of_hbm_peak")
+FULL_LINE_KEYS = ("step_same_destination", "roofline")   # --full only
 ROOFLINE_KEYS = ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "us_per_launch", "frac_rocprof_avg", "us_rocprof_avg", "rocprof_file",
                  "per_kernel", "library_replay_alone", "note", "hbm_cold")
 EXTRA_KEYS = {"c1": ("c1_symmetrise_4000_f64",), "hbm128": ("permutedims_128^4_f64", "broadcast4_128^4_f64"),
@@ -245,11 +250,13 @@ def dry_run(args, world, rank):
         seen, ranksum = 1, 0
     assert seen == world and ranksum == world * (world - 1) // 2
     if rank == 0:
-        print(json.dumps({"dry": True, "n_gpus": seen, "requested_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        full = args.full
+        print(json.dumps({"dry": True, "n_gpus": seen, "requested_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "full": full,
                           "backend": "gloo" if world > 1 else "none",
                           # the shape the real line will have for this job (asserted by the real run before it prints)
-                          "line_keys": list(LINE_KEYS) + ([] if args.no_cpu or seen > 1 else ["cpu_baseline"]) + ([] if args.no_extra else ["extra"]),
-                          "roofline_keys": list(ROOFLINE_KEYS), "extra_keys": [] if args.no_extra else extra_keys(seen, args.extras),
+                          "line_keys": list(LINE_KEYS) + (list(FULL_LINE_KEYS) if full else []) + ([] if not full or args.no_cpu or seen > 1 else ["cpu_baseline"])
+                          + ([] if not full or args.no_extra else ["extra"]),
+                          "roofline_keys": list(ROOFLINE_KEYS) if full else [], "extra_keys": [] if not full or args.no_extra else extra_keys(seen, args.extras),
                           "timed_region": "barrier | per-rank clock: K steps + local device sync | barrier, then MAX over ranks"}))
     if world > 1:
         dist.barrier()
@@ -262,10 +269,15 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads")
-    ap.add_argument("--extra-timeout", type=int, default=300, help="N > 1: seconds the secondary workloads may take before the headline is printed without them")
-    ap.add_argument("--extras", default="all", help="comma-separated subset of the secondary workloads: c1,hbm128,cold,c5,c4,sharded (default: all; `sharded` = the map/permute configs cut into --gpus slabs, runs by default only for N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the checks and measurements it does not need: bit-exact output checks, roofline / "
+                         "per-kernel figures, the other step forms, the same-destination step, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (Float64, 16 MiB in all; rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary workloads")
+    ap.add_argument("--extra-timeout", type=int, default=300, help="--full, N > 1: seconds the secondary workloads may take before the headline is printed without them")
+    ap.add_argument("--extras", default="all", help="--full: comma-separated subset of the secondary workloads: c1,hbm128,cold,c5,c4,sharded (default: all; `sharded` = the map/permute configs cut into --gpus slabs, runs by default only for N > 1)")
     ap.add_argument("--step-mode", choices=("seq", "seq1", "inorder", "chains"), default="seq",
                     help="seq: the library's own replay of the recorded step (smr_seq: AQL packets on its HSA queues, one queue per "
                          "dependency component -- the step's two operations are independent, both only read A -- results of in-order "
@@ -273,6 +285,8 @@ def main():
                          "stream; chains: hipGraph, one stream-ordered chain per output array")
     ap.add_argument("--dry", action="store_true", help="rendezvous only (gloo, no GPU): checks that --gpus N yields N ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch_as_ranks(args.gpus))
@@ -329,14 +343,17 @@ def main():
         plan2.execute(s)
         plan3.execute(s)
 
-    # correctness guard inside the bench: outputs must equal the torch permutes exactly
-    a4 = tA.reshape((n,) * 4)  # row-major view of the same memory: index order reversed
-    # column-major (i1,i2,i3,i4) <-> torch index [i4,i3,i2,i1]
-    ref2 = a4.permute(3, 2, 1, 0).contiguous().reshape(-1)
-    cm = lambda p: a4.permute(*[3 - p[3 - i] for i in range(4)])  # noqa: E731
-    ref3 = (((cm(perms[0]) + cm(perms[1])) + cm(perms[2])) + cm(perms[3])).contiguous().reshape(-1)
+    # correctness guard inside the bench (--full): outputs must equal the torch permutes exactly
+    if args.full:
+        a4 = tA.reshape((n,) * 4)  # row-major view of the same memory: index order reversed
+        # column-major (i1,i2,i3,i4) <-> torch index [i4,i3,i2,i1]
+        ref2 = a4.permute(3, 2, 1, 0).contiguous().reshape(-1)
+        cm = lambda p: a4.permute(*[3 - p[3 - i] for i in range(4)])  # noqa: E731
+        ref3 = (((cm(perms[0]) + cm(perms[1])) + cm(perms[2])) + cm(perms[3])).contiguous().reshape(-1)
 
     def check_outputs(when):
+        if not args.full:   # a plain run does only what the headline needs
+            return
         torch.cuda.synchronize()
         assert torch.equal(tB, ref2), "permutedims! result is wrong (%s)" % when
         assert torch.equal(tC, ref3), "fused 4-way broadcast result is wrong (%s)" % when
@@ -402,6 +419,9 @@ def main():
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     barrier()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: B = permutedims(A, (4,3,2,1)), C = the 4-way sum
+        dump_outputs(np, args.dump_outputs, {"permutedims_B": tB, "broadcast4_C": tC}, (n,) * 4)
     check_outputs("after the timed region")  # bit-exact, AFTER timing: the overlapped replay has in-order results
     if use_seq:
         seq_info = seq.info()
@@ -412,6 +432,42 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     value = world * K * (bytes2 + bytes3) / dt / 1e9
+
+    def headline_line():
+        return {
+            "metric": "GB/s effective HBM for @strided permutedims!+broadcast, 32^4 fp64",
+            "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": round(dt / K * 1e3, 6),
+            # the library's own clock around the same K steps: first doorbell -> completion signals observed (no Python, no torch sync)
+            "ms_per_step_replay": round(replay_us / K * 1e-3, 6) if (use_seq and replay_us is not None) else None,
+            # of ms_per_step * steps: the closing torch.cuda.synchronize() alone, after smr_seq_wait had already seen the completion signals
+            "closing_device_sync_us": round(t_sync * 1e6, 1) if use_seq else None,
+            "higher_is_better": True, "scaling": "weak", "degraded": False,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "rehearsal": ("$SMR_RCCL_LIB is set: %d ranks over gloo sharing %d GPU(s), the collective is a stand-in -- a rehearsal of the N-rank "
+                          "path, not a measurement" % (world, ndev)) if rehearsal else None,
+            "config": {"workload": "configs[1]+configs[2]: permutedims!(B,A,(4,3,2,1)) then C .= sum of 4 permuted views of A, 32x32x32x32 Float64, one "
+                                   "set of arrays (A, B, C) per GPU.  C is a THIRD array chosen so that the two statements share only the read-only A "
+                                   "and overlap; the README writes both into B -- that form is `step_same_destination` on the --full line",
+                       "algorithmic_bytes_per_step": bytes2 + bytes3,
+                       "launch": ("smr_seq replay (AQL packets on the library's HSA queues), " +
+                                  ("one queue per dependency component, the heavier chain (the 4-way sum) cut into two block ranges: the step's two "
+                                   "operations only share the read-only input A and overlap; acquire fences only where the sequence reads what it "
+                                   "writes (nowhere here); results of in-order execution" + (", verified bit-exactly after the timed region" if args.full else "")
+                                   if args.step_mode == "seq" else "one queue, in recorded order") + " | " + str(seq_info)) if use_seq else
+                                 ("hipGraph, " + ("two stream-ordered chains (one per output array; both operations only read A), one fork / one join per graph"
+                                                  if args.step_mode == "chains" else "in order on one stream")) if use_graph else "eager",
+                       "parallelism": "replicas x%d (independent arrays per rank)" % world},
+            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBS, 4),
+        }
+
+    if not args.full:
+        if rank == 0:
+            out = headline_line()
+            assert set(LINE_KEYS) <= set(out), sorted(set(LINE_KEYS) - set(out))
+            print(json.dumps(out), flush=True)
+        close_ranks(world, dist if world > 1 else None, False)
+        return
 
     # per-kernel launch durations, HIP events on the launch stream (graph replay of one kernel
     # type back to back: includes the dependent-launch gap, excludes host overhead)
@@ -623,50 +679,39 @@ def main():
         cold = {k: {"us": v.get("us"), "frac": v.get("frac_of_8TBs")} for k, v in extra.items() if k.endswith("_cold") or "_cold_" in k}
         roofline["hbm_cold"] = cold or None
     if rank == 0:
-        out = {
-            "metric": "GB/s effective HBM for @strided permutedims!+broadcast, 32^4 fp64",
-            "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(dt / K * 1e3, 6),
-            # the library's own clock around the same K steps: first doorbell -> completion signals observed (no Python, no torch sync)
-            "ms_per_step_replay": round(replay_us / K * 1e-3, 6) if (use_seq and replay_us is not None) else None,
-            # of ms_per_step * steps: the closing torch.cuda.synchronize() alone, after smr_seq_wait had already seen the completion signals
-            "closing_device_sync_us": round(t_sync * 1e6, 1) if use_seq else None,
-            "higher_is_better": True, "scaling": "weak",
-            # a secondary workload failed or a rank's watchdog fired: the headline was measured before them, but this is not a clean run
-            "degraded": bool(stuck or (isinstance(extra, dict) and "error" in extra)),
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "rehearsal": ("$SMR_RCCL_LIB is set: %d ranks over gloo sharing %d GPU(s), the collective is a stand-in -- a rehearsal of the N-rank "
-                          "path, not a measurement" % (world, ndev)) if rehearsal else None,
-            "config": {"workload": "configs[1]+configs[2]: permutedims!(B,A,(4,3,2,1)) then C .= sum of 4 permuted views of A, 32x32x32x32 Float64, one "
-                                   "set of arrays (A, B, C) per GPU.  C is a THIRD array chosen so that the two statements share only the read-only A "
-                                   "and overlap; the README writes both into B -- that form is `step_same_destination` on this line",
-                       "algorithmic_bytes_per_step": bytes2 + bytes3,
-                       "launch": ("smr_seq replay (AQL packets on the library's HSA queues), " +
-                                  ("one queue per dependency component, the heavier chain (the 4-way sum) cut into two block ranges: the step's two "
-                                   "operations only share the read-only input A and overlap; acquire fences only where the sequence reads what it "
-                                   "writes (nowhere here); results of in-order execution, verified bit-exactly after the timed region" if args.step_mode == "seq"
-                                   else "one queue, in recorded order") + " | " + str(seq_info)) if use_seq else
-                                 ("hipGraph, " + ("two stream-ordered chains (one per output array; both operations only read A), one fork / one join per graph"
-                                                  if args.step_mode == "chains" else "in order on one stream")) if use_graph else "eager",
-                       "step_us_long_graph": step_us,
-                       "parallelism": "replicas x%d (independent arrays per rank)" % world},
-            "frac_of_hbm_peak": round(value / world / HBM_PEAK_GBS, 4),
-            "step_same_destination": step_same_destination,
-            "roofline": roofline,
-        }
+        out = headline_line()
+        # a secondary workload failed or a rank's watchdog fired: the headline was measured before them, but this is not a clean run
+        out["degraded"] = bool(stuck or (isinstance(extra, dict) and "error" in extra))
+        out["config"]["step_us_long_graph"] = step_us
+        out["step_same_destination"] = step_same_destination
+        out["roofline"] = roofline
         if not args.no_cpu and world == 1:  # timed on rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(S)
         if extra:
             out["extra"] = extra
         # the line has the shape --dry announces (tests/test_distributed_cpu.py checks that one on the CPU)
-        assert set(LINE_KEYS) <= set(out), sorted(set(LINE_KEYS) - set(out))
+        assert set(LINE_KEYS + FULL_LINE_KEYS) <= set(out), sorted(set(LINE_KEYS + FULL_LINE_KEYS) - set(out))
         assert set(ROOFLINE_KEYS) <= set(roofline), sorted(set(ROOFLINE_KEYS) - set(roofline))
         if extra and "error" not in extra:
             missing = [k for k in extra_keys(world, args.extras) if k not in extra]
             assert not missing, "secondary workloads missing from the line: %s" % missing
         print(json.dumps(out), flush=True)
+    close_ranks(world, dist if world > 1 else None, stuck)
+
+
+def dump_outputs(np, dirname, tensors, shape):
+    """--dump-outputs: each (flat, column-major) device tensor as DIR/<name>.npy, an array of `shape` indexed like the Julia array."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy().reshape(shape, order="F")
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def close_ranks(world, dist, stuck):
+    """N ranks: the closing barrier (a peer may be stuck: it gets a watchdog of its own); a rescued run exits 3."""
     if world > 1:
-        if not stuck:   # (a peer may be stuck: the closing barrier gets a watchdog of its own)
+        if not stuck:
             import threading
             th = threading.Thread(target=lambda: (dist.barrier(), dist.destroy_process_group()), daemon=True)
             th.start()

@@ -92,8 +92,16 @@ class UnsupportedOnDevice(StridedHIPError):
 
 
 def build(jobs: int | None = None, verbose: bool = False) -> str:
-    """Compile libstrided_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
-    jobs = jobs or max(1, os.cpu_count() or 1)
+    """Compile libstrided_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+    Parallel jobs: `jobs`, else $MAX_JOBS, else the CPUs this process may use, at most 16 (on a shared host os.cpu_count() is
+    the whole machine's)."""
+    if not jobs:
+        try:
+            jobs = int(os.environ.get("MAX_JOBS", "0"))
+        except ValueError:
+            jobs = 0
+    jobs = jobs or min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+    jobs = max(1, jobs)
     r = subprocess.run(["make", "-C", CSRC_DIR, f"-j{jobs}"], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("building libstrided_hip.so failed:\n" + r.stdout[-4000:] + r.stderr[-8000:])

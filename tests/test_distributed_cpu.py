@@ -152,20 +152,28 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "1", "--dry"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "7", "--warmup", "1", "--full", "--dry"],
                        capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout            # rank 0 prints ONE line
     out = json.loads(lines[0])
-    assert out["n_gpus"] == 2 and out["requested_gpus"] == 2 and out["steps"] == 7 and out["warmup"] == 1
-    # the shape of the line a 2-rank job prints (round 6: the real run asserts the same constants before it prints): the map / permute
-    # configs cut into N slabs are there with the reduce path, the README's same-destination step and both roofline witnesses are
-    # top-level, and the collective barrier is outside the timed region
+    assert out["n_gpus"] == 2 and out["requested_gpus"] == 2 and out["steps"] == 7 and out["warmup"] == 1 and out["full"] is True
+    # the shape of the line a 2-rank --full job prints (round 6: the real run asserts the same constants before it prints): the map /
+    # permute configs cut into N slabs are there with the reduce path, the README's same-destination step and both roofline witnesses
+    # are top-level, and the collective barrier is outside the timed region
     assert {"c1_symmetrise_sharded", "broadcast4_sharded", "c4_mapreduce_abs2_4096x4096x64_f32"} <= set(out["extra_keys"])
     assert {"step_same_destination", "roofline", "ms_per_step_replay", "degraded"} <= set(out["line_keys"]) and "cpu_baseline" not in out["line_keys"]
     assert {"frac", "frac_rocprof_avg", "hbm_cold", "per_kernel"} <= set(out["roofline_keys"])
     assert out["timed_region"].startswith("barrier | per-rank clock")
+    # a plain run (no --full) prints the headline alone: the fields its result line is read by, nothing that needs runs of its own
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1", "--dry"],
+                       capture_output=True, text=True, timeout=120, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    plain = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert plain["full"] is False and plain["steps"] == 7 and plain["warmup"] == 1
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(plain["line_keys"])
+    assert not {"step_same_destination", "roofline", "cpu_baseline", "extra"} & set(plain["line_keys"]) and plain["extra_keys"] == []
     sys.path.insert(0, root)
     import bench
     assert "c1_symmetrise_sharded" not in bench.extra_keys(1, "all") and "broadcast4_sharded" in bench.extra_keys(1, "c4,sharded")

@@ -12,11 +12,11 @@ mkdir -p $O
 PARTS=${*:-bench prof probe times sanity rehearsal}
 has() { case " $PARTS " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has bench; then
-  python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 200 $O/bench_n1.json; echo
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_n1_driver_style.json 2>/dev/null; cut -c1-200 $O/bench_n1_driver_style.json
+  python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 200 $O/bench_n1.json; echo
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_n1_driver_style.json 2>/dev/null; cut -c1-200 $O/bench_n1_driver_style.json
 fi
 if has prof; then
-  ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/kt -o kt -- python $R/bench.py --steps 1000 --no-cpu --no-extra > $R/$O/kt.log 2>&1 ); echo "rocprof rc=$?"
+  ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $R/$O/kt -o kt -- python $R/bench.py --steps 1000 --full --no-cpu --no-extra > $R/$O/kt.log 2>&1 ); echo "rocprof rc=$?"
   python tools/rocpd_summary.py --hist $O/kt/kt_results.db > $O/bench_kernel_trace_stats.txt 2>&1; head -5 $O/bench_kernel_trace_stats.txt | cut -c1-160
   bash tools/pmc_passes.sh $O/pmc32 both 32 20 > $O/pmc_headline_kernels.txt 2>&1; grep -E "FETCH_SIZE|WRITE_SIZE|TCP_TCC_READ_REQ" $O/pmc_headline_kernels.txt | head -8 | cut -c1-200
   rm -rf $O/kt $O/pmc32
@@ -43,7 +43,7 @@ if has sanity; then
 fi
 if has rehearsal; then
   for n in 2 8; do
-    SMR_RCCL_LIB=tests/libfake_rccl.so timeout 900 python bench.py --gpus $n --steps 20 --warmup 5 --no-cpu --extras c4,sharded > $O/bench_gpus${n}_rehearsal.json 2> $O/bench_gpus${n}.err; echo "rehearsal $n rc=$?"
+    SMR_RCCL_LIB=tests/libfake_rccl.so timeout 900 python bench.py --gpus $n --steps 20 --warmup 5 --full --no-cpu --extras c4,sharded > $O/bench_gpus${n}_rehearsal.json 2> $O/bench_gpus${n}.err; echo "rehearsal $n rc=$?"
   done
 fi
 if has tests; then
