@@ -217,22 +217,13 @@ int smr_stream_sync(void* stream);
 
 /* ---- overlap windows: independent launches of one stream may run concurrently -----------------
  * The reference runs the independent halves of a problem as concurrent tasks and waits only where it
- * must (src/mapreduce.jl:203-223).  The GPU analogue: between smr_overlap_begin(stream) and
- * smr_overlap_end(stream) the library tracks the byte ranges its launches on `stream` read and write;
- * a launch that conflicts with none of the launches still in flight (no read-after-write, write-after-
- * write, write-after-read on any operand or on a plan's own partials) is dispatched without the AQL
- * barrier bit, so its waves start while its predecessors are still running or draining (a kernel
- * boundary costs 1.6-1.9 us on MI355X: more than a third of a 16 MiB launch); every other launch is
- * stream-ordered as usual.  Results are those of in-order execution.  The FIRST launch after begin is
- * always ordered (after whatever the caller queued before); end issues one ordered empty kernel when
- * needed, so that work the caller queues afterwards -- kernels, copies, events, synchronisation -- is
- * ordered after everything in the window.  Inside an open window the caller must not put work of its
- * own on `stream` (or must call smr_overlap_fence(stream) first).  Windows nest; they survive stream
- * capture into a hipGraph.
- * ON gfx942 / gfx950 THE WINDOW IS A NO-OP FOR LAUNCHES THAT GO THROUGH HIP: HIP accepts hipExtAnyOrderLaunch and ignores it on gfx9
- * (measured with device stamps, profiles/r04_overlap.txt), so the library does not even run the analysis there unless option
- * "overlap_window_hip" = 1 asks for it.  Independent launches DO overlap where the library dispatches by itself: on the streams of
- * smr_stream_create (next paragraph) and in recorded sequences (smr_seq_*).
+ * must (src/mapreduce.jl:203-223).  smr_overlap_begin(stream) / smr_overlap_end(stream) mark such a stretch of
+ * work on `stream`; windows nest, and an end without a matching begin returns SMR_EINVAL.  For launches that go
+ * through HIP a window is a no-op: they stay stream-ordered (HIP accepts hipExtAnyOrderLaunch and ignores it on
+ * gfx9, measured with device stamps, profiles/r04_overlap.txt).  smr_overlap_fence(stream) orders everything the
+ * library launched on `stream` before work the caller queues there next; on a library-owned stream it waits for
+ * the library's direct launches.  Independent launches DO overlap where the library dispatches by itself: on
+ * the streams of smr_stream_create (next paragraph) and in recorded sequences (smr_seq_*).
  * smr_stream_create returns a stream of the library's own -- the stream of a host (the Julia shim) that routes ALL its device work
  * through this library.  On MI355X its launches do not go through HIP at all: the library submits every launch itself as an AQL
  * packet on one of four HSA queues it owns, choosing the queue by the data -- a launch that conflicts with nothing in flight goes to
@@ -241,8 +232,8 @@ int smr_stream_sync(void* stream);
  * (csrc/smr_seq.cpp: eager direct dispatch; ~1 us of host time per launch instead of HIP's 3.6-4 us).  Results are those of in-order
  * execution.  The library fences by itself (waits for its queues) before every copy / synchronisation / sequence replay it performs on
  * such a stream (smr_memcpy_*, smr_stream_sync, smr_mapreduce_scalar, smr_seq_run, smr_free, smr_plan_destroy) and drains the HIP
- * work it queued there before the next direct launch.  Option "eager_direct" = 0 sends the launches through HIP instead (the window
- * of such a stream is then permanently open).                                                                                      */
+ * work it queued there before the next direct launch.  Option "eager_direct" = 0 sends the launches through HIP instead, in stream
+ * order.                                                                                      */
 int smr_overlap_begin(void* stream);
 int smr_overlap_end(void* stream);
 int smr_overlap_fence(void* stream);
@@ -439,39 +430,57 @@ int smr_mapreduce_sharded(const smr_problem* problem);
 /* ... with block-partitioned operands (see smr_shard_ex).                                   */
 int smr_mapreduce_sharded_ex(const smr_problem* problem, uint32_t local_ops);
 
-/* Tuning knobs; smr_set_option returns SMR_EINVAL for unknown names.  Analogue of the
- * reference's compile-time constants MINTHREADLENGTH / BLOCKMEMORYSIZE
- * (src/mapreduce.jl:141,462).  Names: "force_family" (0 auto, 1 generic, 3 tiled),
- * "tile_log2" (0 auto, 10, 12), "tile_lg0".."tile_lg7" (per-dim log2 tile extent, -1 auto),
- * "tiled_vec", "max_lds_bytes", "tile_order" (orbit-major tile order on/off),
- * "tiled_persist" / "tiled_persist_wpc" / "tiled_persist_min" (persistent pipelined form),
- * "reduce_blocks", "reduce_part_kind" (-1 auto, 0 general, 1 row, 2 col), "reduce_col_txlog",
- * "reduce_part_wgs" (partial reductions with fewer workgroups are split until about this many run), "reduce_col_narrow",
- * "reduce_single" (split reductions of at most this many chunks fold their partials inside the same launch; 0 = always a
- * second launch; a plan that owns partials must not run concurrently with itself on two streams), "reduce_tree" (up to this many
- * chunks fold inside the launch through two levels of arrival counters; 0 = off),
- * "jit" (runtime compilation of f on/off), "orbit" (ORBIT family on/off),
- * "orbit_lg" / "orbit_min" / "orbit_few" (orbit tile edge and thresholds), "orbit_pipe" (persistent
- * pipelined orbits: -1 auto, 0, 1), "nt_store" (non-temporal stores: -1 auto, 0 never, 1 always),
- * "nt_stream_min", "nt_load" (non-temporal loads of complete reductions: -1 auto, 0, 1), "flat" (FLAT family for short
- * leading dims that are not powers of two, on/off), "flat2" (its two-sided form: 0 off, 1 planner's rule, 2 wherever it applies) /
- * "flat2_bytes" / "flat2_lead_bytes", "reduce_row_floor", "reduce_row_dense", "tile_block" (block tile order for distinct arrays with several unit
- * axes: -1 auto, 0 off, n), "tile_block_xcd", "orbit_group", "orbit_minrun", "orbit_wgs".  Experiment
- * switches: "stream_u", "stream_pack_rows", "flatb" (batched FLAT form on/off), "eager_direct", "orbit_lds_min", "orbit_skew", "tile_block_min_axes"; "stamp_base" / "stamp_cap" / "stamp_used" (debug build
- * with device-side wall-clock stamps, csrc/smr_device.h).  Read-only counters through
- * smr_get_option: "jit_compiles", "jit_hits", "jit_failures", "jit_compile_ms", "overlap_any" / "overlap_ordered" /
- * "overlap_fences" (launches dispatched without / with the barrier bit inside overlap windows, fences issued); "eager_launches",
- * "eager_free" / "eager_same" / "eager_cross" (direct launches; executions that conflicted with nothing / one queue / several),
- * "eager_fallback" (executions sent through HIP).
- * Round 5: "seq_self_release" (1: launches recorded for a sequence issue agent-scope write-through stores where the family can and
- * their packets carry no release fence), "eager_self_release" (1: the same on library-owned streams), "self_release_max_bytes"
- * (64 MiB: largest destination for which that is done), "self_release_max_total" (128 MiB: largest footprint of a whole sequence /
- * of the recently written destinations), "nt_store" = 2 (force write-through stores), "tiled_gorder" (-1: HBM-sized transposing
- * copies walk the tile index along the input's unit axis second; 0 canonical; 1 always), "tiled_xpose" (1: the lean kernel for
- * HBM-sized transposing copies), "stream_ua" (1: element-aligned 16-byte vectors + a partial vector per row in STREAM),
- * "allreduce_f64" (0; 1: Float32 / ComplexF32 sums cross the ranks as Float64), "overlap_window_hip" (0; see smr_overlap_begin),
- * "orbit_deal" (experiment).  Read-only: "launches" (kernel launches the library issued, through HIP or directly), "allreduces",
- * "allreduces_inplace".  Environment: $SMR_DIRECT_TIMEOUT_MS (30000: no-progress limit of waits on the direct queues),
+/* Tuning knobs: the analogue of the reference's compile-time constants MINTHREADLENGTH /
+ * BLOCKMEMORYSIZE (src/mapreduce.jl:141,462).  smr_set_option returns SMR_EINVAL for an unknown name and
+ * clears the plan cache (except for the stamp buffer); smr_get_option returns -1 for an unknown name.
+ * Defaults in parentheses; -1 usually means "the planner's rule".
+ *   Families: "force_family" (0 auto, 1 generic, 3 tiled), "jit" (1: runtime compilation of f;
+ *     0 interprets), "max_lds_bytes" (65536).
+ *   TILED: "tile_log2" (0 auto, 10, 12), "tile_lg0".."tile_lg7" (-1: per-dim log2 tile extent),
+ *     "tile_order" (1: orbit-major tile order for permuted views of one buffer), "tile_block" (-1: block
+ *     tile order for distinct arrays with >= 3 unit axes; 0 off; n: blocks of n tiles per dim),
+ *     "tile_block_xcd" (-1: one run of the block list per XCD while the operands fit the Infinity Cache;
+ *     0 never; 1 always), "tiled_vec" (1: 16-byte accesses), "tiled_uavec" (1: ... at element
+ *     alignment), "tiled_edge_first" (1: partly filled last tiles start first), "tiled_persist" (1) /
+ *     "tiled_persist_wpc" (0 auto) / "tiled_persist_min" (32) (persistent pipelined form),
+ *     "tiled_xpose" (1: lean kernel for HBM-sized transposing copies), "tiled_gorder" (-1: those copies
+ *     walk the input's unit axis second; 0 canonical; 1 always).
+ *   ORBIT: "orbit" (1: family on), "orbit_lg" (-1: log2 tile edge), "orbit_min" (150) / "orbit_few" (40)
+ *     (orbit-count thresholds), "orbit_minrun" (16: shortest contiguous run in bytes), "orbit_group" (2:
+ *     super-cell edge of the work list), "orbit_pipe" (-1: persistent pipelined form; 0 never; 1 always),
+ *     "orbit_wgs" (0: cap on the workgroups of that form), "orbit_pair" (1: PAIR form of 4^4 cubes of
+ *     8-byte elements), "orbit_pack" (1: orbits with fewer distinct tiles share a workgroup).
+ *   FLAT: "flat" (1: family for short leading dims that are not powers of two), "flat_wide" (1: one-sided
+ *     form for rows of 65..128 elements in matrices of >= 32 MiB; 2 wherever it applies), "flat2" (1:
+ *     two-sided form; 0 off; 2 wherever it applies), "flat2_pair" (1), "flat2_bytes" (384),
+ *     "flat2_lead_bytes" (512), "flat2_long" (80: two-sided form for long unit-stride dims whose 32 x 32
+ *     tiles would be less full than this per cent; 0 off), "flatb" (1: batched form for small contiguous
+ *     blocks).
+ *   STREAM: "stream_ua" (1: element-aligned 16-byte vectors + a partial vector per row),
+ *     "stream_pack_rows" (1: short rows share a workgroup), "nt_store" (-1: non-temporal stores; 0 never;
+ *     1 always; 2 write-through), "nt_stream_min" (0).
+ *   Reductions: "reduce_blocks" (2048), "reduce_part_wgs" (1024: partial reductions with fewer workgroups
+ *     are split until about this many run), "reduce_part_kind" (-1; 0 general, 1 row, 2 col),
+ *     "reduce_single" (4: split reductions of at most this many chunks fold their partials inside the same
+ *     launch; 0 = always a second launch; a plan that owns partials must not run concurrently with itself
+ *     on two streams), "reduce_row_floor" (-1), "reduce_row_dense" (1), "reduce_col_txlog" (5),
+ *     "reduce_col_exact" (1), "reduce_col_narrow" (1), "nt_load" (-1: non-temporal loads of complete
+ *     reductions; 0 never; 1 always).
+ *   Dispatch: "eager_direct" (1: library-owned streams submit launches themselves), "seq_self_release"
+ *     (1: launches recorded for a sequence issue agent-scope write-through stores where the family can and
+ *     their packets carry no release fence), "eager_self_release" (1: the same on library-owned streams),
+ *     "self_release_max_bytes" (64 MiB: largest destination for which that is done),
+ *     "self_release_max_total" (128 MiB: largest footprint of a whole sequence / of the recently written
+ *     destinations).
+ *   Sharding: "allreduce_f64" (0; 1: Float32 / ComplexF32 sums cross the ranks as Float64).
+ *   Debug builds with device-side wall-clock stamps (csrc/smr_device.h): "stamp_base" / "stamp_cap" /
+ *     "stamp_used"; read-only "stamp_build".
+ *   Read-only counters: "launches" (kernel launches the library issued, through HIP or directly),
+ *     "jit_compiles", "jit_hits", "jit_failures", "jit_compile_ms", "eager_launches", "eager_free" /
+ *     "eager_same" / "eager_cross" (direct launches; executions that conflicted with nothing / one queue /
+ *     several), "eager_fallback" (executions sent through HIP), "eager_kernarg_device", "eager_arg_hits",
+ *     "eager_gpu_only_signals", "allreduces", "allreduces_inplace".
+ * Environment: $SMR_DIRECT_TIMEOUT_MS (30000: no-progress limit of waits on the direct queues),
  * $SMR_DIRECT_SELFTEST (0 skips, "fail" forces the failure path), $SMR_DIRECT_METADATA (0: code-object-v5 rule instead of the
  * metadata), $SMR_SEQ_DIRECT (0: sequences replay through HIP), $SMR_SEQ_STREAM_WAIT (1: hipStreamWaitValue64 where supported),
  * $SMR_RCCL_LIB (which collective library to dlopen).      */

@@ -45,47 +45,25 @@ int launch_reduce_part(const Plan& plan, void* const* bases, hipStream_t s) { SM
 int launch_orbit_map(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_orbit_map) }
 int launch_flat_map(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_flat_map) }
 
-// ---- overlap window: dependency-aware launch order --------------------------------------------------------------------
-// The reference runs the independent halves of a problem as concurrent tasks and waits only where it must
-// (src/mapreduce.jl:203-223: spawn one half, run the other, wait).  On the GPU the analogous unit is the LAUNCH: a 16 MiB
-// launch here is a span of 1.6-3.2 us followed by a 1.6-1.9 us boundary (drain, write-back, next dispatch -- profiles/
-// r03_device_span.txt) that a stream-ordered successor pays even when it touches none of the predecessor's data.  Inside an
-// overlap window (smr_overlap_begin / _end, or any stream made by smr_stream_create) the library therefore keeps, per stream,
-// the byte ranges read and written by the launches that went out since the last ORDERED one; a new launch whose ranges do
-// not conflict with them (no read-after-write, write-after-write or write-after-read) is dispatched without the AQL barrier
-// bit (hipExtAnyOrderLaunch) -- its waves start while the earlier launches are still running or draining -- anything else
-// goes out in order and becomes the new window base.  Closing the window (and, on library-owned streams, every copy /
-// synchronisation the library performs) first issues one ordered empty kernel, so that "the stream's last command has
-// completed" again implies "everything before it has" for whatever follows (events, copies, hipStreamSynchronize).
+// ---- overlap windows and library-owned streams --------------------------------------------------------------------------
+// smr_overlap_begin / _end nest per stream.  HIP ignores the any-order dispatch flag on gfx9 (profiles/r04_overlap.txt), so a window
+// does not change how launches that go through HIP are ordered.  Independent launches overlap where the library dispatches itself:
+// library-owned streams (smr_stream_create, registered here for good) and recorded sequences (smr_seq.cpp).
 namespace {
 struct Span {
     uintptr_t lo, hi;
 };
 struct Window {
-    int depth = 0;        // nesting of smr_overlap_begin
-    bool owned = false;   // smr_stream_create: permanently open
-    bool loose = false;   // the last launch went out without the barrier bit: a fence is due before foreign work
-    int unordered = 0;    // launches since the window base
-    std::vector<Span> reads, writes;
+    int depth = 0;       // nesting of smr_overlap_begin
+    bool owned = false;  // smr_stream_create: permanently registered
 };
 struct Windows {
     std::mutex mu;
     std::unordered_map<void*, Window> map;
-    long stat_any = 0, stat_ordered = 0, stat_fences = 0;
 };
 Windows& windows() {
     static Windows* w = new Windows();
     return *w;
-}
-thread_local unsigned tl_launch_flags = 0;
-constexpr int WINDOW_CAP = 32;  // launches tracked before the window is re-based by an ordered launch
-
-__global__ void k_window_fence() {}
-
-bool overlaps(const std::vector<Span>& v, const Span& x) {
-    for (const Span& y : v)
-        if (x.lo < y.hi && y.lo < x.hi) return true;
-    return false;
 }
 
 // byte ranges one execution of `plan` reads and writes (every operand's bounding range; the plan's own partials)
@@ -113,71 +91,19 @@ void footprint(const Plan& plan, void* const* bases, std::vector<Span>& rd, std:
     }
 }
 
-// decides the ordering of the execution about to be launched on `s`
-void window_admit(const Plan& plan, void* const* bases, hipStream_t s) {
-    tl_launch_flags = 0;
-    // HIP accepts hipExtAnyOrderLaunch and IGNORES it on gfx9 (hip_ext.h says so; device stamps confirm it, profiles/r04_overlap.txt):
-    // on gfx942 / gfx950 a window on a stream that launches through HIP cannot change anything.  The analysis below -- two mutex
-    // acquisitions, a footprint with vector allocations per launch, a fence kernel -- therefore runs only on request (option
-    // "overlap_window_hip" = 1, for a runtime that honours the flag); by default the window API is a no-op for HIP launches, and
-    // independent launches overlap where the library dispatches itself: library-owned streams and recorded sequences (smr_seq.cpp).
-    if (!options().overlap_window_hip) return;
+bool stream_is_owned(hipStream_t s) {
     Windows& W = windows();
     std::lock_guard<std::mutex> g(W.mu);
-    if (W.map.empty()) return;
+    if (W.map.empty()) return false;
     auto it = W.map.find((void*)s);
-    if (it == W.map.end() || (it->second.depth == 0 && !it->second.owned)) return;
-    Window& w = it->second;
-    std::vector<Span> rd, wr;
-    footprint(plan, bases, rd, wr);
-    bool free_ = w.unordered > 0 && w.unordered < WINDOW_CAP;
-    for (size_t i = 0; free_ && i < wr.size(); ++i) free_ = !overlaps(w.reads, wr[i]) && !overlaps(w.writes, wr[i]);
-    for (size_t i = 0; free_ && i < rd.size(); ++i) free_ = !overlaps(w.writes, rd[i]);
-    if (free_) {
-        tl_launch_flags = hipExtAnyOrderLaunch;
-        w.loose = true;
-        ++W.stat_any;
-    } else {
-        w.reads.clear();
-        w.writes.clear();
-        w.unordered = 0;
-        w.loose = false;
-        ++W.stat_ordered;
-    }
-    ++w.unordered;
-    w.reads.insert(w.reads.end(), rd.begin(), rd.end());
-    w.writes.insert(w.writes.end(), wr.begin(), wr.end());
+    return it != W.map.end() && it->second.owned;
 }
 
-// one ordered empty kernel: everything launched before it has completed when it has
-int window_fence_locked(Windows& W, Window& w, hipStream_t s) {
-    w.reads.clear();
-    w.writes.clear();
-    w.unordered = 0;
-    if (!w.loose) return SMR_OK;
-    w.loose = false;
-    ++W.stat_fences;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_window_fence, dim3(1), dim3(64), 0, s);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SMR_OK : hip_error(e, "overlap window fence");
-}
+// on a library-owned stream, what the library submitted directly completes before whatever follows on the stream through HIP ...
 int window_fence(hipStream_t s) {
-    bool owned = false;
-    int rc = SMR_OK;
-    {
-        Windows& W = windows();
-        std::lock_guard<std::mutex> g(W.mu);
-        auto it = W.map.find((void*)s);
-        if (it == W.map.end()) return SMR_OK;
-        owned = it->second.owned;
-        rc = window_fence_locked(W, it->second, s);
-    }
-    if (owned && eager_available(s)) {  // what the library submitted directly completes before whatever follows on the stream through HIP ...
-        const int rc2 = eager_fence_all();
-        eager_note_hip_work(s);        // ... and that HIP work completes before the next direct launch ON THIS STREAM
-        if (rc == SMR_OK) rc = rc2;
-    }
+    if (!stream_is_owned(s) || !eager_available(s)) return SMR_OK;
+    const int rc = eager_fence_all();
+    eager_note_hip_work(s);  // ... and that HIP work completes before the next direct launch ON THIS STREAM
     return rc;
 }
 }  // namespace
@@ -188,21 +114,7 @@ int fence_for_foreign_work(hipStream_t s) { return window_fence(s); }
 static std::atomic<long> g_launches{0};
 void count_launch() { g_launches.fetch_add(1, std::memory_order_relaxed); }
 
-unsigned take_launch_flags() {
-    const unsigned f = tl_launch_flags;
-    tl_launch_flags = 0;
-    return f;
-}
-
 static int execute_family(const Plan& plan, void* const* bases, hipStream_t s);
-
-static bool stream_is_owned(hipStream_t s) {
-    Windows& W = windows();
-    std::lock_guard<std::mutex> g(W.mu);
-    if (W.map.empty()) return false;
-    auto it = W.map.find((void*)s);
-    return it != W.map.end() && it->second.owned;
-}
 
 static int execute(const Plan& plan, void* const* bases, hipStream_t s) {
     if (!jit_no_launch() && !recorder()) {
@@ -230,11 +142,8 @@ static int execute(const Plan& plan, void* const* bases, hipStream_t s) {
             if (int rc3 = eager_fence_all()) return rc3;
             eager_note_hip_work(s);
         }
-        window_admit(plan, bases, s);
     }
-    const int rc = execute_family(plan, bases, s);
-    tl_launch_flags = 0;  // an execution that launched nothing must not leak its flag to the next one
-    return rc;
+    return execute_family(plan, bases, s);
 }
 
 static int execute_family(const Plan& plan, void* const* bases, hipStream_t s) {
@@ -482,6 +391,87 @@ void cache_clear_locked(Cache& c, std::vector<PlanRef>& dropped) {
     c.lru.clear();
     c.map.clear();
 }
+
+// ---- options (smr_set_option / smr_get_option; include/strided_hip.h describes them) -------------------------------------
+// Every option that plans depend on, by family.  The stamp buffer, tile_lg0..7 and the read-only counters are handled
+// by name in the two functions.
+struct OptionField {
+    const char* name;
+    i64 Options::*field;
+};
+const OptionField OPTION_FIELDS[] = {
+    {"force_family", &Options::force_family},
+    {"jit", &Options::jit},
+    {"max_lds_bytes", &Options::max_lds_bytes},
+    // TILED
+    {"tile_log2", &Options::tile_log2},
+    {"tile_order", &Options::tile_order},
+    {"tile_block", &Options::tile_block},
+    {"tile_block_xcd", &Options::tile_block_xcd},
+    {"tiled_vec", &Options::tiled_vec},
+    {"tiled_uavec", &Options::tiled_uavec},
+    {"tiled_edge_first", &Options::tiled_edge_first},
+    {"tiled_persist", &Options::tiled_persist},
+    {"tiled_persist_wpc", &Options::tiled_persist_wpc},
+    {"tiled_persist_min", &Options::tiled_persist_min},
+    {"tiled_xpose", &Options::tiled_xpose},
+    {"tiled_gorder", &Options::tiled_gorder},
+    // ORBIT
+    {"orbit", &Options::orbit},
+    {"orbit_lg", &Options::orbit_lg},
+    {"orbit_min", &Options::orbit_min},
+    {"orbit_few", &Options::orbit_few},
+    {"orbit_minrun", &Options::orbit_minrun},
+    {"orbit_group", &Options::orbit_group},
+    {"orbit_pipe", &Options::orbit_pipe},
+    {"orbit_wgs", &Options::orbit_wgs},
+    {"orbit_pair", &Options::orbit_pair},
+    {"orbit_pack", &Options::orbit_pack},
+    // FLAT
+    {"flat", &Options::flat},
+    {"flat_wide", &Options::flat_wide},
+    {"flat2", &Options::flat2},
+    {"flat2_pair", &Options::flat2_pair},
+    {"flat2_bytes", &Options::flat2_bytes},
+    {"flat2_lead_bytes", &Options::flat2_lead_bytes},
+    {"flat2_long", &Options::flat2_long},
+    {"flatb", &Options::flatb},
+    // STREAM
+    {"stream_ua", &Options::stream_ua},
+    {"stream_pack_rows", &Options::stream_pack_rows},
+    {"nt_store", &Options::nt_store},
+    {"nt_stream_min", &Options::nt_stream_min},
+    // reductions
+    {"reduce_blocks", &Options::reduce_blocks},
+    {"reduce_part_wgs", &Options::reduce_part_wgs},
+    {"reduce_part_kind", &Options::reduce_part_kind},
+    {"reduce_single", &Options::reduce_single},
+    {"reduce_row_floor", &Options::reduce_row_floor},
+    {"reduce_row_dense", &Options::reduce_row_dense},
+    {"reduce_col_txlog", &Options::reduce_col_txlog},
+    {"reduce_col_exact", &Options::reduce_col_exact},
+    {"reduce_col_narrow", &Options::reduce_col_narrow},
+    {"nt_load", &Options::nt_load},
+    // dispatch on library-owned streams and in sequences
+    {"eager_direct", &Options::eager_direct},
+    {"eager_self_release", &Options::eager_self_release},
+    {"seq_self_release", &Options::seq_self_release},
+    {"self_release_max_bytes", &Options::self_release_max_bytes},
+    {"self_release_max_total", &Options::self_release_max_total},
+    // sharding
+    {"allreduce_f64", &Options::allreduce_f64},
+};
+
+i64 Options::*option_field(const std::string& n) {
+    for (const OptionField& f : OPTION_FIELDS)
+        if (n == f.name) return f.field;
+    return nullptr;
+}
+
+// "tile_lg0" .. "tile_lg7": the canonical dim, else -1
+int tile_lg_dim(const std::string& n) {
+    return n.size() == 8 && n.rfind("tile_lg", 0) == 0 && n[7] >= '0' && n[7] <= '7' ? n[7] - '0' : -1;
+}
 }  // namespace
 
 extern "C" {
@@ -552,13 +542,7 @@ int smr_overlap_begin(void* stream) {
     if (rc) return rc;
     Windows& W = windows();
     std::lock_guard<std::mutex> g(W.mu);
-    Window& w = W.map[stream];
-    if (w.depth++ == 0 && !w.owned) {  // the first launch of a window is always ordered (after whatever the caller queued before)
-        w.reads.clear();
-        w.writes.clear();
-        w.unordered = 0;
-        w.loose = false;
-    }
+    ++W.map[stream].depth;
     return SMR_OK;
 }
 
@@ -567,11 +551,8 @@ int smr_overlap_end(void* stream) {
     std::lock_guard<std::mutex> g(W.mu);
     auto it = W.map.find(stream);
     if (it == W.map.end() || it->second.depth == 0) return set_error(SMR_EINVAL, "smr_overlap_end without smr_overlap_begin on this stream");
-    Window& w = it->second;
-    if (--w.depth > 0) return SMR_OK;
-    const int rc = window_fence_locked(W, w, (hipStream_t)stream);
-    if (!w.owned) W.map.erase(it);
-    return rc;
+    if (--it->second.depth == 0 && !it->second.owned) W.map.erase(it);
+    return SMR_OK;
 }
 
 int smr_overlap_fence(void* stream) { return window_fence((hipStream_t)stream); }
@@ -597,7 +578,6 @@ int smr_stream_destroy(void* stream) {
         std::lock_guard<std::mutex> g(W.mu);
         auto it = W.map.find(stream);
         if (it == W.map.end() || !it->second.owned) return set_error(SMR_EINVAL, "smr_stream_destroy: not a stream made by smr_stream_create");
-        (void)window_fence_locked(W, it->second, (hipStream_t)stream);
         W.map.erase(it);
     }
     (void)eager_fence_if_active();
@@ -903,76 +883,14 @@ int smr_shard_ex(const smr_problem* p, int nshards, int shard, uint32_t local_op
 int smr_set_option(const char* name, int64_t value) {
     if (!name) return set_error(SMR_EINVAL, "null option name");
     Options& o = options();
-    std::string n(name);
-    bool ok = true;
-    if (n == "force_family") o.force_family = value;
-    else if (n == "tile_log2") o.tile_log2 = value;
-    else if (n == "tile_order") o.tile_order = value;
-    else if (n == "tile_block") o.tile_block = value;
-    else if (n == "tile_block_xcd") o.tile_block_xcd = value;
-    else if (n == "tile_block_min_axes") o.tile_block_min_axes = value;
-    else if (n == "reduce_blocks") o.reduce_blocks = value;
-    else if (n == "jit") o.jit = value;
-    else if (n == "tiled_persist") o.tiled_persist = value;
-    else if (n == "stream_u") o.stream_u = value;
-    else if (n == "stream_pack_rows") o.stream_pack_rows = value;
-    else if (n == "flatb") o.flatb = value;
-    else if (n == "flat2_long") o.flat2_long = value;
-    else if (n == "flat2_pair") o.flat2_pair = value;
-    else if (n == "eager_direct") o.eager_direct = value;
-    else if (n == "reduce_tree") o.reduce_tree = value;
-    else if (n == "tiled_persist_wpc") o.tiled_persist_wpc = value;
-    else if (n == "tiled_persist_min") o.tiled_persist_min = value;
-    else if (n == "reduce_part_kind") o.reduce_part_kind = value;
-    else if (n == "reduce_col_txlog") o.reduce_col_txlog = value;
-    else if (n == "reduce_part_wgs") o.reduce_part_wgs = value;
-    else if (n == "reduce_single") o.reduce_single = value;
-    else if (n == "reduce_col_narrow") o.reduce_col_narrow = value;
-    else if (n == "reduce_col_exact") o.reduce_col_exact = value;
-    else if (n == "reduce_row_floor") o.reduce_row_floor = value;
-    else if (n == "reduce_row_dense") o.reduce_row_dense = value;
-    else if (n == "flat2") o.flat2 = value;
-    else if (n == "flat_wide") o.flat_wide = value;
-    else if (n == "flat2_bytes") o.flat2_bytes = value;
-    else if (n == "flat2_lead_bytes") o.flat2_lead_bytes = value;
-    else if (n == "tiled_vec") o.tiled_vec = value;
-    else if (n == "tiled_uavec") o.tiled_uavec = value;
-    else if (n == "tiled_force_edge") o.tiled_force_edge = value;
-    else if (n == "tiled_edge_first") o.tiled_edge_first = value;
-    else if (n == "nt_stream_min") o.nt_stream_min = value;
-    else if (n == "nt_store") o.nt_store = value;
-    else if (n == "seq_self_release") o.seq_self_release = value;
-    else if (n == "eager_self_release") o.eager_self_release = value;
-    else if (n == "overlap_window_hip") o.overlap_window_hip = value;
-    else if (n == "tiled_gorder") o.tiled_gorder = value;
-    else if (n == "tiled_xpose") o.tiled_xpose = value;
-    else if (n == "stream_ua") o.stream_ua = value;
-    else if (n == "allreduce_f64") o.allreduce_f64 = value;
-    else if (n == "self_release_max_bytes") o.self_release_max_bytes = value;
-    else if (n == "self_release_max_total") o.self_release_max_total = value;
-    else if (n == "nt_load") o.nt_load = value;
-    else if (n == "orbit_min") o.orbit_min = value;
-    else if (n == "orbit_few") o.orbit_few = value;
-    else if (n == "orbit_pack") o.orbit_pack = value;
-    else if (n == "orbit_pair") o.orbit_pair = value;
-    else if (n == "orbit_pipe") o.orbit_pipe = value;
-    else if (n == "orbit_lds_min") o.orbit_lds_min = value;
-    else if (n == "orbit_group") o.orbit_group = value;
-    else if (n == "orbit_wgs") o.orbit_wgs = value;
-    else if (n == "orbit_minrun") o.orbit_minrun = value;
-    else if (n == "orbit_skew") o.orbit_skew = value;
-    else if (n == "orbit_deal") o.orbit_deal = value;
-    else if (n == "flat") o.flat = value;
-    else if (n == "stamp_base" || n == "stamp_cap" || n == "stamp_used") {  // no plan depends on these: keep the cache
+    const std::string n(name);
+    if (n == "stamp_base" || n == "stamp_cap" || n == "stamp_used") {  // no plan depends on these: keep the cache
         (n == "stamp_base" ? o.stamp_base : (n == "stamp_cap" ? o.stamp_cap : o.stamp_used)) = value;
         return SMR_OK;
     }
-    else if (n == "orbit_lg") o.orbit_lg = value;
-    else if (n == "orbit") o.orbit = value;
-    else if (n == "max_lds_bytes") o.max_lds_bytes = value;
-    else if (n.rfind("tile_lg", 0) == 0 && n.size() == 8 && n[7] >= '0' && n[7] <= '7') o.tile_lg[n[7] - '0'] = value;
-    else ok = false;
-    if (!ok) return set_error(SMR_EINVAL, "unknown option " + n);
+    if (i64 Options::*f = option_field(n)) o.*f = value;
+    else if (const int d = tile_lg_dim(n); d >= 0) o.tile_lg[d] = value;
+    else return set_error(SMR_EINVAL, "unknown option " + n);
     Cache& c = cache();
     std::vector<PlanRef> dropped;
     {
@@ -986,93 +904,29 @@ int smr_set_option(const char* name, int64_t value) {
 int64_t smr_get_option(const char* name) {
     if (!name) return -1;
     const Options& o = options();
-    std::string n(name);
-    if (n == "force_family") return o.force_family;
-    if (n == "tile_log2") return o.tile_log2;
-    if (n == "tile_order") return o.tile_order;
-    if (n == "tile_block") return o.tile_block;
-    if (n == "tile_block_xcd") return o.tile_block_xcd;
-    if (n == "tile_block_min_axes") return o.tile_block_min_axes;
-    if (n == "reduce_blocks") return o.reduce_blocks;
-    if (n == "jit") return o.jit;
-    if (n == "tiled_persist") return o.tiled_persist;
-    if (n == "stream_u") return o.stream_u;
-    if (n == "stream_pack_rows") return o.stream_pack_rows;
-    if (n == "flatb") return o.flatb;
-    if (n == "flat2_long") return o.flat2_long;
-    if (n == "flat2_pair") return o.flat2_pair;
-    if (n == "eager_direct") return o.eager_direct;
+    const std::string n(name);
+    if (i64 Options::*f = option_field(n)) return o.*f;
+    if (const int d = tile_lg_dim(n); d >= 0) return o.tile_lg[d];
+    if (n == "stamp_base") return o.stamp_base;
+    if (n == "stamp_cap") return o.stamp_cap;
+    if (n == "stamp_used") return o.stamp_used;
+    if (n == "stamp_build") return SMR_STAMP;
+    // read-only counters
+    if (n == "launches") return g_launches.load();
+    if (n == "jit_compiles") return jit_stats().compiles;
+    if (n == "jit_hits") return jit_stats().hits;
+    if (n == "jit_failures") return jit_stats().failures;
+    if (n == "jit_compile_ms") return (int64_t)jit_stats().compile_ms;
     if (n == "eager_launches") return eager_stat(0);
     if (n == "eager_free") return eager_stat(1);
     if (n == "eager_same") return eager_stat(2);
     if (n == "eager_cross") return eager_stat(3);
     if (n == "eager_fallback") return eager_stat(4);
     if (n == "eager_kernarg_device") return eager_stat(5);
-    if (n == "eager_arg_hits") return eager_stat(7);
     if (n == "eager_gpu_only_signals") return eager_stat(6);
-    if (n == "reduce_tree") return o.reduce_tree;
-    if (n == "tiled_persist_wpc") return o.tiled_persist_wpc;
-    if (n == "tiled_persist_min") return o.tiled_persist_min;
-    if (n == "reduce_part_kind") return o.reduce_part_kind;
-    if (n == "reduce_col_txlog") return o.reduce_col_txlog;
-    if (n == "reduce_part_wgs") return o.reduce_part_wgs;
-    if (n == "reduce_single") return o.reduce_single;
-    if (n == "reduce_col_narrow") return o.reduce_col_narrow;
-    if (n == "reduce_col_exact") return o.reduce_col_exact;
-    if (n == "reduce_row_floor") return o.reduce_row_floor;
-    if (n == "reduce_row_dense") return o.reduce_row_dense;
-    if (n == "flat2") return o.flat2;
-    if (n == "flat_wide") return o.flat_wide;
-    if (n == "flat2_bytes") return o.flat2_bytes;
-    if (n == "flat2_lead_bytes") return o.flat2_lead_bytes;
-    if (n == "overlap_any" || n == "overlap_ordered" || n == "overlap_fences") {
-        Windows& W = windows();
-        std::lock_guard<std::mutex> g(W.mu);
-        return n == "overlap_any" ? W.stat_any : (n == "overlap_ordered" ? W.stat_ordered : W.stat_fences);
-    }
-    if (n == "jit_compiles") return jit_stats().compiles;
-    if (n == "jit_hits") return jit_stats().hits;
-    if (n == "jit_failures") return jit_stats().failures;
-    if (n == "jit_compile_ms") return (int64_t)jit_stats().compile_ms;
-    if (n == "tiled_vec") return o.tiled_vec;
-    if (n == "tiled_uavec") return o.tiled_uavec;
-    if (n == "tiled_force_edge") return o.tiled_force_edge;
-    if (n == "tiled_edge_first") return o.tiled_edge_first;
-    if (n == "nt_stream_min") return o.nt_stream_min;
-    if (n == "nt_store") return o.nt_store;
-    if (n == "seq_self_release") return o.seq_self_release;
-    if (n == "eager_self_release") return o.eager_self_release;
-    if (n == "overlap_window_hip") return o.overlap_window_hip;
-    if (n == "tiled_gorder") return o.tiled_gorder;
-    if (n == "tiled_xpose") return o.tiled_xpose;
-    if (n == "stream_ua") return o.stream_ua;
-    if (n == "allreduce_f64") return o.allreduce_f64;
-    if (n == "launches") return g_launches.load();
+    if (n == "eager_arg_hits") return eager_stat(7);
     if (n == "allreduces") return comm_stat(0);
     if (n == "allreduces_inplace") return comm_stat(1);
-    if (n == "self_release_max_bytes") return o.self_release_max_bytes;
-    if (n == "self_release_max_total") return o.self_release_max_total;
-    if (n == "nt_load") return o.nt_load;
-    if (n == "orbit_min") return o.orbit_min;
-    if (n == "orbit_few") return o.orbit_few;
-    if (n == "orbit_pack") return o.orbit_pack;
-    if (n == "orbit_pair") return o.orbit_pair;
-    if (n == "orbit_pipe") return o.orbit_pipe;
-    if (n == "orbit_lds_min") return o.orbit_lds_min;
-    if (n == "orbit_group") return o.orbit_group;
-    if (n == "orbit_wgs") return o.orbit_wgs;
-    if (n == "orbit_minrun") return o.orbit_minrun;
-    if (n == "orbit_skew") return o.orbit_skew;
-    if (n == "orbit_deal") return o.orbit_deal;
-    if (n == "flat") return o.flat;
-    if (n == "stamp_base") return o.stamp_base;
-    if (n == "stamp_cap") return o.stamp_cap;
-    if (n == "stamp_used") return o.stamp_used;
-    if (n == "stamp_build") return SMR_STAMP;
-    if (n == "orbit_lg") return o.orbit_lg;
-    if (n == "orbit") return o.orbit;
-    if (n == "max_lds_bytes") return o.max_lds_bytes;
-    if (n.rfind("tile_lg", 0) == 0 && n.size() == 8 && n[7] >= '0' && n[7] <= '7') return o.tile_lg[n[7] - '0'];
     return -1;
 }
 

@@ -120,10 +120,7 @@ inline OpTab make_optab(const Canon& c, void* const* bases) {
     return t;
 }
 
-// Every kernel launch of the library goes through SMR_LAUNCH.  take_launch_flags() hands out -- ONCE, to the first launch of
-// the execution in progress -- the AQL ordering the overlap window decided on (smr_api.cpp: hipExtAnyOrderLaunch = the
-// dispatch packet goes out without the barrier bit, so its waves may start while earlier, independent launches of the
-// same stream are still draining); every later launch of the same execution (a folding pass) is ordered as usual.
+// Every kernel launch of the library goes through SMR_LAUNCH.
 // While a sequence records (smr_seq.cpp) nothing is launched: the launch is appended to the recorder with its arguments packed the
 // way the kernarg segment holds them (every argument at its natural alignment, in order).
 template <class T> inline void pack_arg(std::vector<unsigned char>& b, const T& v) {
@@ -148,9 +145,7 @@ template <class... A> inline void record_launch(std::vector<RecLaunch>* rec, con
             break;                                                                                                     \
         }                                                                                                              \
         ::smr::count_launch();                                                                                        \
-        const unsigned smr_lf_ = ::smr::take_launch_flags();                                                           \
-        if (smr_lf_) hipExtLaunchKernelGGL(kern, grid, block, (unsigned)(lds), s, nullptr, nullptr, smr_lf_, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern, grid, block, lds, s, __VA_ARGS__);                                               \
+        hipLaunchKernelGGL(kern, grid, block, lds, s, __VA_ARGS__);                                                    \
     } while (0)
 
 // A failed earlier HIP call (e.g. an attribute query) must not be mistaken for a launch failure.

@@ -5,7 +5,6 @@
 // The top part (types, ProgD, enums) is also compiled by hiprtc (SMR_JIT, see smr_jit.cpp): device
 // code only there, everything host-side sits behind #ifndef SMR_JIT.
 #ifndef SMR_JIT
-#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -259,7 +258,6 @@ struct Plan {
 };
 
 // Options (smr_set_option)
-constexpr int RED_SHARDS = 16;       // shard partials per output of the two-level in-launch fold
 constexpr int RED_COUNTERS = 16384;  // arrival counters per reduction plan (one per output group of a split reduction)
 struct Options {
     i64 force_family = 0;
@@ -267,7 +265,6 @@ struct Options {
     i64 tile_order = 1;      // orbit-major tile order for inputs that are permuted views of one buffer
     i64 tile_block = -1;     // distinct arrays with >= 3 unit axes: tiles in compact blocks of this many per dim (0 = natural
                              // order, -1 = blocks of 4 for grids of >= 1024 tiles)
-    i64 tile_block_min_axes = 3;  // experiment: 2 = block order for plain transposes as well
     i64 tile_block_xcd = -1; // block-ordered list in one contiguous run per XCD: 0 never, 1 always, -1 = while the operands fit the Infinity Cache
     i64 jit = 1;             // compile unrecognised f-programs with hiprtc (0 = always interpret)
     i64 reduce_col_txlog = 5;   // COL form: log2 of the lanes along kept dim 0 (cap)
@@ -291,9 +288,6 @@ struct Options {
     i64 tiled_persist_wpc = 0;  // workgroups per CU of that form (0 = derived from threads / LDS)
     i64 tiled_persist_min = 32; // ... used when the work list holds at least this many rounds (measured: 64^4 / 4000^2
                                 // problems with ~16 rounds are 2-12 % faster in the classic form, 128^4 / 8192^2 ones 6-18 % slower)
-    i64 stream_u = 0;           // experiment: vectors per lane of the STREAM family (runtime-compiled functors only)
-    i64 reduce_tree = 0;        // split reductions of up to this many chunks (beyond reduce_single) fold inside the launch through TWO levels of arrival
-                                // counters (shards of ~sqrt(chunks)); 0: a second launch folds, as in rounds 1-3
     i64 eager_direct = 1;       // launches on a library-owned stream (smr_stream_create) are submitted by the library itself (AQL packets on its HSA queues,
                                 // queue chosen by the data dependencies); 0: through HIP, in stream order
     i64 flat2_long = 80;        // two-sided FLAT form for LONG unit-stride dims (arrays of >= 8 MiB) whose 32 x 32 tiles would be under this many per cent full (0: off)
@@ -301,13 +295,11 @@ struct Options {
     i64 stream_pack_rows = 1;   // STREAM: rows of 129 .. 128*U vectors share a workgroup (U / ceil(n0v / 256) rows per lane) instead of one row segment per workgroup
     i64 tiled_vec = 1;       // 16-byte global accesses in the tiled family when alignment allows
     i64 tiled_edge_first = 1; // partly filled last tiles start first: one ragged grid dim runs slowest and backwards, several only backwards (2 / 3: one of the two forms always)
-    i64 tiled_force_edge = 0; // experiment: run the bounds-checking variant of TILED even when every tile is whole
     i64 tiled_uavec = 1;     // ... and at element alignment (odd extents / row strides), partial vectors of ragged tiles element by element
     i64 orbit = 1;           // FAM_ORBIT for inputs that are permuted views of one buffer (0 = classic tiled kernel)
     i64 stream_ua = 1;          // STREAM: element-aligned 16-byte vectors + a partial vector per row for rows that are not whole aligned vectors
     i64 tiled_xpose = 1;        // HBM-sized transposing copies (one staged input, 128 x 32 tiles, whole tiles, 8- / 16-byte elements) run the lean kernel k_xpose_big
     i64 tiled_gorder = -1;      // TILED grid-dim order: 0 canonical, 1 the staged input's split unit axis second, -1 = that for HBM-sized 128 x 32 transposes
-    i64 overlap_window_hip = 0; // 1: launches of an overlap window that go through HIP carry hipExtAnyOrderLaunch when independent (ignored by HIP on gfx9: default off)
     i64 allreduce_f64 = 0;      // smr_mapreduce_sharded: Float32 / ComplexF32 sums cross the ranks as Float64 (staging + two launches); default: in the destination's type
     i64 eager_self_release = 1; // launches of library-owned streams use write-through stores and their packets drop the release fence while the recently written destinations fit the caches (profiles/r05_eager_self_release.txt: bench step issued eagerly 6.19 -> 5.35 us, dependent chain 3.24 -> 2.93, independent launches 2.17 -> 1.62 us)
     i64 seq_self_release = 1;   // launches recorded for a sequence use write-through stores where the family can, and their packets drop the release fence
@@ -320,12 +312,9 @@ struct Options {
                              // next to each other on one XCD
     i64 stamp_base = 0, stamp_cap = 0, stamp_used = 0;  // SMR_STAMP builds: device buffer of 8-byte words for wave stamps
     i64 flat = 1;            // FAM_FLAT for transposing unary maps with short non-power-of-two leading dims (0 = TILED as in round 2)
-    i64 orbit_deal = 0;      // experiment: 1 = super-cell c runs on XCD c mod 8 (instead of one contiguous run of the list per XCD)
-    i64 orbit_skew = 0;      // experiment: diagonal enumeration of the ORBIT super-cells (step per super-cell along the other dims)
     i64 orbit_minrun = 16;   // shortest contiguous run (bytes) an ORBIT tile edge may have (round 3: 16 -- Float32 4^4 cubes at 32^4:
                              // 5.60 -> 4.61 us, 24^4 3.41 -> 3.01 us; larger sizes keep the 8^4 cubes)
     i64 orbit_wgs = 0;       // persistent ORBIT form: cap on the number of workgroups (0 = as many as the machine holds at once)
-    i64 orbit_lds_min = 0;   // experiment: request at least this much LDS per ORBIT workgroup (limits residency)
     i64 orbit_pair = 1;      // 4^4 cubes of 8-byte elements: two orbits per workgroup, unit-axis neighbours in the lane pairs (64-byte runs in slot 0)
     i64 orbit_pack = 1;      // orbits with fewer distinct tiles than |G| share a workgroup (0: one workgroup per orbit, tiles repeated)
     i64 orbit_few = 40;      // fewer orbits than this even with the smallest admissible edge: classic tiled kernel
@@ -380,12 +369,9 @@ struct JitStats {
 };
 JitStats jit_stats();
 
-// AQL ordering of the next kernel launch of the calling thread (0 or hipExtAnyOrderLaunch), consumed by the first launch that asks
-// (SMR_LAUNCH in smr_dispatch.h, jit_launch): set by the overlap window in smr_api.cpp
-unsigned take_launch_flags();
-// Before work that does NOT go through the library's launchers is queued on `s` (a collective, a copy): inside an overlap window / on a
-// library-owned stream everything the library launched so far is ordered before it (and, on an owned stream, that work before the
-// library's next direct launch).  No-op on ordinary streams.
+// Before work that does NOT go through the library's launchers is queued on `s` (a collective, a copy): on a library-owned stream
+// everything the library launched so far is ordered before it, and that work before the library's next direct launch.  No-op on
+// other streams.
 int fence_for_foreign_work(hipStream_t s);
 
 // Recording (smr_seq.cpp): while a sequence records, SMR_LAUNCH / jit_launch append what they WOULD launch instead of launching it

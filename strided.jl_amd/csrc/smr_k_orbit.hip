@@ -819,8 +819,7 @@ static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
     const bool wt = has_wt_store<OVec<T, V>>::value && (opt.nt_store == 2 || want_self_release(plan));
     if (wt) a.nts = 2;
     const unsigned block = 1u << a.ntlog;
-    size_t lds = (size_t)NG * (sizeof(T) << o.tilelog);
-    if (opt.orbit_lds_min > 0) lds = std::max(lds, (size_t)opt.orbit_lds_min);  // experiment: fewer resident workgroups per CU
+    const size_t lds = (size_t)NG * (sizeof(T) << o.tilelog);
     a.nlist = (int32_t)o.wmap.size();
     unsigned grid = (unsigned)o.wmap.size();
     if (PIPE) {

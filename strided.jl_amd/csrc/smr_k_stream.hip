@@ -194,15 +194,11 @@ __global__ void __launch_bounds__(256) k_stream_map(StreamArgs a, F f SMR_STAMP_
     SMR_STAMP_END
 }
 
-template <class T, class F, bool MIXED, int V, int UOVR = 0>
+template <class T, class F, bool MIXED, int V>
 static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     const Canon& c = plan.c;
     // vectors in flight per lane: measured on 256-512 MiB maps, 2 x 16 B beats 4 (2-3 %) and 8 (5-8 % worse)
-    constexpr int U = UOVR ? UOVR : ((sizeof(T) * V >= 16) ? 2 : 8);
-    if constexpr (is_jit<F>::value && UOVR == 0) {  // experiment (runtime-compiled functors only): option stream_u
-        if (options().stream_u == 2) return go<T, F, MIXED, V, 2>(plan, bases, s, f);
-        if (options().stream_u == 8) return go<T, F, MIXED, V, 8>(plan, bases, s, f);
-    }
+    constexpr int U = (sizeof(T) * V >= 16) ? 2 : 8;
     StreamArgs a;
     std::memset(&a, 0, sizeof a);
     a.ops = make_optab(c, bases);

@@ -1255,7 +1255,6 @@ static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua =
     // ragged extents: the lean kernel plus bounds checks in the workgroups that sit on a last, partly filled tile (round 6; every
     // ragged problem used to take variant 7 -- lane tables from memory, 64-bit origins, order lookups -- and paid ~2 us for it:
     // transposes of 7200 x 100 Float64 5.4 us against 3.0 us for 7200 x 128, profiles/r06_ragged_tiles.txt)
-    if (options().tiled_force_edge) ragged = true;  // experiment: the bounds-checking variant on whole tiles (what does the variant itself cost?)
     bool pv = false;  // does some operand's vector axis end in a partial vector?
     if constexpr (V > 1) {
         for (int k = 0; k < c.M; ++k) {

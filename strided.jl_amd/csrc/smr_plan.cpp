@@ -933,7 +933,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
     }
     std::vector<char> seen((size_t)o.ntiles_total, 0);
     std::vector<uint32_t> list;
-    std::vector<uint32_t> cell_of;  // super-cell (linear index, dim 0 fastest) every list entry came from
     i64 ncell[MAXN], cells = 1;
     int sub[MAXN];
     for (int d = 0; d < c.N; ++d) {
@@ -948,17 +947,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
         for (int d = 0; d < c.N; ++d) {
             cc[d] = r % ncell[d];
             r /= ncell[d];
-        }
-        // skewed enumeration (option orbit_skew): consecutive super-cells step along the DIAGONAL of the tiled dims, so
-        // that the orbits in flight together differ in every coordinate -- at power-of-two sizes the lines of one cube
-        // share a handful of L2 sets (strides 1 KiB / 128 KiB / 16 MiB), and neighbours along one dim share them too
-        if (opt.orbit_skew) {
-            int first = -1;
-            for (int d = 0; d < c.N; ++d)
-                if (sub[d] > 1 || o.lg[d] > 0) {
-                    if (first < 0) first = d;
-                    else cc[d] = (cc[d] + cc[first] * opt.orbit_skew) % ncell[d];
-                }
         }
         for (int q = 0; q < nsub; ++q) {
             i64 t[MAXN];
@@ -979,7 +967,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
             if (seen[(size_t)root]) continue;
             seen[(size_t)root] = 1;
             list.push_back((uint32_t)root);
-            cell_of.push_back((uint32_t)cell);
         }
     }
     o.norbits = (int)list.size();
@@ -994,7 +981,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
     auto field = [](int g, int k) { return (unsigned)((g * 8 + k) * 2); };  // k = input index - 1
     std::vector<Wg> wgs;
     std::vector<char> wg_full;      // the workgroup holds ONE orbit of |G| distinct tiles, slot g = g_g . t (PAIR form)
-    std::vector<uint32_t> cell_wg;  // super-cell of every workgroup (orbit_deal = 1)
     // pending[s]: orbits of s distinct tiles waiting for company -- (tiles, per-tile reads as indices into the orbit's own tiles)
     struct Part {
         uint32_t tile[MAXG];
@@ -1002,7 +988,7 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
         int n;
     };
     std::vector<Part> pending[MAXG + 1];
-    auto emit_packed = [&](int sdist, uint32_t cell) {
+    auto emit_packed = [&](int sdist) {
         std::vector<Part>& pp = pending[sdist];
         if (pp.empty()) return;
         Wg w;
@@ -1021,7 +1007,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
         }
         wgs.push_back(w);
         wg_full.push_back(0);
-        cell_wg.push_back(cell);
         pp.clear();
     };
     for (size_t i = 0; i < list.size(); ++i) {
@@ -1056,7 +1041,6 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
             }
             wgs.push_back(w);
             wg_full.push_back(ndist == o.ng && NS == o.ng ? 1 : 0);
-            cell_wg.push_back(cell_of[i]);
             continue;
         }
         Part q;
@@ -1066,9 +1050,9 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
             for (int k = 1; k < c.M; ++k) q.rd[j][k] = dix[o.slot[first[j]][k]];
         }
         pending[ndist].push_back(q);
-        if ((int)pending[ndist].size() * ndist + ndist > NS) emit_packed(ndist, cell_of[i]);
+        if ((int)pending[ndist].size() * ndist + ndist > NS) emit_packed(ndist);
     }
-    for (int sd = 1; sd <= MAXG; ++sd) emit_packed(sd, cell_wg.empty() ? 0u : cell_wg.back());
+    for (int sd = 1; sd <= MAXG; ++sd) emit_packed(sd);
     constexpr int NX = 8;
     // ---- PAIR form: two slot sets per workgroup, unit-axis neighbours first ----------------------------------------------------------
     o.pair_ok = false;
@@ -1080,7 +1064,7 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
                 ++ntd;
                 if (o.lg[d] != 2) cubes = false;
             }
-        if (opt.orbit_pair && o.ng == 4 && NS == 4 && ntd == 4 && cubes && o.tilelog == 8 && es == 8 && o.vec == 2 && o.lg[0] == 2 && opt.orbit_deal != 1 && wgs.size() >= 16) {
+        if (opt.orbit_pair && o.ng == 4 && NS == 4 && ntd == 4 && cubes && o.tilelog == 8 && es == 8 && o.vec == 2 && o.lg[0] == 2 && wgs.size() >= 16) {
             std::vector<int> owner((size_t)o.ntiles_total, -1);
             for (size_t i = 0; i < wgs.size(); ++i)
                 if (wg_full[i])
@@ -1164,30 +1148,17 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
             o.pair_ok = true;
         }
     }
-    auto place = [&](size_t pos, const Wg& w) {
-        for (int g = 0; g < NS; ++g) o.wtile[pos * NS + g] = w.tile[g];
-        o.wmap[pos] = w.map;
-    };
-    if (opt.orbit_deal == 1) {
-        // experiment (round 5): super-cell c runs on XCD c mod 8 -- consecutive super-cells step along dim 0, so at any time the eight
-        // XCDs work on eight neighbours along the buffer's unit axis (whole DRAM pages chip-wide) while the partner halves of every
-        // line still meet inside one XCD's L2
-        std::vector<size_t> perx[NX];
-        for (size_t i = 0; i < wgs.size(); ++i) perx[cell_wg[i] % NX].push_back(i);
-        size_t cs2 = 0;
-        for (int x = 0; x < NX; ++x) cs2 = std::max(cs2, perx[x].size());
-        o.wtile.assign(cs2 * NX * NS, 0xffffffffu);
-        o.wmap.assign(cs2 * NX, 0);
-        for (int x = 0; x < NX; ++x)
-            for (size_t sl = 0; sl < perx[x].size(); ++sl) place(sl * NX + x, wgs[perx[x][sl]]);
-        return true;
-    }
     const size_t cs = (wgs.size() + NX - 1) / NX;
     o.wtile.assign(cs * NX * NS, 0xffffffffu);
     o.wmap.assign(cs * NX, 0);
     for (size_t x = 0; x < (size_t)NX; ++x)
         for (size_t sl = 0; sl < cs; ++sl)
-            if (x * cs + sl < wgs.size()) place(sl * NX + x, wgs[x * cs + sl]);
+            if (x * cs + sl < wgs.size()) {
+                const Wg& w = wgs[x * cs + sl];
+                const size_t pos = sl * NX + x;
+                for (int g = 0; g < NS; ++g) o.wtile[pos * NS + g] = w.tile[g];
+                o.wmap[pos] = w.map;
+            }
     return true;
 }
 
@@ -1452,7 +1423,7 @@ static bool plan_tiles(const Canon& c, TilePlan& t) {
     // 128 x 32 transposing tiles run one-shot: measured round 3 (tools/perm_block_ab.py, Float64) permutedims! 128^4
     // 826 -> 791 us, (2,3,4,1) 866 -> 745 us, (3,4,1,2) 801 -> 699 us, transpose 16384^2 859 -> 719 us, 8192^2 / 12000^2 tie
     t.no_persist = big_transpose;
-    if (t.ord.empty() && (na >= 3 || (o.tile_block_min_axes <= 2 && na >= 2)) && o.tile_block != 0 && (o.tile_block > 0 || o.tile_block == -2 || t.grid >= 1024)) {
+    if (t.ord.empty() && na >= 3 && o.tile_block != 0 && (o.tile_block > 0 || o.tile_block == -2 || t.grid >= 1024)) {
         // one contiguous run of the list per XCD while the operands fit the Infinity Cache (a block's partner pieces meet in ONE
         // L2: 48^4 45.0 -> 38.5 us); round-robin once they stream from HBM (64^4: 157 vs 175 us)
         const bool xcd_runs = o.tile_block_xcd > 0 || (o.tile_block_xcd < 0 && c.algbytes <= ((i64)256 << 20));
@@ -2113,8 +2084,7 @@ int make_plan(const smr_problem* p, Plan& plan) {
                 plan.part_split = (int)split;
             }
             if (plan.part_split > 1) {
-                // chunk partials, then RED_SHARDS shard partials per output (two-level in-launch fold, smr_k_reduce.hip)
-                plan.scratch_bytes = (size_t)c.nout * ((size_t)plan.part_split + RED_SHARDS) * es;
+                plan.scratch_bytes = (size_t)c.nout * (size_t)plan.part_split * es;  // chunk partials
                 plan.red_blocks = plan.part_split;  // > 1: the API allocates the partials buffer
             }
         }

@@ -10,7 +10,7 @@
 //   * a hipGraph with two branches is executed node by node through that same eager path (8.2-8.8 us per step), only single-chain
 //     graphs get the batched submission.
 // So the library submits its own packets: a sequence is recorded ONCE (every launch's kernel object, grid and kernarg block, resident
-// in device memory), the dependency analysis of the overlap window (smr_api.cpp: byte ranges read / written) decides per launch whether
+// in device memory), a dependency analysis (byte ranges read / written: footprint() in smr_api.cpp) decides per launch whether
 // its packet carries the barrier bit, and a replay is N x 64-byte stores into the queue rings plus a doorbell per queue -- ~0.1 us of
 // host time per launch, no host thread in the loop.  Independent launches go to DIFFERENT hardware queues (one per dependency
 // component): inside one queue the packet processor runs consecutive dispatches one after the other on their agent-scope fences even

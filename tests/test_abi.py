@@ -262,6 +262,13 @@ def test_invalid_problems_return_einval():
     p.fprog_len = 1
     assert lib.smr_plan_create(C.byref(p), C.byref(h)) == L.SMR_EINVAL
     assert lib.smr_set_option(b"no_such_option", 1) == L.SMR_EINVAL
+    # retired experiment switches (and the overlap-window counters) are unknown names now
+    for name in (b"reduce_tree", b"overlap_window_hip", b"stream_u", b"orbit_deal", b"orbit_skew", b"orbit_lds_min",
+                 b"tiled_force_edge", b"tile_block_min_axes"):
+        assert lib.smr_set_option(name, 1) == L.SMR_EINVAL, name
+        assert lib.smr_get_option(name) == -1, name
+    for name in (b"overlap_any", b"overlap_ordered", b"overlap_fences"):
+        assert lib.smr_get_option(name) == -1, name
 
 
 def test_map_into_zero_stride_destination_is_unsupported():

@@ -94,44 +94,32 @@ RED_SHAPES = [((100, 90, 80, 7), (1, 2, 3), np.float32), ((100, 90, 80, 7), (1, 
 
 
 @pytest.mark.parametrize("shape,dims,dt", RED_SHAPES)
-def test_two_level_in_launch_fold(shape, dims, dt):
+def test_split_reduction_fold(shape, dims, dt):
     rng = np.random.default_rng(sum(shape))
     a = rng.integers(-8, 9, size=shape).astype(dt)          # small integers: every summation order gives the same float
     A = dview(a)
-    got = {}
-    for tree in (1024, 0):
-        S.set_option("reduce_tree", tree)
-        try:
-            r1 = S.sum(A, dims=dims).toarray()
-            r2 = S.sum(A, dims=dims).toarray()
-            m = S.maximum(A, dims=dims).toarray()
-        finally:
-            S.set_option("reduce_tree", 0)
-        assert np.array_equal(r1, r2)
-        got[tree] = (r1, m)
-    want = a.astype(np.float64).sum(axis=dims, keepdims=True)
-    assert np.array_equal(got[1024][0].astype(np.float64), want) and np.array_equal(got[0][0].astype(np.float64), want)
-    assert np.array_equal(got[1024][1], a.max(axis=dims, keepdims=True)) and np.array_equal(got[0][1], a.max(axis=dims, keepdims=True))
+    r1 = S.sum(A, dims=dims).toarray()
+    r2 = S.sum(A, dims=dims).toarray()
+    m = S.maximum(A, dims=dims).toarray()
+    assert np.array_equal(r1, r2)
+    assert np.array_equal(r1.astype(np.float64), a.astype(np.float64).sum(axis=dims, keepdims=True))
+    assert np.array_equal(m, a.max(axis=dims, keepdims=True))
 
 
-def test_two_level_fold_is_reproducible_and_accurate_on_real_data():
+def test_split_fold_is_reproducible_and_accurate_on_real_data():
     rng = np.random.default_rng(5)
     a = rng.standard_normal((100, 50400)).astype(np.float32)
     A = dview(a)
-    S.set_option("reduce_tree", 1024)   # off by default: measured slower than the second launch (profiles/r04_reduce_tree_ab.txt)
-    try:
-        runs = [S.sum(A, dims=(1,)).toarray() for _ in range(5)]
-        for r in runs[1:]:
-            assert np.array_equal(r, runs[0])                    # fold order is fixed by the lane layout, not by arrival order
-        want = a.astype(np.float64).sum(axis=1, keepdims=True)
-        assert np.allclose(runs[0], want, rtol=0, atol=2e-3 * np.sqrt(50400))
-        # accumulate INTO a destination with an initop (the epilogue of the last shard applies it once)
-        out = dview(np.full((100, 1), 2.0, dtype=np.float32))
-        S.mapreducedim_(lambda x: x, "+", out, A)
-        sync()
-        assert np.allclose(out.toarray(), want + 2.0, rtol=0, atol=2e-3 * np.sqrt(50400))
-    finally:
-        S.set_option("reduce_tree", 0)
+    runs = [S.sum(A, dims=(1,)).toarray() for _ in range(5)]
+    for r in runs[1:]:
+        assert np.array_equal(r, runs[0])                    # fold order is fixed by the lane layout, not by arrival order
+    want = a.astype(np.float64).sum(axis=1, keepdims=True)
+    assert np.allclose(runs[0], want, rtol=0, atol=2e-3 * np.sqrt(50400))
+    # accumulate INTO a destination with an initop (the fold's epilogue applies it once)
+    out = dview(np.full((100, 1), 2.0, dtype=np.float32))
+    S.mapreducedim_(lambda x: x, "+", out, A)
+    sync()
+    assert np.allclose(out.toarray(), want + 2.0, rtol=0, atol=2e-3 * np.sqrt(50400))
 
 
 @pytest.mark.parametrize("shape", [(100, 90, 80), (257, 129, 65), (17, 33, 65, 31), (200, 300, 70), (999, 1001), (130, 70, 50, 9), (1400, 1500)])
