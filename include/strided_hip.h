@@ -121,7 +121,12 @@ typedef enum {
 
 /* f-program: the fused N-ary elementwise function f (the CaptureArgs functor tree of
  * src/broadcast.jl:67-98, or map!'s closure) serialised as postfix code, two bytes per
- * instruction: {opcode, immediate}.  The program must leave exactly one value.          */
+ * instruction: {opcode, immediate}.  The program must leave exactly one value.
+ * Opcode ranges: 0..7 push, unary 8..31 and 96..127, binary 32..63 and 128..159, ternary 64..95.
+ * The opcodes from 65 and from 96 on (the "math" opcodes: powers, fma, more of Base's math and the bitwise
+ * operations) run in runtime-compiled kernels only: a plan that would interpret such a program (option
+ * "jit" = 0, or no runtime compiler) is refused with SMR_EUNSUPPORTED.  Where Julia throws (DomainError),
+ * they give the IEEE result (pow(-8.0, 1/3) is NaN).                                      */
 typedef enum {
     SMR_OP_ARG = 0,   /* push input #imm (1-based: ops[imm]), conj flag applied           */
     SMR_OP_CONST = 1, /* push fconsts[2*imm] + i*fconsts[2*imm+1]                         */
@@ -168,7 +173,39 @@ typedef enum {
     SMR_OP_EQ = 42,
     SMR_OP_NE = 43,
     /* ternary: pop c, pop b, pop a, push (real(a) != 0 ? b : c)                           */
-    SMR_OP_SELECT = 64
+    SMR_OP_SELECT = 64,
+    SMR_OP_FMA = 65, /* fma(a, b, c) and muladd(a, b, c): fused on real types; complex: Julia's muladd(::Complex, ...) with fused parts */
+    /* unary math (runtime-compiled kernels only) */
+    SMR_OP_POWI = 96, /* Base.literal_pow(^, x, Val(n)) / x ^ n for an integer literal n = imm as int8 (-128..127): n = 0 1 2 3 -1 -2
+                         are one(x), x, x*x, x*x*x, inv(x), inv(x)^2; other n: Float32 via Float64 pown rounded once, Float64
+                         pown, complex power_by_squaring (of inv(x) for n < 0), integers (n >= 0 only) wrapping        */
+    SMR_OP_TAN = 97,
+    SMR_OP_ASIN = 98,
+    SMR_OP_ACOS = 99,
+    SMR_OP_ATAN = 100,
+    SMR_OP_SINH = 101,
+    SMR_OP_COSH = 102,
+    SMR_OP_EXP2 = 103,
+    SMR_OP_EXPM1 = 104,
+    SMR_OP_LOG2 = 105,
+    SMR_OP_LOG10 = 106,
+    SMR_OP_LOG1P = 107,
+    SMR_OP_CBRT = 108,
+    SMR_OP_FLOOR = 109,
+    SMR_OP_CEIL = 110,
+    SMR_OP_TRUNC = 111,
+    SMR_OP_ROUND = 112, /* RoundNearest: ties to even (each part of a complex value)                                    */
+    SMR_OP_SIGN = 113,  /* keeps NaN and +-0; complex: z / abs(z), 0 for z = 0                                          */
+    SMR_OP_NOT = 114,   /* ~ on integers (bitwise complement); Bool ! / ~ is XOR with true                              */
+    /* binary math (runtime-compiled kernels only); ops without a complex form act on real parts (imaginary part 0) */
+    SMR_OP_POW = 128,   /* a ^ b                                                                                        */
+    SMR_OP_ATAN2 = 129, /* atan(a, b) = atan(y, x)                                                                      */
+    SMR_OP_HYPOT = 130,
+    SMR_OP_REM = 131,   /* rem (Julia's %): truncated, the sign of a; integers: non-zero constant divisors only          */
+    SMR_OP_MOD = 132,   /* mod: floored, the sign of b; integers: non-zero constant divisors only                       */
+    SMR_OP_AND = 133,   /* & | xor on integer (and Bool) values; in a float class on the values converted to Int64       */
+    SMR_OP_OR = 134,
+    SMR_OP_XOR = 135
 } smr_opcode;
 
 /* One StridedView operand: (parent, size, strides, offset, op) of the reference's

@@ -129,6 +129,11 @@ const UNARY = Dict((-) => 8, abs => 9, abs2 => 10, conj => 11, real => 12, imag 
 const BINARY = Dict((+) => 32, (-) => 33, (*) => 34, (/) => 35, min => 36, max => 37, (<) => 38, (<=) => 39, (>) => 40,
                     (>=) => 41, (==) => 42, (!=) => 43)
 const OP_ARG, OP_CONST, OP_ROUND32, OP_WIDEN, OP_SELECT = 0x00, 0x01, 0x15, 0x16, 0x40
+# math opcodes (runtime-compiled kernels only): x^n for an integer literal n is POWI (n in the immediate), fma / muladd FMA, !x / ~x on Bool xor(x, true)
+const UNARY_MATH = Dict(tan => 97, asin => 98, acos => 99, atan => 100, sinh => 101, cosh => 102, exp2 => 103, expm1 => 104, log2 => 105,
+                        log10 => 106, log1p => 107, cbrt => 108, floor => 109, ceil => 110, trunc => 111, round => 112, sign => 113, (~) => 114)
+const BINARY_MATH = Dict((^) => 128, atan => 129, hypot => 130, rem => 131, mod => 132, (&) => 133, (|) => 134, xor => 135)
+const OP_FMA, OP_POWI, OP_XOR, UNARY_ALL, BINARY_ALL = 0x41, 0x60, 0x87, merge(UNARY, UNARY_MATH), merge(BINARY, BINARY_MATH)
 const NARROW, WIDE = (Float32, ComplexF32), (Float64, ComplexF64)
 mutable struct Prog
     code::Vector{UInt8}
@@ -139,11 +144,7 @@ mutable struct Prog
 end
 # every emit! returns the Julia type of the value it pushed: Julia types each operation of a fused expression
 # separately, the library computes one class per call -> ROUND32 after operations Julia carries out in 32 bits
-function emit!(p::Prog, ::Arg)
-    p.nextarg += 1
-    push!(p.code, OP_ARG, UInt8(p.nextarg))
-    return p.eltypes[p.nextarg]
-end
+emit!(p::Prog, ::Arg) = (p.nextarg += 1; push!(p.code, OP_ARG, UInt8(p.nextarg)); p.eltypes[p.nextarg])
 struct ArgK                                    # argument k of a traced closure (explicit index; `Arg` counts occurrences)
     k::Int
 end
@@ -153,21 +154,30 @@ function emit!(p::Prog, x::Number)
     push!(p.code, OP_CONST, UInt8(length(p.consts) ÷ 2 - 1))
     return typeof(x)
 end
-function round32!(p::Prog, T)
-    p.wide && T in NARROW && push!(p.code, OP_ROUND32, 0x00)
-    return T
-end
+round32!(p::Prog, T) = (p.wide && T in NARROW && push!(p.code, OP_ROUND32, 0x00); T)
+valn(::Val{n}) where {n} = n
 function emit!(p::Prog, c::CaptureArgs)
     f, args = c.f, c.args
-    if length(args) == 1 && haskey(UNARY, f)
-        T = emit!(p, args[1])
-        push!(p.code, UNARY[f], 0x00)
+    f === Base.literal_pow && length(args) == 3 && args[3] isa Val && return emit!(p, CaptureArgs(^, (args[2], valn(args[3]))))  # A .^ 2
+    if f === (^) && length(args) == 2 && args[2] isa Integer && -128 <= args[2] <= 127
+        T = emit!(p, args[1]); push!(p.code, OP_POWI, UInt8(args[2] & 0xff))
+        return round32!(p, Base.promote_op(^, T, Int))
+    elseif f in (fma, muladd) && length(args) == 3
+        Ts = map(a -> emit!(p, a), args); push!(p.code, OP_FMA, 0x00)
+        return round32!(p, Base.promote_op(f, Ts...))
+    elseif f in (!, ~) && length(args) == 1 && (T = emit!(p, args[1])) === Bool
+        emit!(p, true); push!(p.code, OP_XOR, 0x00)
+        return Bool
+    elseif f === (~) && length(args) == 1      # (T: the operand's type, from the condition above)
+        T <: Integer || throw(Unsupported("~ on $T")); push!(p.code, UNARY_MATH[~], 0x00); return T
+    elseif length(args) == 1 && haskey(UNARY_ALL, f)
+        T = emit!(p, args[1]); push!(p.code, UNARY_ALL[f], 0x00)
         return round32!(p, Base.promote_op(f, T))
-    elseif haskey(BINARY, f) && (length(args) == 2 || f in (+, *, min, max))
+    elseif haskey(BINARY_ALL, f) && (length(args) == 2 || f in (+, *, min, max))
         T = emit!(p, args[1])                  # Julia's +(a,b,c,d) folds left
         for a in args[2:end]
             T = Base.promote_op(f, T, emit!(p, a))
-            push!(p.code, BINARY[f], 0x00)
+            push!(p.code, BINARY_ALL[f], 0x00)
             round32!(p, T)
         end
         return T
@@ -205,14 +215,16 @@ node(x::Number) = x
 jltype(::Traced{T}) where {T} = T
 jltype(x::Number) = typeof(x)
 traced(f, args...) = Traced{Base.promote_op(f, map(jltype, args)...)}(CaptureArgs(f, map(node, args)))
-for f in keys(UNARY)
+for f in keys(UNARY) ∪ keys(UNARY_MATH) ∪ [!]
     @eval (::typeof($f))(x::Traced) = traced($f, x)
 end
-for f in keys(BINARY)
+for f in keys(BINARY) ∪ keys(BINARY_MATH)
     @eval (::typeof($f))(x::Traced, y::Traced) = traced($f, x, y)
     @eval (::typeof($f))(x::Traced, y::Number) = traced($f, x, y)
     @eval (::typeof($f))(x::Number, y::Traced) = traced($f, x, y)
 end
+Base.:^(x::Traced, n::Integer) = traced(^, x, n); Base.literal_pow(::typeof(^), x::Traced, ::Val{n}) where {n} = x^n
+(::Union{typeof(fma),typeof(muladd)})(x::Traced, y::Number, z::Number) = traced(fma, x, y, z)
 Base.ifelse(c::Traced{Bool}, x::Number, y::Number) = Traced{promote_type(jltype(x), jltype(y))}(CaptureArgs(ifelse, (node(c), node(x), node(y))))
 function fprogram(f, eltypes, desttype)
     tree = try
@@ -226,13 +238,8 @@ end
 # map!'s plain functions: identity / conj / a few arities of + and *
 fprogram(::typeof(identity), eltypes, desttype) = Prog(UInt8[OP_ARG, 1], Float64[], 1, DataType[], false)
 fprogram(::typeof(conj), eltypes, desttype) = Prog(UInt8[OP_ARG, 1, 11, 0], Float64[], 1, DataType[], false)
-function fprogram(f::Union{typeof(+),typeof(*)}, eltypes, desttype)
-    p = Prog(UInt8[OP_ARG, 1], Float64[], 1, DataType[], false)
-    for k in 2:length(eltypes)
-        push!(p.code, OP_ARG, UInt8(k), BINARY[f], 0x00)
-    end
-    return p
-end
+fprogram(f::Union{typeof(+),typeof(*)}, eltypes, desttype) =
+    Prog(UInt8[OP_ARG, 1, (UInt8[OP_ARG, k, BINARY[f], 0x00][i] for k in 2:length(eltypes) for i in 1:4)...], Float64[], 1, DataType[], false)
 
 const REDOPS = Dict(nothing => 0, (+) => 1, Base.add_sum => 1, (*) => 2, Base.mul_prod => 2, min => 3, max => 4, (&) => 5, (|) => 6)
 redcode(op) = get(() -> throw(Unsupported("reduction $op")), REDOPS, op)

@@ -33,7 +33,11 @@ OPCODES = dict(
     NEG=8, ABS=9, ABS2=10, CONJ=11, REAL=12, IMAG=13, SQRT=14, EXP=15, LOG=16, SIN=17, COS=18,
     TANH=19, INV=20, ROUND32=21, WIDEN=22,
     ADD=32, SUB=33, MUL=34, DIV=35, MIN=36, MAX=37, LT=38, LE=39, GT=40, GE=41, EQ=42, NE=43,
-    SELECT=64,
+    SELECT=64, FMA=65,
+    # math opcodes: runtime-compiled kernels only (include/strided_hip.h)
+    POWI=96, TAN=97, ASIN=98, ACOS=99, ATAN=100, SINH=101, COSH=102, EXP2=103, EXPM1=104, LOG2=105, LOG10=106, LOG1P=107,
+    CBRT=108, FLOOR=109, CEIL=110, TRUNC=111, ROUND=112, SIGN=113, NOT=114,
+    POW=128, ATAN2=129, HYPOT=130, REM=131, MOD=132, AND=133, OR=134, XOR=135,
 )
 
 

@@ -126,7 +126,8 @@ def _sv_make(op, *args):
 
 
 StridedView._make = staticmethod(_sv_make)
-for _name in ("__add__", "__radd__", "__sub__", "__rsub__", "__mul__", "__rmul__", "__truediv__",
+for _name in ("__add__", "__radd__", "__sub__", "__rsub__", "__mul__", "__rmul__", "__truediv__", "__pow__", "__rpow__",
+              "__mod__", "__rmod__", "__and__", "__rand__", "__or__", "__ror__", "__xor__", "__rxor__", "__invert__",
               "__rtruediv__", "__neg__", "__pos__", "__abs__", "__lt__", "__le__", "__gt__", "__ge__"):
     setattr(StridedView, _name, getattr(E._OpsMixin, _name))
 

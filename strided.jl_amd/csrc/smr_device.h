@@ -256,6 +256,59 @@ struct mathx_real {
         return a;
     }
     static SMR_DEV bool truthy(R a) { return a != R(0); }
+
+    // The math opcodes (strided_hip.h: 65, 96..127, 128..159).  Runtime-compiled kernels only: FJit calls them with the opcode and
+    // the exponent as template arguments, the interpreter never does (its switch stays as small as it is, csrc/smr_plan.cpp refuses
+    // to interpret such a program).  Float32 calls the Float32 entry points of the device math library.
+    template <int N>
+    static SMR_DEV R powi(R a) {
+        if constexpr (N == 0) return R(1);
+        else if constexpr (N == 1) return a;
+        else if constexpr (N == 2) return a * a;
+        else if constexpr (N == 3) return a * a * a;
+        else if constexpr (N == -1) return R(1) / a;
+        else if constexpr (N == -2) { const R i = R(1) / a; return i * i; }
+        else return (R)::powi((double)a, N);  // Julia: Float32 ^ n in Float64, rounded once; Float64: pown (within 1 ulp)
+    }
+    static SMR_DEV R fma3(R a, R b, R c) { return fma(a, b, c); }
+    template <int OP>
+    static SMR_DEV R ext_un(R a) {
+        if constexpr (OP == SMR_OP_TAN) return tan(a);
+        else if constexpr (OP == SMR_OP_ASIN) return asin(a);
+        else if constexpr (OP == SMR_OP_ACOS) return acos(a);
+        else if constexpr (OP == SMR_OP_ATAN) return atan(a);
+        else if constexpr (OP == SMR_OP_SINH) return sinh(a);
+        else if constexpr (OP == SMR_OP_COSH) return cosh(a);
+        else if constexpr (OP == SMR_OP_EXP2) return exp2(a);
+        else if constexpr (OP == SMR_OP_EXPM1) return expm1(a);
+        else if constexpr (OP == SMR_OP_LOG2) return log2(a);
+        else if constexpr (OP == SMR_OP_LOG10) return log10(a);
+        else if constexpr (OP == SMR_OP_LOG1P) return log1p(a);
+        else if constexpr (OP == SMR_OP_CBRT) return cbrt(a);
+        else if constexpr (OP == SMR_OP_FLOOR) return floor(a);
+        else if constexpr (OP == SMR_OP_CEIL) return ceil(a);
+        else if constexpr (OP == SMR_OP_TRUNC) return trunc(a);
+        else if constexpr (OP == SMR_OP_ROUND) return rint(a);  // round-to-nearest-even mode: Julia's RoundNearest
+        else if constexpr (OP == SMR_OP_SIGN) return (a == R(0) || a != a) ? a : copysign(R(1), a);
+        else if constexpr (OP == SMR_OP_NOT) return (R)(~(ix64)a);
+        else return a;
+    }
+    template <int OP>
+    static SMR_DEV R ext_bin(R a, R b) {
+        if constexpr (OP == SMR_OP_POW) return pow(a, b);
+        else if constexpr (OP == SMR_OP_ATAN2) return atan2(a, b);
+        else if constexpr (OP == SMR_OP_HYPOT) return hypot(a, b);
+        else if constexpr (OP == SMR_OP_REM) return fmod(a, b);
+        else if constexpr (OP == SMR_OP_MOD) {  // Julia's mod(::T, ::T) for floats: floored, the result takes the sign of b
+            const R r = fmod(a, b);
+            if (r == R(0)) return copysign(r, b);
+            return ((r > R(0)) != (b > R(0))) ? r + b : r;
+        }
+        else if constexpr (OP == SMR_OP_AND) return (R)((ix64)a & (ix64)b);
+        else if constexpr (OP == SMR_OP_OR) return (R)((ix64)a | (ix64)b);
+        else if constexpr (OP == SMR_OP_XOR) return (R)((ix64)a ^ (ix64)b);
+        else return a;
+    }
 };
 template <> struct mathx<float> : mathx_real<float> {};
 template <> struct mathx<double> : mathx_real<double> {};
@@ -298,6 +351,38 @@ template <> struct mathx<ix64> {
         return a;
     }
     static SMR_DEV bool truthy(ix64 a) { return a != 0; }
+
+    // math opcodes (runtime-compiled kernels only); the planner admits x ^ n for n >= 0, floor / ceil / trunc / round (identities),
+    // sign, ~, & | xor, fma (= a*b + c) and rem / mod by a non-zero constant
+    template <int N>
+    static SMR_DEV ix64 powi(ix64 a) {
+        U r = 1, x = (U)a;
+        for (int n = N < 0 ? 0 : N; n > 0; n >>= 1) {  // the product mod 2^64 does not depend on its order
+            if (n & 1) r *= x;
+            x *= x;
+        }
+        return (ix64)r;
+    }
+    static SMR_DEV ix64 fma3(ix64 a, ix64 b, ix64 c) { return (ix64)((U)a * (U)b + (U)c); }
+    template <int OP>
+    static SMR_DEV ix64 ext_un(ix64 a) {
+        if constexpr (OP == SMR_OP_SIGN) return a > 0 ? 1 : (a < 0 ? -1 : 0);
+        else if constexpr (OP == SMR_OP_NOT) return ~a;
+        else return a;  // floor ceil trunc round: identities on integers
+    }
+    template <int OP>
+    static SMR_DEV ix64 ext_bin(ix64 a, ix64 b) {
+        if constexpr (OP == SMR_OP_REM || OP == SMR_OP_MOD) {
+            if (b == 0 || b == -1) return 0;  // (b = 0 is refused by the planner; rem(typemin, -1) = 0 without overflow)
+            const ix64 r = a % b;
+            if constexpr (OP == SMR_OP_MOD) return (r != 0 && ((r < 0) != (b < 0))) ? r + b : r;
+            else return r;
+        }
+        else if constexpr (OP == SMR_OP_AND) return a & b;
+        else if constexpr (OP == SMR_OP_OR) return a | b;
+        else if constexpr (OP == SMR_OP_XOR) return a ^ b;
+        else return a;
+    }
 };
 
 template <class R>
@@ -357,6 +442,59 @@ struct mathx_cx {
         return a;
     }
     static SMR_DEV bool truthy(T a) { return a.re != R(0); }
+
+    // math opcodes (runtime-compiled kernels only).  Complex forms of x ^ n, fma, sinh, cosh, exp2, log2, log10, sign and round;
+    // every other math opcode acts on the real parts and returns imaginary part 0 (front ends never send it a complex value)
+    template <int N>
+    static SMR_DEV T powi(T a) {
+        if constexpr (N == 0) return T{R(1), R(0)};
+        else if constexpr (N == 1) return a;
+        else if constexpr (N == 2) return a * a;
+        else if constexpr (N == 3) return a * a * a;
+        else if constexpr (N == -1) return T{R(1), R(0)} / a;
+        else if constexpr (N == -2) { const T i = T{R(1), R(0)} / a; return i * i; }
+        else {  // Base.power_by_squaring (of inv(z) for n < 0, complex.jl)
+            T x = N < 0 ? T{R(1), R(0)} / a : a;
+            int p = N < 0 ? -N : N;
+            int t = __builtin_ctz(p) + 1;
+            p >>= t;
+            while (--t > 0) x = x * x;
+            T y = x;
+            while (p > 0) {
+                t = __builtin_ctz(p) + 1;
+                p >>= t;
+                while (--t >= 0) x = x * x;
+                y = y * x;
+            }
+            return y;
+        }
+    }
+    // Julia's muladd(::Complex, ::Complex, ::Complex) (complex.jl), every part fused
+    static SMR_DEV T fma3(T a, T b, T c) {
+        return T{fma(a.re, b.re, -fma(a.im, b.im, -c.re)), fma(a.re, b.im, fma(a.im, b.re, c.im))};
+    }
+    template <int OP>
+    static SMR_DEV T ext_un(T a) {
+        if constexpr (OP == SMR_OP_SINH) return T{sinh(a.re) * cos(a.im), cosh(a.re) * sin(a.im)};
+        else if constexpr (OP == SMR_OP_COSH) return T{cosh(a.re) * cos(a.im), sinh(a.re) * sin(a.im)};
+        else if constexpr (OP == SMR_OP_EXP2) {
+            const R e = exp2(a.re), th = a.im * R(0.69314718055994530942);
+            return T{e * cos(th), e * sin(th)};
+        }
+        else if constexpr (OP == SMR_OP_LOG2 || OP == SMR_OP_LOG10) {  // log(z) / log(oftype(real(z), 2 or 10))
+            const R d = OP == SMR_OP_LOG2 ? R(0.69314718055994530942) : R(2.30258509299404568402);
+            return T{log(hypot(a.re, a.im)) / d, atan2(a.im, a.re) / d};
+        }
+        else if constexpr (OP == SMR_OP_SIGN) {
+            if (a.re == R(0) && a.im == R(0)) return a;
+            const R r = hypot(a.re, a.im);
+            return T{a.re / r, a.im / r};
+        }
+        else if constexpr (OP == SMR_OP_ROUND) return T{rint(a.re), rint(a.im)};
+        else return T{mathx_real<R>::template ext_un<OP>(a.re), R(0)};
+    }
+    template <int OP>
+    static SMR_DEV T ext_bin(T a, T b) { return T{mathx_real<R>::template ext_bin<OP>(a.re, b.re), R(0)}; }
 };
 template <> struct mathx<c32> : mathx_cx<float> {};
 template <> struct mathx<c64> : mathx_cx<double> {};

@@ -62,6 +62,8 @@ int with_prog(const Canon& c, Fn&& fn) {
         if (rc != SMR_JIT_UNAVAILABLE) return rc;
         if (jit_dry_run()) return set_error(SMR_EUNSUPPORTED, "runtime compilation is unavailable (hiprtc missing or the generated source failed to compile)");
     }
+    if (prog_uses_math(c.prog))  // the interpreter does not know the math opcodes (smr_device.h: FProg)
+        return set_error(SMR_EUNSUPPORTED, "f-program with a math opcode (pow, fma, tan, rem, &, ...) needs runtime compilation, which is off or unavailable");
     return fn(FProg<T>{c.prog});
 }
 

@@ -93,6 +93,13 @@ enum Family : int {
 };
 
 #ifndef SMR_JIT
+// Does the program hold a math opcode (strided_hip.h: FMA, 96..127, 128..159)?  Those run in runtime-compiled kernels only.
+inline bool prog_uses_math(const ProgD& p) {
+    for (int pc = 0; pc < p.len; ++pc)
+        if (p.code[2 * pc] == SMR_OP_FMA || p.code[2 * pc] >= SMR_OP_POWI) return true;
+    return false;
+}
+
 // Canonical problem: size-1 dims dropped, dims sorted (kept dims by destination stride,
 // then reduced dims), destination strides made positive, jointly contiguous dims fused,
 // identical inputs deduplicated.  GPU analogue of _mapreduce_fuse! + _mapreduce_order!

@@ -55,10 +55,12 @@ static int check_prog(const ProgD& p, int M, int& maxdepth) {
             ++sp;
         } else if (op >= SMR_OP_NEG && op <= SMR_OP_WIDEN) {
             if (sp < 1) return -1;
-        } else if (op >= SMR_OP_ADD && op <= SMR_OP_NE) {
+        } else if (op >= SMR_OP_POWI && op <= SMR_OP_NOT) {
+            if (sp < 1) return -1;
+        } else if ((op >= SMR_OP_ADD && op <= SMR_OP_NE) || (op >= SMR_OP_POW && op <= SMR_OP_XOR)) {
             if (sp < 2) return -1;
             --sp;
-        } else if (op == SMR_OP_SELECT) {
+        } else if (op == SMR_OP_SELECT || op == SMR_OP_FMA) {
             if (sp < 3) return -1;
             sp -= 2;
         } else {
@@ -152,6 +154,64 @@ static bool int_class_fit_julia(const smr_problem* p, const bool* isbool, ProgD&
                 if (a.cong < w) exact(a);
                 if (b.cong < w) { exact(b); }
                 a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                break;
+            }
+            // math opcodes (strided_hip.h 65, 96.., 128..): x ^ n (n >= 0), ~ and & | xor are ring operations; floor ceil trunc round
+            // are identities; sign, rem and mod need exact operands (rem / mod by an Int64 literal: the result is an Int64)
+            case SMR_OP_POWI: case SMR_OP_NOT: {
+                Slot& a = st[sp - 1];
+                if (a.amb) return false;
+                a.prod = pc;
+                if (a.bits == 1) {  // Bool ^ n is a Bool (0 or 1 either way; true ^ 0 = true); ~true would be -2: the front ends send XOR
+                    if (op == SMR_OP_NOT) return false;
+                    break;
+                }
+                a.cong = std::min(a.cong, a.bits);
+                break;
+            }
+            case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: st[sp - 1].prod = pc; break;
+            case SMR_OP_SIGN: {
+                Slot& a = st[sp - 1];
+                exact(a);
+                a.prod = pc;
+                break;
+            }
+            case SMR_OP_REM: case SMR_OP_MOD: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb) return false;
+                exact(a);
+                exact(b);
+                a = {64, true, 64, pc, false};
+                break;
+            }
+            case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb) return false;
+                int w;
+                bool sg;
+                promote(a, b, w, sg);  // Bool & Bool is a Bool
+                if (a.cong < w) exact(a);
+                if (b.cong < w) exact(b);
+                a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                break;
+            }
+            case SMR_OP_FMA: {  // a*b + c, typed as that expression; the product cannot be re-wrapped on its own
+                Slot c = st[--sp], b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb || c.amb) return false;
+                int w, w2;
+                bool sg, sg2;
+                promote(a, b, w, sg);
+                if (a.cong < w) exact(a);
+                if (b.cong < w) exact(b);
+                Slot m = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                promote(m, c, w2, sg2);
+                if (m.bits == 1 && c.bits == 1) { w2 = 64; sg2 = true; }
+                if (m.cong < w2) return false;
+                if (c.cong < w2) exact(c);
+                a = {w2, sg2, w2 == 1 ? 64 : std::min({m.cong, c.cong, w2}), pc, false};
                 break;
             }
             case SMR_OP_MIN: case SMR_OP_MAX: {
@@ -304,6 +364,8 @@ int canonicalise(const smr_problem* p0, Canon& c) {
     int depth = 0;
     if (check_prog(prog, std::max(M0, 1), depth) != 0) return set_error(SMR_EINVAL, "malformed f-program");
     if (depth > STACK) return set_error(SMR_EUNSUPPORTED, "f-program needs more than 8 stack slots");
+    if (!options().jit && prog_uses_math(prog))
+        return set_error(SMR_EUNSUPPORTED, "f-program with a math opcode (pow, fma, tan, rem, &, ...) with option \"jit\" = 0: the interpreter does not run them");
 
     // compute class (Julia promote_type over the operand eltypes, restricted to the four
     // float classes of the reference tests)
@@ -329,7 +391,7 @@ int canonicalise(const smr_problem* p0, Canon& c) {
             if (p->ops[k].dtype == SMR_U64) has_u64 = true;
             if (p->ops[k].dtype >= SMR_I8 && p->ops[k].dtype <= SMR_I64) has_signed = true;
         }
-        bool closed = true, ordered = p->redop == SMR_RED_MIN || p->redop == SMR_RED_MAX;
+        bool closed = true, ordered = p->redop == SMR_RED_MIN || p->redop == SMR_RED_MAX, negpow = false, baddiv = false;
         for (int pc = 0; pc < prog.len && closed; ++pc) {
             const int op = prog.code[2 * pc];
             switch (op) {
@@ -344,6 +406,19 @@ int canonicalise(const smr_problem* p0, Canon& c) {
                 case SMR_OP_EQ: case SMR_OP_NE:
                     eqne = true;
                     break;
+                // math opcodes that stay in the integers (the rest -- pow, the transcendentals -- compute in Float64 like sqrt)
+                case SMR_OP_NOT: case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: case SMR_OP_FMA:
+                case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: break;
+                case SMR_OP_POWI:
+                    if ((int8_t)prog.code[2 * pc + 1] < 0) negpow = true;
+                    break;
+                case SMR_OP_SIGN: ordered = true; break;
+                case SMR_OP_REM: case SMR_OP_MOD: {
+                    ordered = true;
+                    const bool cdiv = pc > 0 && prog.code[2 * (pc - 1)] == SMR_OP_CONST;
+                    if (!cdiv || prog.consts[2 * prog.code[2 * pc - 1]] == 0.0) baddiv = true;
+                    break;
+                }
                 case SMR_OP_CONST: {
                     has_const = true;
                     const double re = prog.consts[2 * prog.code[2 * pc + 1]], im = prog.consts[2 * prog.code[2 * pc + 1] + 1];
@@ -359,6 +434,10 @@ int canonicalise(const smr_problem* p0, Canon& c) {
             if (im != 0.0 || re != std::floor(re) || std::fabs(re) > 9223372036854775808.0) closed = false;
         }
         if (eqne && has_u64 && (has_signed || has_const)) ordered = true;  // (round 5: all-unsigned equality tests are exact and stay on the device)
+        if (allint && negpow)
+            return set_error(SMR_EUNSUPPORTED, "integer x ^ n with a negative literal n (Julia throws DomainError)");
+        if (allint && baddiv)
+            return set_error(SMR_EUNSUPPORTED, "integer rem / mod with a divisor that is not a non-zero constant (Julia throws DivideError on a zero divisor)");
         if (allint && closed && !(has_u64 && ordered)) {
             if (!int_class_fit_julia(p, isbool, prog, &c.int_wraps))
                 return set_error(SMR_EUNSUPPORTED,

@@ -23,6 +23,19 @@ _UNARY = {"neg": "NEG", "abs": "ABS", "abs2": "ABS2", "conj": "CONJ", "real": "R
 _BINARY = {"add": "ADD", "sub": "SUB", "mul": "MUL", "div": "DIV", "min": "MIN", "max": "MAX",
            "lt": "LT", "le": "LE", "gt": "GT", "ge": "GE", "eq": "EQ", "ne": "NE"}
 _NARY_FOLD = {"add", "mul", "min", "max"}  # Julia's +(a,b,c,d) folds left: ((a+b)+c)+d
+# math opcodes (runtime-compiled kernels only, include/strided_hip.h).  "pow" with a Python int literal in int8 range as its
+# exponent is Base.literal_pow: POWI, the exponent in the immediate; "not" on a Bool-typed value is XOR with true
+_UNARY.update({"tan": "TAN", "asin": "ASIN", "acos": "ACOS", "atan": "ATAN", "sinh": "SINH", "cosh": "COSH", "exp2": "EXP2",
+               "expm1": "EXPM1", "log2": "LOG2", "log10": "LOG10", "log1p": "LOG1P", "cbrt": "CBRT", "floor": "FLOOR",
+               "ceil": "CEIL", "trunc": "TRUNC", "round": "ROUND", "sign": "SIGN", "not": "NOT"})
+_BINARY.update({"pow": "POW", "atan2": "ATAN2", "hypot": "HYPOT", "rem": "REM", "mod": "MOD", "and": "AND", "or": "OR",
+                "xor": "XOR"})
+_TERNARY = {"fma": "FMA"}
+_FLOAT_UNARY = {"sqrt", "exp", "log", "sin", "cos", "tanh", "inv", "tan", "asin", "acos", "atan", "sinh", "cosh", "exp2", "expm1",
+                "log2", "log10", "log1p", "cbrt"}
+_BITS = {"and", "or", "xor", "not"}
+_NO_COMPLEX = {"floor", "ceil", "trunc", "cbrt", "hypot", "rem", "mod", "atan2"} | _BITS  # MethodError in Julia
+_NO_COMPLEX_DEVICE = {"tan", "asin", "acos", "atan", "expm1", "log1p", "pow"}          # defined in Julia, not on the device
 
 
 class _OpsMixin:
@@ -51,6 +64,17 @@ class _OpsMixin:
     def __le__(self, o): return self._make("le", self, o)
     def __gt__(self, o): return self._make("gt", self, o)
     def __ge__(self, o): return self._make("ge", self, o)
+    def __pow__(self, o): return self._make("pow", self, o)
+    def __rpow__(self, o): return self._make("pow", o, self)
+    def __mod__(self, o): return self._make("mod", self, o)  # Python's % is floored, like Julia's mod
+    def __rmod__(self, o): return self._make("mod", o, self)
+    def __and__(self, o): return self._make("and", self, o)
+    def __rand__(self, o): return self._make("and", o, self)
+    def __or__(self, o): return self._make("or", self, o)
+    def __ror__(self, o): return self._make("or", o, self)
+    def __xor__(self, o): return self._make("xor", self, o)  # Python's ^ is xor; power is **
+    def __rxor__(self, o): return self._make("xor", o, self)
+    def __invert__(self): return self._make("not", self)
     # == / != stay Python identity semantics; use fn.eq / fn.ne for elementwise comparison
     __hash__ = object.__hash__
 
@@ -76,6 +100,8 @@ class Const(Expr):
     non-array args captured as they are)."""
 
     def __init__(self, value):
+        # a Python int literal: `x ** 3` is Base.literal_pow(^, x, Val(3))
+        self.literal = int(value) if isinstance(value, numbers.Integral) and not isinstance(value, (bool, np.generic)) else None
         if isinstance(value, (np.generic,)):
             self.dtype = value.dtype           # strongly typed, like a Julia Float32 literal
             value = value.item()
@@ -108,7 +134,7 @@ class Const(Expr):
 
 class Call(Expr):
     def __init__(self, op: str, args: tuple):
-        if op not in _UNARY and op not in _BINARY and op != "select":
+        if op not in _UNARY and op not in _BINARY and op not in _TERNARY and op != "select":
             raise NotImplementedError(f"operation {op!r} is outside the device whitelist")
         self.op, self.args = op, args
 
@@ -138,6 +164,72 @@ def trace(f, nargs: int) -> Expr:
 
 
 # ---- serialisation ---------------------------------------------------------------------------------
+def powi_exponent(n):
+    """n of `x ** n` for a Python int literal n in int8 range (POWI), else None (POW)."""
+    if isinstance(n, Call) and n.op == "pow" and isinstance(n.args[1], Const) and n.args[1].literal is not None \
+            and -128 <= n.args[1].literal <= 127:
+        return n.args[1].literal
+    return None
+
+
+def _jl_promote(*ts):
+    """Julia's promote_type over real / complex NumPy dtypes (Bool yields to everything; Int8 with UInt16 is UInt16;
+    a float wins over any integer: Float32 with Int64 is Float32)."""
+    ts = [np.dtype(t) for t in ts]
+    cx = any(t.kind == "c" for t in ts)
+    re = [_real_of(t) for t in ts]
+    fl = [t for t in re if t.kind == "f"]
+    if fl:
+        r = max(fl, key=lambda t: t.itemsize)
+    else:
+        ints = [t for t in re if t != np.bool_]
+        if not ints:
+            r = np.dtype(np.bool_)
+        else:
+            w = max(t.itemsize for t in ints)
+            same = [t for t in ints if t.itemsize == w]
+            r = same[0] if all(t.kind == "i" for t in same) else next(t for t in same if t.kind == "u")
+    if cx:
+        r = np.dtype(np.complex64) if r == np.float32 else np.dtype(np.complex128)
+    return r
+
+
+def _math_dtype(n, ts):
+    """node_dtype of the math opcodes; raises where Julia has no method (TypeError) or the device has none."""
+    strong = [t for t in ts if t is not None]
+    if any(t.kind == "c" for t in strong):
+        if n.op in _NO_COMPLEX:
+            raise TypeError(f"{n.op} has no method for complex values")
+        if n.op in _NO_COMPLEX_DEVICE and powi_exponent(n) is None:
+            from ._lib import UnsupportedOnDevice, SMR_EUNSUPPORTED
+            raise UnsupportedOnDevice(SMR_EUNSUPPORTED, f"complex {n.op} is not available on the device")
+    if n.op in _BITS and any(t.kind in "fc" for t in strong):
+        raise TypeError(f"bitwise {n.op} needs integer or Bool values")
+    if n.op in _FLOAT_UNARY:
+        return _float_of(strong[0]) if strong else np.dtype(np.float64)
+    if n.op in ("atan2", "hypot"):
+        return _float_of(_jl_promote(*strong)) if strong else np.dtype(np.float64)
+    if n.op in ("floor", "ceil", "trunc", "round", "sign", "not"):
+        return strong[0] if strong else None
+    if n.op == "pow":
+        k = powi_exponent(n)
+        if ts[0] is None:
+            return _jl_promote(*strong) if strong else None
+        if k is not None and k < 0 and ts[0].kind in "biu":
+            return np.dtype(np.float64)  # literal_pow: inv(x) of an integer
+        if k is not None or (ts[1] is not None and ts[1].kind in "biu") or (ts[1] is None and n.args[1].literal is not None):
+            return ts[0]  # x ^ n::Integer keeps the type of x
+        return _jl_promote(*strong)
+    if n.op in ("rem", "mod"):
+        # an integer literal is an Int64: mod(::Int16, 7) is an Int64, mod(::Float32, 7) a Float32
+        if any(t.kind in "biu" for t in strong) and not any(t.kind in "fc" for t in strong) and \
+                any(isinstance(a, Const) and a.dtype is None for a in n.args):
+            strong = strong + [np.dtype(np.int64)]
+    if not strong:
+        return None
+    return _jl_promote(*strong)  # and / or / xor (Bool & Bool is a Bool), rem, mod, fma
+
+
 def node_dtype(n, arg_dtypes):
     """Element type Julia would give this sub-expression (None = weakly typed constant)."""
     if isinstance(n, Arg):
@@ -145,6 +237,9 @@ def node_dtype(n, arg_dtypes):
     if isinstance(n, Const):
         return n.dtype
     ts = [node_dtype(a, arg_dtypes) for a in n.args]
+    if n.op in _TERNARY or n.op in ("pow", "atan2", "hypot", "rem", "mod", "and", "or", "xor") or \
+            (n.op in _UNARY and OPCODES[_UNARY[n.op]] >= OPCODES["POWI"]):
+        return _math_dtype(n, ts)
     strong = [t for t in ts if t is not None]
     if n.op in ("lt", "le", "gt", "ge", "eq", "ne"):
         return np.dtype(np.bool_)
@@ -198,7 +293,16 @@ def serialize(e: Expr, arg_dtypes=None, wide: bool = False):
         elif isinstance(node, Const):
             code.extend((OPCODES["CONST"], const_index(node.value)))
         elif isinstance(node, Call):
-            if node.op in _UNARY:
+            k = powi_exponent(node)
+            if k is not None:
+                emit(node.args[0])
+                code.extend((OPCODES["POWI"], k & 0xFF))
+                if rounds(node):
+                    code.extend((OPCODES["ROUND32"], 0))
+            elif node.op == "not" and arg_dtypes is not None and node_dtype(node.args[0], arg_dtypes) == np.bool_:
+                emit(node.args[0])  # !x / ~x on a Bool is xor(x, true): NOT would give ~1 = -2
+                code.extend((OPCODES["CONST"], const_index(1 + 0j), OPCODES["XOR"], 0))
+            elif node.op in _UNARY:
                 emit(node.args[0])
                 code.extend((OPCODES[_UNARY[node.op]], 0))
                 if rounds(node):
@@ -207,6 +311,14 @@ def serialize(e: Expr, arg_dtypes=None, wide: bool = False):
                 for a in node.args:
                     emit(a)
                 code.extend((OPCODES["SELECT"], 0))
+            elif node.op in _TERNARY:
+                if len(node.args) != 3:
+                    raise ValueError(f"{node.op} takes three arguments")
+                for a in node.args:
+                    emit(a)
+                code.extend((OPCODES[_TERNARY[node.op]], 0))
+                if rounds(node):
+                    code.extend((OPCODES["ROUND32"], 0))
             else:
                 if len(node.args) < 2 or (len(node.args) > 2 and node.op not in _NARY_FOLD):
                     raise ValueError(f"{node.op} takes two arguments")

@@ -3,6 +3,7 @@ tracing a map! closure, and on StridedView / Broadcasted operands for dot-fusion
 spelling of `sin.(A)`, `max.(abs.(B1), real.(B3))`, ... from test/othertests.jl:46-66)."""
 from __future__ import annotations
 
+import builtins
 import cmath
 import math
 import numbers
@@ -81,6 +82,76 @@ eq = _binary("eq", lambda a, b: a == b)
 ne = _binary("ne", lambda a, b: a != b)
 
 
+# ---- math opcodes: runtime-compiled kernels only (include/strided_hip.h) -----------------------------------------------
+def _sign(x):
+    if isinstance(x, complex):
+        return x if x == 0 else x / builtins.abs(x)
+    if isinstance(x, numbers.Integral):
+        return type(x)((x > 0) - (x < 0))
+    return x if (x == 0 or x != x) else math.copysign(1.0, x)
+
+
+def _round(x):
+    if isinstance(x, complex):
+        return complex(builtins.round(x.real), builtins.round(x.imag))
+    return x if isinstance(x, numbers.Integral) else float(builtins.round(x))  # Python's round: ties to even, like RoundNearest
+
+
+def _rem(a, b):
+    if isinstance(a, numbers.Integral) and isinstance(b, numbers.Integral):
+        r = builtins.abs(a) % builtins.abs(b)
+        return -r if a < 0 else r
+    return math.fmod(a, b)
+
+
+tan = _unary("tan", _cm(math.tan, cmath.tan))
+asin = _unary("asin", _cm(math.asin, cmath.asin))
+acos = _unary("acos", _cm(math.acos, cmath.acos))
+sinh = _unary("sinh", _cm(math.sinh, cmath.sinh))
+cosh = _unary("cosh", _cm(math.cosh, cmath.cosh))
+exp2 = _unary("exp2", lambda x: 2.0 ** x)
+expm1 = _unary("expm1", math.expm1)
+log2 = _unary("log2", _cm(math.log2, lambda z: cmath.log(z) / math.log(2)))
+log10 = _unary("log10", _cm(math.log10, cmath.log10))
+log1p = _unary("log1p", math.log1p)
+cbrt = _unary("cbrt", lambda x: math.copysign(builtins.abs(x) ** (1.0 / 3.0), x))
+floor = _unary("floor", lambda x: x if isinstance(x, numbers.Integral) else float(math.floor(x)))
+ceil = _unary("ceil", lambda x: x if isinstance(x, numbers.Integral) else float(math.ceil(x)))
+trunc = _unary("trunc", lambda x: x if isinstance(x, numbers.Integral) else float(math.trunc(x)))
+round = _unary("round", _round)  # noqa: A001  RoundNearest (ties to even)
+sign = _unary("sign", _sign)
+not_ = _unary("not", lambda x: not x if isinstance(x, (bool, np.bool_)) else ~x)  # Julia's ~ (! on Bool)
+_atan1 = _unary("atan", _cm(math.atan, cmath.atan))
+_atan2 = _binary("atan2", math.atan2)
+
+
+def atan(y, x=None):
+    """atan(y) or, with two arguments, atan(y, x) (the angle of the point (x, y))."""
+    return _atan1(y) if x is None else _atan2(y, x)
+
+
+hypot = _binary("hypot", math.hypot)
+rem = _binary("rem", _rem)  # truncated (Julia's rem / %)
+mod = _binary("mod", lambda a, b: a % b)  # floored (Julia's mod, Python's %)
+pow = _binary("pow", lambda a, b: a ** b)  # noqa: A001  an int literal exponent in int8 range is Base.literal_pow (POWI)
+and_ = _binary("and", lambda a, b: a & b)
+or_ = _binary("or", lambda a, b: a | b)
+xor = _binary("xor", lambda a, b: a ^ b)
+
+
+def fma(a, b, c):
+    """fma(a, b, c): a*b + c rounded once."""
+    n = _node("fma", a, b, c)
+    if n is not None:
+        return n
+    if all(isinstance(v, numbers.Real) for v in (a, b, c)) and hasattr(math, "fma"):
+        return math.fma(a, b, c)
+    return a * b + c
+
+
+muladd = fma
+
+
 def ifelse(c, a, b):
     n = _node("select", c, a, b)
     if n is not None:
@@ -90,4 +161,4 @@ def ifelse(c, a, b):
 
 select = ifelse
 __all__ = [k for k in list(globals()) if not k.startswith("_") and k not in
-           ("annotations", "cmath", "math", "numbers", "np", "as_expr")]
+           ("annotations", "cmath", "math", "numbers", "np", "as_expr", "builtins")]
