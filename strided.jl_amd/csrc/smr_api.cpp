@@ -26,6 +26,29 @@ int hip_error(hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? SMR_ENOMEM : (e == hipErrorNoDevice ? SMR_ENODEVICE : SMR_EHIP);
 }
 
+int upload_table(void** dst, const void* src, size_t bytes, const char* what) {
+    void* dptr = nullptr;
+    hipError_t e = hipMalloc(&dptr, bytes);
+    if (e != hipSuccess) return hip_error(e, ("hipMalloc(" + std::string(what) + ")").c_str());
+    e = hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dptr);
+        return hip_error(e, ("hipMemcpy(" + std::string(what) + ")").c_str());
+    }
+    *dst = dptr;
+    return SMR_OK;
+}
+
+int cu_count() {
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        (void)hipGetLastError();
+        return n;
+    }();
+    return ncu;
+}
+
 // ---- per-type dispatch ---------------------------------------------------------------------------
 #define SMR_DISPATCH_CT(fn)                                                   \
     switch (plan.c.bitcopy ? SMR_F32 : plan.c.ct) {                           \
@@ -284,12 +307,11 @@ static void plan_free(smr_plan* h) {
     if (!h) return;
     (void)eager_fence_if_active();  // launches submitted directly may still read the plan's tables
     if (h->plan.scratch) (void)hipFree(h->plan.scratch);
-    for (void*& p : h->plan.lanetab)
-        if (p) {
-            (void)hipFree(p);
-            p = nullptr;
+    for (void** p : h->plan.dev_tables())
+        if (*p) {
+            (void)hipFree(*p);
+            *p = nullptr;
         }
-    if (h->plan.ordtab) (void)hipFree(h->plan.ordtab);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     delete h;
 }
@@ -320,8 +342,8 @@ namespace {
 struct PlanDeleter {
     void operator()(smr_plan* h) const {
         if (!h) return;
-        if (h->plan.scratch || h->plan.ordtab || h->plan.lanetab[0] || h->plan.lanetab[1] || h->plan.lanetab[2] || h->plan.lanetab[3])
-        {
+        const auto tabs = h->plan.dev_tables();
+        if (h->plan.scratch || std::any_of(tabs.begin(), tabs.end(), [](void** p) { return *p != nullptr; })) {
             (void)window_fence((hipStream_t)h->stream);
             (void)hipStreamSynchronize((hipStream_t)h->stream);  // queued kernels may still read the tables
         }

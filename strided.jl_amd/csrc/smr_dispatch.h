@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstring>
 #include <initializer_list>
+#include <string>
 #include <vector>
 #endif
 
@@ -65,6 +66,27 @@ int with_prog(const Canon& c, Fn&& fn) {
     if (prog_uses_math(c.prog))  // the interpreter does not know the math opcodes (smr_device.h: FProg)
         return set_error(SMR_EUNSUPPORTED, "f-program with a math opcode (pow, fma, tan, rem, &, ...) needs runtime compilation, which is off or unavailable");
     return fn(FProg<T>{c.prog});
+}
+
+// Opaque element moves (Canon::bitcopy): fn(FIdent<E>{}) with E the element's size.  Only the Float32 object (CT) carries them;
+// NARROW = false leaves out the 1- and 2-byte movers.
+template <class F> struct ident_elem;
+template <class E> struct ident_elem<FIdent<E>> { typedef E type; };
+template <int CT, bool NARROW = true, class Fn>
+int with_bitcopy(const Canon& c, Fn&& fn) {
+    if constexpr (CT != SMR_F32) {
+        return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
+    } else {
+        switch (c.esize[0]) {
+            case 1: if constexpr (NARROW) return fn(FIdent<b8>{}); break;
+            case 2: if constexpr (NARROW) return fn(FIdent<b16>{}); break;
+            case 4: return fn(FIdent<float>{});
+            case 8: return fn(FIdent<double>{});
+            case 16: return fn(FIdent<c64>{});
+            default: if constexpr (NARROW) return fn(FIdent<c64>{}); break;
+        }
+        return set_error(SMR_EINVAL, "flat plan: 1- / 2-byte moves take the generic family");
+    }
 }
 
 constexpr unsigned fbit(int k) { return 1u << k; }
@@ -157,6 +179,43 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_error(e, what);
     return SMR_OK;
+}
+
+// ---- the two halves of a launch --------------------------------------------------------------------
+// Runtime-compiled: the kernel's body is `smr::<body><T, smr::FJit, targs...>(a, <lead>smr::FJit{kc});` on the argument struct
+// `a` of device type `argtype`, from the source file smr_k_<family>.hip.
+inline std::string targ(bool b) { return b ? "true" : "false"; }
+inline std::string targ(int v) { return std::to_string(v); }
+template <class T, class A, class... P>
+int launch_jit(const Canon& c, hipStream_t s, const char* family, const char* argtype, const char* body, const char* lead, unsigned grid,
+               unsigned block, size_t lds, const A& a, P... targs) {
+    JitLaunch l;
+    l.family = family;
+    l.tname = tname<T>();
+    l.argtype = argtype;
+    l.entry = std::string("smr::") + body + "<" + tname<T>() + ", smr::FJit";
+    (void)std::initializer_list<int>{(l.entry += ", " + targ(targs), 0)...};
+    l.entry += std::string(">(a, ") + lead + "smr::FJit{kc});";
+    l.grid = grid;
+    l.block = block;
+    l.lds = lds;
+    l.args = &a;
+    l.argsize = sizeof a;
+    return jit_launch(c, l, s);
+}
+
+// Natively compiled: nothing in a dry run or a prepare-only execution; otherwise the kernel `kern` may use more than 64 KiB of LDS
+// (kern = nullptr: the limit is left as it is), `launch` issues the SMR_LAUNCH, and its error is reported under `name`.
+template <class L>
+int launch_native(const void* kern, size_t lds, const char* name, L&& launch) {
+    if (jit_no_launch()) return SMR_OK;
+    clear_sticky_error();
+    if (kern && lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
+    }
+    launch();
+    return check_launch(name);
 }
 
 #endif  // !SMR_JIT

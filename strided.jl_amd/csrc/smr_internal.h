@@ -7,6 +7,7 @@
 #ifndef SMR_JIT
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -244,13 +245,26 @@ struct Plan {
     int part_col_tx = 0, part_col_v = 1; // COL, exact lane map (round 6): lanes along kept dim 0 (0 = the power of two above), valid for this vector width
     int part_col_y0 = 1, part_col_y1 = 1; //   rows of a workgroup along the inner reduced dim x along the outer index (TY = 256 / tx = y0 * y1)
     int part_xsplit = 1, part_qsplit = 1;  // split of the inner / outer reduced range over workgroups
-    // TILED: per-lane index tables in device memory, one per kernel variant (built on first use)
-    mutable void* lanetab[4] = {nullptr, nullptr, nullptr, nullptr};
-    // first execution builds the tables below; concurrent executions of one (cached) plan from
+    // TILED / ORBIT: a kernel form's arguments, built by the family's argument builder (smr_k_tiled.hip: build_tiled_args,
+    // smr_k_orbit.hip: build_orbit_args / build_pair_args) on the plan's first execution of that form, together with the device
+    // table it reads; later executions patch the operand addresses only.  Nothing is cached or uploaded by a dry run (jit_dry_run).
+    struct FormCache {
+        std::vector<unsigned char> args;  // the argument struct, empty until built
+        void* tab = nullptr;              // TILED: lane table; ORBIT: lane table; ORBIT PAIR: the work list of 8-word entries
+    };
+    // first execution builds the caches below (upload_table); concurrent executions of one (cached) plan from
     // several host threads serialise on this
     mutable std::shared_ptr<std::mutex> build_mu = std::make_shared<std::mutex>();
-    mutable void* ordtab = nullptr;  // TILED: tile-order table in device memory (large grids)
-    mutable std::vector<unsigned char> tiled_args[4];  // fully built kernel arguments per variant
+    mutable FormCache tiled_cache[4];           // TILED, per kernel variant: 64-bit offsets * 2 + vector accesses
+    mutable void* tiled_order = nullptr;  // TILED: tile-order table (grids with more entries than fit the arguments)
+    mutable FormCache orbit_cache[2];           // ORBIT one-orbit form: element / vector accesses
+    mutable void* orbit_list = nullptr;   // ORBIT one-orbit form: per workgroup the slot origins and the slot map
+    mutable FormCache pair_cache;         // ORBIT PAIR form
+    // every device table above, for plan_free
+    std::array<void**, 9> dev_tables() const {
+        return {&tiled_cache[0].tab, &tiled_cache[1].tab, &tiled_cache[2].tab, &tiled_cache[3].tab, &tiled_order,
+                &orbit_cache[0].tab, &orbit_cache[1].tab, &orbit_list, &pair_cache.tab};
+    }
     // eager direct dispatch (smr_seq.cpp): argument blocks of this plan's launches that are resident in device memory, keyed by their
     // bytes -- a repeated execution (same base pointers) reuses the block: no write through the BAR, no read-back round trip
     struct ArgBlock {
@@ -422,6 +436,13 @@ void set_recorder(std::vector<RecLaunch>* r, bool allow_self_release = false, bo
 // regime where the fence matters (what it writes fits the caches: option "self_release_max_bytes", default 64 MiB)?  Launchers that
 // can issue write-through stores then do (store policy 2) and call mark_self_released().
 bool want_self_release(const Plan& plan);
+
+// Copies a per-plan table of `bytes` bytes to new device memory in *dst (nothing on failure: the memory is freed again).  Synchronous,
+// once per plan and table: it must not happen inside a stream capture (execute a plan once before capturing it into a hipGraph).
+// `what` names the table in the error message.
+int upload_table(void** dst, const void* src, size_t bytes, const char* what);
+// Compute units of the current device (256 when the query fails): sizes the persistent TILED / ORBIT grids.
+int cu_count();
 
 // launchers (one per kernel TU)
 int launch_generic_map(const Plan& plan, void* const* bases, hipStream_t s);

@@ -558,28 +558,10 @@ static int gob(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     if (blocks > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "flat plan: too many tiles");
     const size_t lds = (((size_t)fp.K * fp.P * sizeof(T) + 15) & ~(size_t)15) + (((size_t)fp.P * sizeof(uint16_t) + 15) & ~(size_t)15);
     const unsigned grid = (unsigned)blocks;
-    if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "flat";
-        l.tname = tname<T>();
-        l.argtype = "smr::FlatBArgs";
-        l.entry = std::string("smr::flatb_body<") + tname<T>() + ", smr::FJit>(a, smr::FJit{kc});";
-        l.grid = grid;
-        l.block = 256;
-        l.lds = lds;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(plan.c, l, s);
-    } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)k_flatb_map<T, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
-        }
-        SMR_LAUNCH((k_flatb_map<T, F>), dim3(grid), dim3(256), lds, s, a, f);
-        return check_launch("k_flatb_map");
-    }
+    if constexpr (is_jit<F>::value)
+        return launch_jit<T>(plan.c, s, "flat", "smr::FlatBArgs", "flatb_body", "", grid, 256, lds, a);
+    else
+        return launch_native((const void*)k_flatb_map<T, F>, lds, "k_flatb_map", [&] { SMR_LAUNCH((k_flatb_map<T, F>), dim3(grid), dim3(256), lds, s, a, f); });
 }
 
 template <class T, class F>
@@ -632,49 +614,23 @@ static int go2(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     for (int k = 1; k < c.M && pair; ++k)
         if (k != fp.kt && ((uintptr_t)a.ops.base[k] % (2 * sizeof(T))) != ((uintptr_t)a.ops.base[0] % (2 * sizeof(T)))) pair = false;
     if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "flat";
-        l.tname = tname<T>();
-        l.argtype = "smr::Flat2Args";
-        l.entry = std::string("smr::flat2_body<") + tname<T>() + ", smr::FJit, " + (pair ? "true" : "false") + ">(a, smr::FJit{kc});";
-        l.grid = grid;
-        l.block = 256;
-        l.lds = lds;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(plan.c, l, s);
+        return launch_jit<T>(plan.c, s, "flat", "smr::Flat2Args", "flat2_body", "", grid, 256, lds, a, pair);
     } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        if (pair)
-            SMR_LAUNCH((k_flat2_map<T, F, true>), dim3(grid), dim3(256), lds, s, a, f);
-        else
-            SMR_LAUNCH((k_flat2_map<T, F, false>), dim3(grid), dim3(256), lds, s, a, f);
-        return check_launch("k_flat2_map");
+        return launch_native(nullptr, lds, "k_flat2_map", [&] {  // (the LDS limit is not raised)
+            if (pair)
+                SMR_LAUNCH((k_flat2_map<T, F, true>), dim3(grid), dim3(256), lds, s, a, f);
+            else
+                SMR_LAUNCH((k_flat2_map<T, F, false>), dim3(grid), dim3(256), lds, s, a, f);
+        });
     }
 }
 
 template <class T, class F, int DIR, int VL, int VF>
 static int go3(const Plan& plan, hipStream_t s, F f, const FlatArgs& a, size_t lds, unsigned grid) {
-    if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "flat";
-        l.tname = tname<T>();
-        l.argtype = "smr::FlatArgs";
-        l.entry = std::string("smr::flat_map_body<") + tname<T>() + ", smr::FJit, " + std::to_string(DIR) + ", " + std::to_string(VL) + ", " +
-                  std::to_string(VF) + ">(a, smr::FJit{kc});";
-        l.grid = grid;
-        l.block = 256;
-        l.lds = lds;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(plan.c, l, s);
-    } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        SMR_LAUNCH((k_flat_map<T, F, DIR, VL, VF>), dim3(grid), dim3(256), lds, s, a, f);
-        return check_launch("k_flat_map");
-    }
+    if constexpr (is_jit<F>::value)
+        return launch_jit<T>(plan.c, s, "flat", "smr::FlatArgs", "flat_map_body", "", grid, 256, lds, a, DIR, VL, VF);
+    else  // (the LDS limit is not raised)
+        return launch_native(nullptr, lds, "k_flat_map", [&] { SMR_LAUNCH((k_flat_map<T, F, DIR, VL, VF>), dim3(grid), dim3(256), lds, s, a, f); });
 }
 
 template <class T, class F>
@@ -780,32 +736,15 @@ int launch_flat_map_ct<SMR_CT>(const Plan& plan, void* const* bases, hipStream_t
     const Canon& c = plan.c;
     const bool two = plan.flat2.on;
     if (plan.flatb.on) {
-        if (c.bitcopy) {
-#if SMR_CT == SMR_F32
-            switch (c.esize[0]) {
-                case 4: return gob<float, FIdent<float>>(plan, bases, s, FIdent<float>{});
-                case 8: return gob<double, FIdent<double>>(plan, bases, s, FIdent<double>{});
-                case 16: return gob<c64, FIdent<c64>>(plan, bases, s, FIdent<c64>{});
-                default: return set_error(SMR_EINVAL, "flat plan: 1- / 2-byte moves take the generic family");
-            }
-#else
-            return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
-#endif
-        }
+        if (c.bitcopy)
+            return with_bitcopy<SMR_CT, false>(c, [&](auto f) { return gob<typename ident_elem<decltype(f)>::type, decltype(f)>(plan, bases, s, f); });
         return with_functor<T>(c, fbit(FK_IDENT) | fbit(FK_SCALE), [&](auto f) { return gob<T, decltype(f)>(plan, bases, s, f); });
     }
-    if (c.bitcopy) {
-#if SMR_CT == SMR_F32
-        switch (c.esize[0]) {
-            case 4: return two ? go2<float, FIdent<float>>(plan, bases, s, FIdent<float>{}) : go<float, FIdent<float>>(plan, bases, s, FIdent<float>{});
-            case 8: return two ? go2<double, FIdent<double>>(plan, bases, s, FIdent<double>{}) : go<double, FIdent<double>>(plan, bases, s, FIdent<double>{});
-            case 16: return two ? go2<c64, FIdent<c64>>(plan, bases, s, FIdent<c64>{}) : go<c64, FIdent<c64>>(plan, bases, s, FIdent<c64>{});
-            default: return set_error(SMR_EINVAL, "flat plan: 1- / 2-byte moves take the generic family");
-        }
-#else
-        return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
-#endif
-    }
+    if (c.bitcopy)
+        return with_bitcopy<SMR_CT, false>(c, [&](auto f) {
+            typedef typename ident_elem<decltype(f)>::type E;
+            return two ? go2<E, decltype(f)>(plan, bases, s, f) : go<E, decltype(f)>(plan, bases, s, f);
+        });
     const unsigned mask = fbit(FK_IDENT) | fbit(FK_SCALE) | fbit(FK_ADD2) | fbit(FK_AXPY) | fbit(FK_AXPBY);
     if (two) return with_functor<T>(c, mask, [&](auto f) { return go2<T, decltype(f)>(plan, bases, s, f); });
     return with_functor<T>(c, mask, [&](auto f) { return go<T, decltype(f)>(plan, bases, s, f); });

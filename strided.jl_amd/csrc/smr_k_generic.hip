@@ -85,43 +85,17 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
         for (int i = 0; i < MAXN; ++i) a.strides[k][i] = (k < c.M) ? c.strides[k][i] : 0;
     i64 blocks = (c.total + 255) / 256;
     blocks = std::min<i64>(blocks, 256 * 32);
-    if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "generic";
-        l.tname = tname<T>();
-        l.argtype = "smr::GenArgs";
-        l.entry = std::string("smr::generic_map_body<") + tname<T>() + ", smr::FJit, " + (MIXED ? "true" : "false") + ">(a, smr::FJit{kc});";
-        l.grid = (unsigned)blocks;
-        l.block = 256;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(c, l, s);
-    } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        SMR_LAUNCH((k_generic_map<T, F, MIXED>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
-        return check_launch("k_generic_map");
-    }
+    if constexpr (is_jit<F>::value)
+        return launch_jit<T>(c, s, "generic", "smr::GenArgs", "generic_map_body", "", (unsigned)blocks, 256, 0, a, MIXED);
+    else
+        return launch_native(nullptr, 0, "k_generic_map", [&] { SMR_LAUNCH((k_generic_map<T, F, MIXED>), dim3((unsigned)blocks), dim3(256), 0, s, a, f); });
 }
 
 template <>
 int launch_generic_map_ct<SMR_CT>(const Plan& plan, void* const* bases, hipStream_t s) {
     typedef ct_type<SMR_CT>::type T;
     const Canon& c = plan.c;
-    if (c.bitcopy) {
-#if SMR_CT == SMR_F32
-        // opaque element moves by size; only this object carries the narrow movers
-        switch (c.esize[0]) {
-            case 1: return go<b8, FIdent<b8>, false>(plan, bases, s, FIdent<b8>{});
-            case 2: return go<b16, FIdent<b16>, false>(plan, bases, s, FIdent<b16>{});
-            case 4: return go<float, FIdent<float>, false>(plan, bases, s, FIdent<float>{});
-            case 8: return go<double, FIdent<double>, false>(plan, bases, s, FIdent<double>{});
-            default: return go<c64, FIdent<c64>, false>(plan, bases, s, FIdent<c64>{});
-        }
-#else
-        return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
-#endif
-    }
+    if (c.bitcopy) return with_bitcopy<SMR_CT>(c, [&](auto f) { return go<typename ident_elem<decltype(f)>::type, decltype(f), false>(plan, bases, s, f); });
     if (c.mixed) return with_prog<T>(c, [&](auto f) { return go<T, decltype(f), true>(plan, bases, s, f); });
     return with_functor<T>(c, fbit(FK_IDENT), [&](auto f) { return go<T, decltype(f), false>(plan, bases, s, f); });
 }

@@ -702,48 +702,76 @@ static OSwz choose_orbit_swizzle(const OrbitArgs& a, int nin, bool own0, int esi
     return best;
 }
 
-template <class T, class F, int V, int NREP, int NG, bool OWN0, bool PIPE>
-static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
+// An ORBIT launch apart from the kernel itself
+struct OrbitLaunch {
+    OrbitArgs a;
+    unsigned grid = 0, block = 0;
+    size_t lds = 0;
+};
+
+// The part of the arguments both forms share: tiled dims in canonical (= natural) order, each view's LDS bit positions and conjugation
+static int orbit_dims(const Plan& plan, const OpTab& tab, int esize, OrbitArgs& a) {
     const Canon& c = plan.c;
     const OrbitPlan& o = plan.orbit;
-    OrbitArgs a;
-    std::vector<unsigned char>& cached = plan.tiled_args[V > 1 ? 1 : 0];
-    if (cached.size() == sizeof a) {
-        std::memcpy(&a, cached.data(), sizeof a);
+    a.nin = c.M - 1;
+    a.tilelog = o.tilelog;
+    a.conj0 = tab.conj[0];
+    int nt = 0, sh = 0, jof[MAXN];
+    for (int d = 0; d < c.N; ++d) {
+        jof[d] = -1;
+        if (o.lg[d] == 0) continue;
+        if (nt >= OMAXT) return set_error(SMR_EUNSUPPORTED, "orbit: too many tiled dims");
+        jof[d] = nt;
+        a.esh[nt] = sh;
+        a.elen[nt] = o.lg[d];
+        a.estride[nt] = (uint32_t)(c.strides[o.k0][d] * esize);
+        sh += o.lg[d];
+        ++nt;
+    }
+    for (int k = 1; k < c.M; ++k) {
+        for (int d = 0; d < c.N; ++d)
+            if (jof[d] >= 0) a.lsh[k - 1][jof[d]] = a.esh[jof[o.pdim[k][d]]];
+        a.conjbit[k - 1] = tab.conj[k] ? 0x80000000u : 0u;
+    }
+    return SMR_OK;
+}
+
+// element offset of tile `id` (canonical tile index) in the shared buffer
+static uint32_t orbit_tile_origin(const Plan& plan, i64 id) {
+    const OrbitPlan& o = plan.orbit;
+    i64 org = 0;
+    for (int d = 0; d < plan.c.N; ++d) {
+        org += (id % o.ntiles[d]) * (plan.c.strides[o.k0][d] << o.lg[d]);
+        id /= o.ntiles[d];
+    }
+    return (uint32_t)org;
+}
+
+// Builds the arguments of the one-orbit form (V elements per access, NREP repeats, NG slots, view 0 the identity view when OWN0, the
+// persistent form when PIPE; nk = inputs of the device functor).  Built on the plan's first execution of the form with the work list
+// and the lane table, and cached in the plan (Plan::orbit_cache, orbit_list); the operand addresses, the grid and the store policy
+// are set per call.  wt_store: the kernel's vector type has write-through stores.
+static int build_orbit_args(const Plan& plan, const OpTab& tab, int esize, int V, int NREP, int NG, bool OWN0, bool PIPE, int nk,
+                            bool wt_store, OrbitLaunch& L) {
+    const Canon& c = plan.c;
+    const OrbitPlan& o = plan.orbit;
+    OrbitArgs& a = L.a;
+    Plan::FormCache& cached = plan.orbit_cache[V > 1 ? 1 : 0];
+    if (cached.args.size() == sizeof a) {
+        std::memcpy(&a, cached.args.data(), sizeof a);
     } else {
         std::memset(&a, 0, sizeof a);
-        const i64 es = (i64)sizeof(T);
-        a.nin = c.M - 1;
-        a.tilelog = o.tilelog;
         int vlog = 0, nreplog = 0;
         while ((1 << vlog) < V) ++vlog;
         while ((1 << nreplog) < NREP) ++nreplog;
         a.ntlog = o.tilelog - vlog - nreplog;
-        a.conj0 = tab.conj[0];
-        // tiled dims in canonical (= natural) order
-        int nt = 0, sh = 0, jof[MAXN];
-        for (int d = 0; d < c.N; ++d) {
-            jof[d] = -1;
-            if (o.lg[d] == 0) continue;
-            if (nt >= OMAXT) return set_error(SMR_EUNSUPPORTED, "orbit: too many tiled dims");
-            jof[d] = nt;
-            a.esh[nt] = sh;
-            a.elen[nt] = o.lg[d];
-            a.estride[nt] = (uint32_t)(c.strides[o.k0][d] * es);
-            sh += o.lg[d];
-            ++nt;
-        }
-        for (int k = 1; k < c.M; ++k) {
-            for (int d = 0; d < c.N; ++d)
-                if (jof[d] >= 0) a.lsh[k - 1][jof[d]] = a.esh[jof[o.pdim[k][d]]];
-            a.conjbit[k - 1] = tab.conj[k] ? 0x80000000u : 0u;
-        }
+        if (int rc = orbit_dims(plan, tab, esize, a)) return rc;
         if (o.nslots != NG) return set_error(SMR_EINVAL, "orbit: slot count mismatch");
-        const OSwz sw = choose_orbit_swizzle(a, c.M - 1, OWN0, (int)sizeof(T), V, NREP);
+        const OSwz sw = choose_orbit_swizzle(a, c.M - 1, OWN0, esize, V, NREP);
         a.swz_s1 = sw.s1;
         a.swz_s2 = sw.s2;
         a.swz_mask = sw.mask;
-        if (!plan.ordtab && !jit_dry_run()) {
+        if (!plan.orbit_list && !jit_dry_run()) {
             // one row per workgroup: the NG slot origins (element offset of the tile in each slot), then the slot map (plan_orbit)
             const size_t nwg = o.wmap.size();
             std::vector<uint32_t> rows(nwg * 2 * NG, 0u);
@@ -753,31 +781,15 @@ static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
                     row[0] = 0xffffffffu;
                     continue;
                 }
-                for (int g = 0; g < NG; ++g) {
-                    i64 id = o.wtile[w * NG + g], org = 0;
-                    for (int d = 0; d < c.N; ++d) {
-                        org += (id % o.ntiles[d]) * (c.strides[o.k0][d] << o.lg[d]);
-                        id /= o.ntiles[d];
-                    }
-                    row[g] = (uint32_t)org;
-                }
+                for (int g = 0; g < NG; ++g) row[g] = orbit_tile_origin(plan, o.wtile[w * NG + g]);
                 row[NG] = (uint32_t)o.wmap[w];
                 row[NG + 1] = (uint32_t)(o.wmap[w] >> 32);
             }
-            void* dptr = nullptr;
-            hipError_t e = hipMalloc(&dptr, rows.size() * sizeof(uint32_t));
-            if (e != hipSuccess) return hip_error(e, "hipMalloc(orbit origins)");
-            e = hipMemcpy(dptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(dptr);
-                return hip_error(e, "hipMemcpy(orbit origins)");
-            }
-            plan.ordtab = dptr;
+            if (int rc = upload_table(&plan.orbit_list, rows.data(), rows.size() * sizeof(uint32_t), "orbit origins")) return rc;
         }
-        a.list = reinterpret_cast<const uint32_t*>(plan.ordtab);
-        if (!plan.lanetab[V > 1 ? 1 : 0] && !jit_dry_run()) {
+        a.list = reinterpret_cast<const uint32_t*>(plan.orbit_list);
+        if (!cached.tab && !jit_dry_run()) {
             // per-lane rows: {byte offset in a tile, LDS read index of every view read from LDS}
-            const int nk = is_jit<F>::value ? c.M - 1 : ((F::NIN >= 0) ? F::NIN : MAXIN);  // = NK of the device functor
             const int nlr = nk - (OWN0 ? 1 : 0);
             const int rowlen = (1 + nlr) <= 2 ? 2 : ((1 + nlr) <= 4 ? 4 : 8);
             const uint32_t nt = 1u << a.ntlog;
@@ -792,20 +804,12 @@ static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
                         for (int k = OWN0 ? 1 : 0; k < nk && k < c.M - 1; ++k) row[1 + k - (OWN0 ? 1 : 0)] |= cj << a.lsh[k][j];
                     }
                 }
-            void* dptr = nullptr;
-            hipError_t e2 = hipMalloc(&dptr, rows.size() * sizeof(uint32_t));
-            if (e2 != hipSuccess) return hip_error(e2, "hipMalloc(orbit lane table)");
-            e2 = hipMemcpy(dptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e2 != hipSuccess) {
-                (void)hipFree(dptr);
-                return hip_error(e2, "hipMemcpy(orbit lane table)");
-            }
-            plan.lanetab[V > 1 ? 1 : 0] = dptr;
+            if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(uint32_t), "orbit lane table")) return rc;
         }
-        a.lanetab = reinterpret_cast<const uint32_t*>(plan.lanetab[V > 1 ? 1 : 0]);
+        a.lanetab = reinterpret_cast<const uint32_t*>(cached.tab);
         if (!jit_dry_run()) {
-            cached.resize(sizeof a);
-            std::memcpy(cached.data(), &a, sizeof a);
+            cached.args.resize(sizeof a);
+            std::memcpy(cached.args.data(), &a, sizeof a);
         }
     }
     a.src = (const char*)tab.base[o.k0];
@@ -813,92 +817,38 @@ static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
     const Options& opt = options();
     // automatic: only tiles that write whole 128-byte lines (symmetrise 4000^2: 40.2 -> 38.5 us); the 32-/64-byte
     // runs of the 4-D orbits rely on line partners meeting in L2 and get slower (4.8 -> 6.3 us at 32^4)
-    a.nts = (opt.nt_store > 0 || (opt.nt_store < 0 && plan.c.strides[0][0] == 1 && (sizeof(T) << o.lg[0]) >= 128)) ? 1 : 0;
+    a.nts = (opt.nt_store > 0 || (opt.nt_store < 0 && plan.c.strides[0][0] == 1 && (esize << o.lg[0]) >= 128)) ? 1 : 0;
     // write-through stores: forced (nt_store = 2), or a launch recorded for a sequence that fits the caches several times over
     // (want_self_release): its packet then needs no release fence
-    const bool wt = has_wt_store<OVec<T, V>>::value && (opt.nt_store == 2 || want_self_release(plan));
-    if (wt) a.nts = 2;
-    const unsigned block = 1u << a.ntlog;
-    const size_t lds = (size_t)NG * (sizeof(T) << o.tilelog);
+    if (wt_store && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
+    L.block = 1u << a.ntlog;
+    L.lds = (size_t)NG * ((size_t)esize << o.tilelog);
     a.nlist = (int32_t)o.wmap.size();
-    unsigned grid = (unsigned)o.wmap.size();
+    L.grid = (unsigned)o.wmap.size();
     if (PIPE) {
         // as many workgroups as the machine holds at once, a multiple of 8 so that a workgroup stays on its XCD's run
-        static const int ncu = [] {
-            int dev = 0, n = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-            (void)hipGetLastError();
-            return n;
-        }();
-        const unsigned cap = (unsigned)ncu * (unsigned)std::max<size_t>(1, (160 * 1024) / lds) / 8u * 8u;
-        if (cap >= 8) grid = std::min<unsigned>(grid, cap);
-        if (opt.orbit_wgs >= 8) grid = std::min<unsigned>(grid, (unsigned)opt.orbit_wgs / 8u * 8u);
+        const unsigned cap = (unsigned)cu_count() * (unsigned)std::max<size_t>(1, (160 * 1024) / L.lds) / 8u * 8u;
+        if (cap >= 8) L.grid = std::min<unsigned>(L.grid, cap);
+        if (opt.orbit_wgs >= 8) L.grid = std::min<unsigned>(L.grid, (unsigned)opt.orbit_wgs / 8u * 8u);
     }
-    if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "orbit";
-        l.tname = tname<T>();
-        l.argtype = "smr::OrbitArgs";
-        l.entry = std::string("smr::orbit_map_body<") + tname<T>() + ", smr::FJit, " + std::to_string(V) + ", " + std::to_string(NREP) + ", " +
-                  std::to_string(NG) + ", " + (OWN0 ? "true" : "false") + ", " + (PIPE ? "true" : "false") + ">(a, smr::orbit_head(a), smr::FJit{kc});";
-        l.grid = grid;
-        l.block = block;
-        l.lds = lds;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(c, l, s);
-    } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        auto kern = k_orbit_map<T, F, V, NREP, NG, OWN0, PIPE>;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
-        }
-        if (!PIPE) mark_sliceable(2, 0u, (unsigned)(2 * NG * sizeof(uint32_t)));  // one table row per workgroup; the pointer is parameter 0
-        if (a.nts == 2) mark_self_released();
-        const OrbitHead h = orbit_head(a);
-        SMR_LAUNCH(kern, dim3(grid), dim3(block), lds, s, h.list, h.src, h.dst, h.eshp, h.elenp, h.estride[0], h.estride[1], h.estride[2], h.estride[3], h.ntlog, a,
-                   f SMR_STAMP_ARG(grid, block));
-        return check_launch("k_orbit_map");
-    }
+    return SMR_OK;
 }
 
-// PAIR form (orbit_pair_body): builds the 8-word entries once per plan, launches 256 lanes per two slot sets
-template <class T, class F>
-static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
+// The same for the PAIR form (orbit_pair_body: 256 lanes per two slot sets, 2 elements per access): its work list of 8-word entries is
+// built once per plan (Plan::pair_cache)
+static int build_pair_args(const Plan& plan, const OpTab& tab, int esize, bool wt_store, OrbitLaunch& L) {
     const Canon& c = plan.c;
     const OrbitPlan& o = plan.orbit;
-    constexpr int NS = 4, V = 2;
-    OrbitArgs a;
-    std::vector<unsigned char>& cached = plan.tiled_args[2];
-    if (cached.size() == sizeof a) {
-        std::memcpy(&a, cached.data(), sizeof a);
+    constexpr int NS = 4;
+    OrbitArgs& a = L.a;
+    Plan::FormCache& cached = plan.pair_cache;
+    if (cached.args.size() == sizeof a) {
+        std::memcpy(&a, cached.args.data(), sizeof a);
     } else {
         std::memset(&a, 0, sizeof a);
-        const i64 es = (i64)sizeof(T);
-        a.nin = c.M - 1;
-        a.tilelog = o.tilelog;
         a.ntlog = 8;
-        a.conj0 = tab.conj[0];
-        int nt = 0, sh = 0, jof[MAXN];
-        for (int d = 0; d < c.N; ++d) {
-            jof[d] = -1;
-            if (o.lg[d] == 0) continue;
-            if (nt >= OMAXT) return set_error(SMR_EUNSUPPORTED, "orbit: too many tiled dims");
-            jof[d] = nt;
-            a.esh[nt] = sh;
-            a.elen[nt] = o.lg[d];
-            a.estride[nt] = (uint32_t)(c.strides[o.k0][d] * es);
-            sh += o.lg[d];
-            ++nt;
-        }
-        for (int k = 1; k < c.M; ++k) {
-            for (int d = 0; d < c.N; ++d)
-                if (jof[d] >= 0) a.lsh[k - 1][jof[d]] = a.esh[jof[o.pdim[k][d]]];
-            a.conjbit[k - 1] = tab.conj[k] ? 0x80000000u : 0u;
-        }
-        if (!plan.lanetab[3] && !jit_dry_run()) {
+        if (int rc = orbit_dims(plan, tab, esize, a)) return rc;
+        if (!cached.tab && !jit_dry_run()) {
             const size_t nwg = o.pmap.size() / 2;
             std::vector<uint32_t> rows(nwg * 4 * 8, 0u);
             auto region = [](int slot, int b) { return (uint32_t)(((2 * slot + b) << 8) | (b ? 17 : 0)); };
@@ -910,12 +860,7 @@ static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
                 for (int j = 0; j < NS; ++j) {
                     uint32_t* en = &rows[(w * 4 + (size_t)j) * 8];
                     for (int b = 0; b < 2; ++b) {
-                        i64 id = o.ptile[w * 8 + (size_t)b * 4 + (size_t)j], org = 0;
-                        for (int d = 0; d < c.N; ++d) {
-                            org += (id % o.ntiles[d]) * (c.strides[o.k0][d] << o.lg[d]);
-                            id /= o.ntiles[d];
-                        }
-                        en[b] = (uint32_t)org;
+                        en[b] = orbit_tile_origin(plan, o.ptile[w * 8 + (size_t)b * 4 + (size_t)j]);
                         en[2] |= region(j, b) << (16 * b);
                         const uint64_t mp = o.pmap[w * 2 + (size_t)b];
                         // view k of the kernel = input k + 1; input 1 is the identity view (the lane's own registers)
@@ -923,46 +868,67 @@ static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
                     }
                 }
             }
-            void* dptr = nullptr;
-            hipError_t e = hipMalloc(&dptr, rows.size() * sizeof(uint32_t));
-            if (e != hipSuccess) return hip_error(e, "hipMalloc(orbit pair table)");
-            e = hipMemcpy(dptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(dptr);
-                return hip_error(e, "hipMemcpy(orbit pair table)");
-            }
-            plan.lanetab[3] = dptr;
+            if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(uint32_t), "orbit pair table")) return rc;
         }
-        a.list = reinterpret_cast<const uint32_t*>(plan.lanetab[3]);
+        a.list = reinterpret_cast<const uint32_t*>(cached.tab);
         if (!jit_dry_run()) {
-            cached.resize(sizeof a);
-            std::memcpy(cached.data(), &a, sizeof a);
+            cached.args.resize(sizeof a);
+            std::memcpy(cached.args.data(), &a, sizeof a);
         }
     }
     a.src = (const char*)tab.base[o.k0];
     a.dst = (char*)tab.base[0];
     const Options& opt = options();
     a.nts = opt.nt_store > 0 ? 1 : 0;  // (32- / 64-byte runs: partial lines meet in L2, plain stores -- as in the one-orbit form)
-    if (has_wt_store<OVec<T, V>>::value && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
+    if (wt_store && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
     a.nlist = (int32_t)(o.pmap.size() / 2);
-    const unsigned grid = (unsigned)(o.pmap.size() / 2), block = 256;
-    const size_t lds = 8 * (sizeof(T) << 8);
-    if (jit_no_launch()) return SMR_OK;
-    clear_sticky_error();
-    mark_sliceable(2, 0u, (unsigned)(4 * 8 * sizeof(uint32_t)));  // one table row (four entries) per workgroup; the pointer is parameter 0
-    if (a.nts == 2) mark_self_released();
-    const OrbitHead h = orbit_head(a);
-    // one kernel per store policy: no branch on a kernel argument between the exchange and the stores
-    if (a.nts == 2)
-        SMR_LAUNCH((k_orbit_pair<T, F, 2>), dim3(grid), dim3(block), lds, s, h.list, h.src, h.dst, h.eshp, h.elenp, h.estride[0], h.estride[1], h.estride[2], h.estride[3],
-                   h.ntlog, a, f SMR_STAMP_ARG(grid, block));
-    else if (a.nts)
-        SMR_LAUNCH((k_orbit_pair<T, F, 1>), dim3(grid), dim3(block), lds, s, h.list, h.src, h.dst, h.eshp, h.elenp, h.estride[0], h.estride[1], h.estride[2], h.estride[3],
-                   h.ntlog, a, f SMR_STAMP_ARG(grid, block));
-    else
-        SMR_LAUNCH((k_orbit_pair<T, F, 0>), dim3(grid), dim3(block), lds, s, h.list, h.src, h.dst, h.eshp, h.elenp, h.estride[0], h.estride[1], h.estride[2], h.estride[3],
-                   h.ntlog, a, f SMR_STAMP_ARG(grid, block));
-    return check_launch("k_orbit_pair");
+    L.grid = (unsigned)(o.pmap.size() / 2);
+    L.block = 256;
+    L.lds = 8 * ((size_t)esize << 8);
+    return SMR_OK;
+}
+
+// the natively compiled kernels take OrbitHead as leading scalar parameters (preloaded into SGPRs), then the struct
+#define SMR_ORBIT_LAUNCH(kern, L, s, f)                                                                                                  \
+    do {                                                                                                                                 \
+        const OrbitHead h_ = orbit_head((L).a);                                                                                          \
+        SMR_LAUNCH(kern, dim3((L).grid), dim3((L).block), (L).lds, s, h_.list, h_.src, h_.dst, h_.eshp, h_.elenp, h_.estride[0],          \
+                   h_.estride[1], h_.estride[2], h_.estride[3], h_.ntlog, (L).a, f SMR_STAMP_ARG((L).grid, (L).block));                  \
+    } while (0)
+
+template <class T, class F, int V, int NREP, int NG, bool OWN0, bool PIPE>
+static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
+    const int nk = is_jit<F>::value ? plan.c.M - 1 : ((F::NIN >= 0) ? F::NIN : MAXIN);  // = NK of the device functor
+    OrbitLaunch L;
+    if (int rc = build_orbit_args(plan, tab, (int)sizeof(T), V, NREP, NG, OWN0, PIPE, nk, has_wt_store<OVec<T, V>>::value, L)) return rc;
+    if constexpr (is_jit<F>::value) {
+        return launch_jit<T>(plan.c, s, "orbit", "smr::OrbitArgs", "orbit_map_body", "smr::orbit_head(a), ", L.grid, L.block, L.lds, L.a, V, NREP,
+                             NG, OWN0, PIPE);
+    } else {
+        auto kern = k_orbit_map<T, F, V, NREP, NG, OWN0, PIPE>;
+        return launch_native((const void*)kern, L.lds, "k_orbit_map", [&] {
+            if (!PIPE) mark_sliceable(2, 0u, (unsigned)(2 * NG * sizeof(uint32_t)));  // one table row per workgroup; the pointer is parameter 0
+            if (L.a.nts == 2) mark_self_released();
+            SMR_ORBIT_LAUNCH(kern, L, s, f);
+        });
+    }
+}
+
+template <class T, class F>
+static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
+    OrbitLaunch L;
+    if (int rc = build_pair_args(plan, tab, (int)sizeof(T), has_wt_store<OVec<T, 2>>::value, L)) return rc;
+    return launch_native(nullptr, L.lds, "k_orbit_pair", [&] {
+        mark_sliceable(2, 0u, (unsigned)(4 * 8 * sizeof(uint32_t)));  // one table row (four entries) per workgroup; the pointer is parameter 0
+        if (L.a.nts == 2) mark_self_released();
+        // one kernel per store policy: no branch on a kernel argument between the exchange and the stores
+        if (L.a.nts == 2)
+            SMR_ORBIT_LAUNCH((k_orbit_pair<T, F, 2>), L, s, f);
+        else if (L.a.nts)
+            SMR_ORBIT_LAUNCH((k_orbit_pair<T, F, 1>), L, s, f);
+        else
+            SMR_ORBIT_LAUNCH((k_orbit_pair<T, F, 0>), L, s, f);
+    });
 }
 
 // persistent pipelined form: when the LDS footprint leaves one workgroup per CU and every CU gets several orbits

@@ -820,24 +820,10 @@ __global__ void __launch_bounds__(256) k_reduce_col(RedArgs a, F f) {
 // ---- launchers ----------------------------------------------------------------------------------------
 template <class T, class F, bool MIXED, int V>
 static int launch_all(const Canon& c, const RedArgs& a, int blocks, hipStream_t s, F f) {
-    if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "reduce";
-        l.tname = tname<T>();
-        l.argtype = "smr::RedArgs";
-        l.entry = std::string("smr::reduce_all_body<") + tname<T>() + ", smr::FJit, " + (MIXED ? "true" : "false") + ", " +
-                  std::to_string(V) + ">(a, smr::FJit{kc});";
-        l.grid = (unsigned)blocks;
-        l.block = 256;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(c, l, s);
-    } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        SMR_LAUNCH((k_reduce_all<T, F, MIXED, V>), dim3(blocks), dim3(256), 0, s, a, f);
-        return check_launch("k_reduce_all");
-    }
+    if constexpr (is_jit<F>::value)
+        return launch_jit<T>(c, s, "reduce", "smr::RedArgs", "reduce_all_body", "", (unsigned)blocks, 256, 0, a, MIXED, V);
+    else
+        return launch_native(nullptr, 0, "k_reduce_all", [&] { SMR_LAUNCH((k_reduce_all<T, F, MIXED, V>), dim3(blocks), dim3(256), 0, s, a, f); });
 }
 
 static void fill_args(const Plan& plan, void* const* bases, RedArgs& a) {
@@ -895,11 +881,7 @@ static int go_all(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     }
     if (!done) rc = launch_all<T, F, MIXED, 1>(c, a, blocks, s, f);
     if (rc) return rc;
-    if (blocks > 1 && !a.single && !jit_no_launch()) {
-        clear_sticky_error();
-    SMR_LAUNCH((k_reduce_final<T, MIXED>), dim3(1), dim3(256), 0, s, a);
-        rc = check_launch("k_reduce_final");
-    }
+    if (blocks > 1 && !a.single) rc = launch_native(nullptr, 0, "k_reduce_final", [&] { SMR_LAUNCH((k_reduce_final<T, MIXED>), dim3(1), dim3(256), 0, s, a); });
     return rc;
 }
 
@@ -907,25 +889,17 @@ static int go_all(const Plan& plan, void* const* bases, hipStream_t s, F f) {
 template <class T, class F, bool MIXED, int KIND, int V>
 static int launch_part(const Canon& c, const RedArgs& a, i64 blocks, hipStream_t s, F f) {
     if constexpr (is_jit<F>::value) {
-        static const char* body[] = {"reduce_part_body", "reduce_row_body", "reduce_col_body"};
-        JitLaunch l;
-        l.family = "reduce";
-        l.tname = tname<T>();
-        l.argtype = "smr::RedArgs";
-        l.entry = std::string("smr::") + body[KIND] + "<" + tname<T>() + ", smr::FJit, " + (MIXED ? "true" : "false") +
-                  (KIND ? ", " + std::to_string(V) : std::string()) + ">(a, smr::FJit{kc});";
-        l.grid = (unsigned)blocks;
-        l.block = 256;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(c, l, s);
+        const char* body = KIND == 0 ? "reduce_part_body" : (KIND == 1 ? "reduce_row_body" : "reduce_col_body");
+        if constexpr (KIND == 0)
+            return launch_jit<T>(c, s, "reduce", "smr::RedArgs", body, "", (unsigned)blocks, 256, 0, a, MIXED);
+        else
+            return launch_jit<T>(c, s, "reduce", "smr::RedArgs", body, "", (unsigned)blocks, 256, 0, a, MIXED, V);
     } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        if constexpr (KIND == 0) SMR_LAUNCH((k_reduce_part<T, F, MIXED>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
-        if constexpr (KIND == 1) SMR_LAUNCH((k_reduce_row<T, F, MIXED, V>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
-        if constexpr (KIND == 2) SMR_LAUNCH((k_reduce_col<T, F, MIXED, V>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
-        return check_launch("k_reduce_part");
+        return launch_native(nullptr, 0, "k_reduce_part", [&] {
+            if constexpr (KIND == 0) SMR_LAUNCH((k_reduce_part<T, F, MIXED>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
+            if constexpr (KIND == 1) SMR_LAUNCH((k_reduce_row<T, F, MIXED, V>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
+            if constexpr (KIND == 2) SMR_LAUNCH((k_reduce_col<T, F, MIXED, V>), dim3((unsigned)blocks), dim3(256), 0, s, a, f);
+        });
     }
 }
 

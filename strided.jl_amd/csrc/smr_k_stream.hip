@@ -249,27 +249,16 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     if (grid > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "stream grid too large");
     const int form = !a.packed ? 0 : (a.txlog < 8 ? 1 : 2);
     if constexpr (is_jit<F>::value) {
-        JitLaunch l;
-        l.family = "stream";
-        l.tname = tname<T>();
-        l.argtype = "smr::StreamArgs";
-        l.entry = std::string("smr::stream_map_body<") + tname<T>() + ", smr::FJit, " + (MIXED ? "true" : "false") + ", " +
-                  std::to_string(V) + ", " + std::to_string(U) + ", " + std::to_string(form) + ">(a, smr::FJit{kc});";
-        l.grid = (unsigned)grid;
-        l.block = 256;
-        l.args = &a;
-        l.argsize = sizeof a;
-        return jit_launch(c, l, s);
+        return launch_jit<T>(c, s, "stream", "smr::StreamArgs", "stream_map_body", "", (unsigned)grid, 256, 0, a, MIXED, V, U, form);
     } else {
-        if (jit_no_launch()) return SMR_OK;
-        clear_sticky_error();
-        if (form == 0)
-            SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 0>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
-        else if (form == 1)
-            SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 1>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
-        else
-            SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
-        return check_launch("k_stream_map");
+        return launch_native(nullptr, 0, "k_stream_map", [&] {
+            if (form == 0)
+                SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 0>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
+            else if (form == 1)
+                SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 1>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
+            else
+                SMR_LAUNCH((k_stream_map<T, F, MIXED, V, U, 2>), dim3((unsigned)grid), dim3(256), 0, s, a, f SMR_STAMP_ARG(grid, 256));
+        });
     }
 }
 
@@ -296,19 +285,7 @@ template <>
 int launch_stream_map_ct<SMR_CT>(const Plan& plan, void* const* bases, hipStream_t s) {
     typedef ct_type<SMR_CT>::type T;
     const Canon& c = plan.c;
-    if (c.bitcopy) {
-#if SMR_CT == SMR_F32
-        switch (c.esize[0]) {
-            case 1: return go_vec<b8>(plan, bases, s, FIdent<b8>{});
-            case 2: return go_vec<b16>(plan, bases, s, FIdent<b16>{});
-            case 4: return go_vec<float>(plan, bases, s, FIdent<float>{});
-            case 8: return go_vec<double>(plan, bases, s, FIdent<double>{});
-            default: return go_vec<c64>(plan, bases, s, FIdent<c64>{});
-        }
-#else
-        return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
-#endif
-    }
+    if (c.bitcopy) return with_bitcopy<SMR_CT>(c, [&](auto f) { return go_vec<typename ident_elem<decltype(f)>::type>(plan, bases, s, f); });
     if (c.mixed) return with_prog<T>(c, [&](auto f) { return go<T, decltype(f), true, 1>(plan, bases, s, f); });
     return with_functor<T>(c, FMASK_ALL, [&](auto f) { return go_vec<T>(plan, bases, s, f); });
 }

@@ -841,108 +841,64 @@ static Swizzle choose_swizzle(int tilelog, int w, const std::vector<LanePattern>
     return sw;
 }
 
-template <class T, class F, bool MIXED, bool WIDE, int V, int MODE, int THRLOG>
-static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua = false) {
-    constexpr bool EDGE = (MODE & 1) != 0;
+// A TILED launch of kernel variant (WIDE, V, MODE, THRLOG) apart from the kernel itself
+template <bool WIDE>
+struct TiledLaunch {
+    TiledArgs<WIDE> a;
+    bool lean_fails = false;  // the lean variants (MODE & 4 == 0) assume 32-bit tile origins over at most NG grid dims: variant 7
+    unsigned grid = 0;        // workgroups of the one-shot form
+    unsigned pgrid = 0;       // of the persistent, software-pipelined form (0: the one-shot form runs)
+    size_t lds = 0;
+};
+
+// Builds the arguments of a TILED launch.  They depend on the plan only, except for the operand addresses: built on the plan's
+// first execution of the variant (WIDE, V) with its lane and tile-order tables, and cached in the plan (Plan::tiled_cache).  The operand
+// addresses, the persistent grid and the store policy are set per call; wt_store: the kernel's vector type has write-through stores.
+template <bool WIDE>
+static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V, int MODE, int THRLOG, bool ua, bool wt_store,
+                            TiledLaunch<WIDE>& L) {
     typedef typename off_t_of<WIDE>::type O;
-    constexpr int NREP = EPL / V;
-    constexpr int NT = 1 << THRLOG;
+    const bool EDGE = (MODE & 1) != 0, LEAN = (MODE & 4) == 0;
+    const int NREP = EPL / V, NT = 1 << THRLOG;
     const Canon& c = plan.c;
     const TilePlan& t = plan.tile;
+    const Options& o = options();
     int vlog = 0;
     while ((1 << vlog) < V) ++vlog;
-    constexpr int variant = (WIDE ? 2 : 0) + (V > 1 ? 1 : 0);
-    const size_t lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * sizeof(T);
-    const unsigned grid_ = t.ord.empty() ? (unsigned)t.grid : (unsigned)t.ord.size();
+    TiledArgs<WIDE>& a = L.a;
+    L.lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * esize;
+    L.grid = t.ord.empty() ? (unsigned)t.grid : (unsigned)t.ord.size();
     // persistent, software-pipelined form when the work list is longer than the machine holds at once
-    unsigned pgrid = 0;
-    if constexpr (!EDGE) {
-        const Options& o = options();
-        if (o.tiled_persist && !t.no_persist && !ua) {  // (the persistent form keeps aligned vector accesses)
-            static const int ncu = [] {
-                int dev = 0, n = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-                (void)hipGetLastError();
-                return n;
-            }();
-            i64 wpc = std::min<i64>(2048 >> THRLOG, lds ? (i64)(160 * 1024 / lds) : 8);
-            wpc = std::max<i64>(1, std::min<i64>(wpc, 4));  // measured: 4 workgroups per CU beat 8 and 2
-            if (o.tiled_persist_wpc > 0) wpc = o.tiled_persist_wpc;
-            const i64 cap = (i64)ncu * wpc / 8 * 8;
-            if ((i64)grid_ >= cap * o.tiled_persist_min && cap >= 8) pgrid = (unsigned)cap;
-        }
+    L.pgrid = 0;
+    if (!EDGE && o.tiled_persist && !t.no_persist && !ua) {  // (the persistent form keeps aligned vector accesses)
+        i64 wpc = std::min<i64>(2048 >> THRLOG, L.lds ? (i64)(160 * 1024 / L.lds) : 8);
+        wpc = std::max<i64>(1, std::min<i64>(wpc, 4));  // measured: 4 workgroups per CU beat 8 and 2
+        if (o.tiled_persist_wpc > 0) wpc = o.tiled_persist_wpc;
+        const i64 cap = (i64)cu_count() * wpc / 8 * 8;
+        if ((i64)L.grid >= cap * o.tiled_persist_min && cap >= 8) L.pgrid = (unsigned)cap;
     }
-    auto launch = [&](const TiledArgs<WIDE>& ka) -> int {
-        auto b2s = [](bool b) { return b ? "true" : "false"; };
-        if constexpr (is_jit<F>::value) {
-            JitLaunch l;
-            l.family = "tiled";
-            l.tname = tname<T>();
-            l.argtype = WIDE ? "smr::TiledArgs<true>" : "smr::TiledArgs<false>";
-            if (pgrid)
-                l.entry = std::string("smr::tiled_map_pipe_body<") + tname<T>() + ", smr::FJit, " + b2s(MIXED) + ", " + b2s(WIDE) + ", " +
-                          std::to_string(V) + ", " + std::to_string(THRLOG) + ">(a, smr::FJit{kc});";
-            else
-                l.entry = std::string("smr::tiled_map_body<") + tname<T>() + ", smr::FJit, " + b2s(MIXED) + ", " + b2s(WIDE) + ", " +
-                          std::to_string(V) + ", " + std::to_string(MODE) + ", " + std::to_string(THRLOG) + ">(a, smr::FJit{kc});";
-            l.grid = pgrid ? pgrid : grid_;
-            l.block = 1u << THRLOG;
-            l.lds = lds;
-            l.args = &ka;
-            l.argsize = sizeof ka;
-            return jit_launch(c, l, s);
-        } else {
-            if (jit_no_launch()) return SMR_OK;
-            clear_sticky_error();
-            if constexpr (!EDGE) {
-                if (pgrid) {
-                    auto kern = k_tiled_map_pipe<T, F, MIXED, WIDE, V, THRLOG>;
-                    if (lds > 64 * 1024) {
-                        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                        if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
-                    }
-                    SMR_LAUNCH(kern, dim3(pgrid), dim3(1u << THRLOG), lds, s, ka, f SMR_STAMP_ARG(pgrid, 1u << THRLOG));
-                    return check_launch("k_tiled_map_pipe");
-                }
-            }
-            auto kern = k_tiled_map<T, F, MIXED, WIDE, V, MODE, THRLOG>;
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
-            }
-            mark_sliceable(1, (unsigned)offsetof(TiledArgs<WIDE>, blk0), 0);  // a workgroup owns its tile: block ranges are independent
-            if (ka.nts == 2) mark_self_released();
-            SMR_LAUNCH(kern, dim3(grid_), dim3(1u << THRLOG), lds, s, ka, f SMR_STAMP_ARG(grid_, 1u << THRLOG));
-            return check_launch("k_tiled_map");
-        }
-    };
-    TiledArgs<WIDE> a;
     // non-temporal stores: measured faster or equal whenever a tile writes whole 128-byte lines (32^4 Float64
     // permutedims! 3.36 -> 2.76 us, 128^4 864 -> 818 us, never slower for a consumer kernel that follows);
     // partial lines must meet in L2 first, so short destination runs keep plain stores
-    int nts_now = (options().nt_store > 0) ? 1 : 0;
-    if (options().nt_store < 0) {
+    int nts_now = (o.nt_store > 0) ? 1 : 0;
+    if (o.nt_store < 0) {
         const i64 run = std::min<i64>(c.dims[0], (i64)1 << t.tlog[0]) * c.esize[0];
         nts_now = (c.strides[0][0] == 1 && run >= 128) ? 1 : 0;
     }
     // write-through stores (policy 2): forced, or a launch recorded for a sequence (its packet then needs no release fence).  Only the
     // one-shot vector form: there every store of the kernel is one of the vector stores below.
-    if constexpr (V > 1 && !MIXED && has_wt_store<TVec<T, V>>::value) {
-        if (pgrid == 0 && (options().nt_store == 2 || want_self_release(plan))) nts_now = 2;
-    }
-    // the arguments depend on the plan only, except for the operand addresses: built once
-    std::vector<unsigned char>& cached = plan.tiled_args[variant];
-    if (cached.size() == sizeof a) {
-        std::memcpy(&a, cached.data(), sizeof a);
-        if constexpr ((MODE & 4) == 0) {
-            if (!a.base32 || a.ng > NG) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, ua);
-        }
+    if (wt_store && L.pgrid == 0 && (o.nt_store == 2 || want_self_release(plan))) nts_now = 2;
+    const int variant = (WIDE ? 2 : 0) + (V > 1 ? 1 : 0);
+    Plan::FormCache& cached = plan.tiled_cache[variant];
+    if (cached.args.size() == sizeof a) {
+        std::memcpy(&a, cached.args.data(), sizeof a);
+        L.lean_fails = LEAN && (!a.base32 || a.ng > NG);
         for (int k = 0; k < c.M; ++k) a.op[k].base = tab.base[k];
         a.nts = nts_now;
-        return launch(a);
+        return SMR_OK;
     }
     std::memset(&a, 0, sizeof a);
-    a.nwork = (int32_t)grid_;
+    a.nwork = (int32_t)L.grid;
     if (!t.ord.empty() && t.ord.size() <= (size_t)NORD16 && t.grid < 0xffff) {
         a.ordmode = 1;
         for (size_t i = 0; i < t.ord.size(); ++i) {
@@ -951,18 +907,9 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
         }
     } else if (!t.ord.empty()) {
         a.ordmode = 2;
-        if (!plan.ordtab && !jit_dry_run()) {
-            void* dptr = nullptr;
-            hipError_t e = hipMalloc(&dptr, t.ord.size() * sizeof(uint32_t));
-            if (e != hipSuccess) return hip_error(e, "hipMalloc(tile order)");
-            e = hipMemcpy(dptr, t.ord.data(), t.ord.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(dptr);
-                return hip_error(e, "hipMemcpy(tile order)");
-            }
-            plan.ordtab = dptr;
-        }
-        a.ordtab = reinterpret_cast<const uint32_t*>(plan.ordtab);
+        if (!plan.tiled_order && !jit_dry_run())
+            if (int rc = upload_table(&plan.tiled_order, t.ord.data(), t.ord.size() * sizeof(uint32_t), "tile order")) return rc;
+        a.ordtab = reinterpret_cast<const uint32_t*>(plan.tiled_order);
     }
     a.M = c.M;
     a.nt = t.nt;
@@ -978,10 +925,10 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
     }
     // LDS swizzle: slot width = the 128 B an LDS write group spans, in elements
     int w = 0;
-    while ((sizeof(T) << w) < 128) ++w;
+    while ((esize << w) < 128) ++w;
     std::vector<LanePattern> pats;
-    if (sizeof(T) >= 4 && t.tilelog > w) {
-        const int nread = sizeof(T) == 16 ? 4 : 5;  // ds_read_b32/b64: 32 lanes, b128: 16 lanes per pass
+    if (esize >= 4 && t.tilelog > w) {
+        const int nread = esize == 16 ? 4 : 5;  // ds_read_b32/b64: 32 lanes, b128: 16 lanes per pass
         for (int k = 1; k < c.M; ++k) {
             if (t.staged[k] < 0) continue;
             // operand k's enumeration: its bit (vlog + i) is lane bit i of the write group
@@ -1003,7 +950,7 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
         pats.push_back(r);
     }
     int cost0 = 0, cost1 = 0;
-    constexpr bool BITS = SMR_TILED_BITS && !WIDE && (MODE & 4) == 0;
+    const bool BITS = SMR_TILED_BITS && !WIDE && LEAN;
     Swizzle swz = choose_swizzle(t.tilelog, w, pats, &cost0, &cost1);
     uint32_t fs1 = 31, fs2 = 31, fmask = 0;
     if (BITS && swz.w != 32) {
@@ -1070,10 +1017,10 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
     // with two -- (100,90,80) permutes -- a tie or a loss: those keep the planner's order.  tiled_edge_first = 2: whenever it applies)
     // ... with two or more they keep the planner's order and only count backwards ((257,129,65) 8.2 -> 7.8 us, (1400,1500) 6.6 -> 6.5;
     // moved to the slow end as well: (300,301,35) 12.1 -> 13.1).  tiled_edge_first = 3: backwards only, 2: moved + backwards, always
-    if (EDGE && (MODE & 4) == 0 && t.ord.empty() && (options().tiled_edge_first == 3 || (options().tiled_edge_first == 1 && nragged >= 2))) {
+    if (EDGE && LEAN && t.ord.empty() && (o.tiled_edge_first == 3 || (o.tiled_edge_first == 1 && nragged >= 2))) {
         for (int d = 0; d < c.N; ++d)
             if (gof[d] >= 0 && gof[d] < NG && is_ragged(d)) a.gflip |= 1u << gof[d];
-    } else if (EDGE && (MODE & 4) == 0 && t.ord.empty() && (options().tiled_edge_first == 2 || (options().tiled_edge_first == 1 && nragged == 1))) {
+    } else if (EDGE && LEAN && t.ord.empty() && (o.tiled_edge_first == 2 || (o.tiled_edge_first == 1 && nragged == 1))) {
         // ragged dims to the slow end of the grid (stable), counted backwards
         int order[MAXN], n2 = 0;
         for (int pass = 0; pass < 2; ++pass)
@@ -1144,13 +1091,13 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
         if (span >= 4294967296.0L) base32 = false;
     }
     a.base32 = base32 ? 1 : 0;
-    if constexpr ((MODE & 4) == 0) {
-        // the lean variants assume 32-bit tile origins over at most 4 grid dims
-        if (!base32 || ng > NG) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, ua);
+    if (LEAN && (!base32 || ng > NG)) {  // (variant 7 builds and caches the arguments)
+        L.lean_fails = true;
+        return SMR_OK;
     }
 
     // per-lane table: built once per (plan, kernel variant), kept in device memory (not needed by the BITS form)
-    const bool build_tab = !BITS && plan.lanetab[variant] == nullptr && !jit_dry_run();
+    const bool build_tab = !BITS && cached.tab == nullptr && !jit_dry_run();
     a.fs1 = fs1;
     a.fs2 = fs2;
     a.fmask = fmask;
@@ -1221,28 +1168,51 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
     }
     for (int r = 0; r < NREP; ++r) a.Lrd[r] = a.op[0].Lr[r];
     for (int h = 0; h < V; ++h) a.Lhd[h] = a.op[0].Lh[h];
-    if (build_tab) {
-        void* dptr = nullptr;
-        const size_t bytes = rows.size() * sizeof(LaneRow<WIDE>);
-        hipError_t e = hipMalloc(&dptr, bytes);
-        if (e != hipSuccess) return hip_error(e, "hipMalloc(lane table)");
-        // synchronous upload, once per plan and kernel variant (must not happen inside a stream
-        // capture: execute a plan once before capturing it into a hipGraph)
-        e = hipMemcpy(dptr, rows.data(), bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(dptr);
-            return hip_error(e, "hipMemcpy(lane table)");
-        }
-        plan.lanetab[variant] = dptr;
-    }
-    a.lanetab = reinterpret_cast<const LaneRow<WIDE>*>(plan.lanetab[variant]);
+    if (build_tab)
+        if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(LaneRow<WIDE>), "lane table")) return rc;
+    a.lanetab = reinterpret_cast<const LaneRow<WIDE>*>(cached.tab);
 
     if (!jit_dry_run()) {
-        cached.resize(sizeof a);
-        std::memcpy(cached.data(), &a, sizeof a);
+        cached.args.resize(sizeof a);
+        std::memcpy(cached.args.data(), &a, sizeof a);
     }
     a.nts = nts_now;
-    return launch(a);
+    return SMR_OK;
+}
+
+template <class T, class F, bool MIXED, bool WIDE, int V, int MODE, int THRLOG>
+static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua = false) {
+    TiledLaunch<WIDE> L;
+    constexpr bool wt_store = V > 1 && !MIXED && has_wt_store<TVec<T, V>>::value;
+    if (int rc = build_tiled_args<WIDE>(plan, tab, (int)sizeof(T), V, MODE, THRLOG, ua, wt_store, L)) return rc;
+    const TiledArgs<WIDE>& ka = L.a;
+    const unsigned block = 1u << THRLOG;
+    auto launch = [&]() -> int {
+        if constexpr (is_jit<F>::value) {
+            const char* argtype = WIDE ? "smr::TiledArgs<true>" : "smr::TiledArgs<false>";
+            if (L.pgrid) return launch_jit<T>(plan.c, s, "tiled", argtype, "tiled_map_pipe_body", "", L.pgrid, block, L.lds, ka, MIXED, WIDE, V, THRLOG);
+            return launch_jit<T>(plan.c, s, "tiled", argtype, "tiled_map_body", "", L.grid, block, L.lds, ka, MIXED, WIDE, V, MODE, THRLOG);
+        } else {
+            if constexpr ((MODE & 1) == 0) {
+                if (L.pgrid) {
+                    auto kern = k_tiled_map_pipe<T, F, MIXED, WIDE, V, THRLOG>;
+                    return launch_native((const void*)kern, L.lds, "k_tiled_map_pipe",
+                                         [&] { SMR_LAUNCH(kern, dim3(L.pgrid), dim3(block), L.lds, s, ka, f SMR_STAMP_ARG(L.pgrid, block)); });
+                }
+            }
+            auto kern = k_tiled_map<T, F, MIXED, WIDE, V, MODE, THRLOG>;
+            return launch_native((const void*)kern, L.lds, "k_tiled_map", [&] {
+                mark_sliceable(1, (unsigned)offsetof(TiledArgs<WIDE>, blk0), 0);  // a workgroup owns its tile: block ranges are independent
+                if (ka.nts == 2) mark_self_released();
+                SMR_LAUNCH(kern, dim3(L.grid), dim3(block), L.lds, s, ka, f SMR_STAMP_ARG(L.grid, block));
+            });
+        }
+    };
+    // (after the lambda: the kernels it names keep their place in the code object, ahead of variant 7's)
+    if constexpr ((MODE & 4) == 0) {
+        if (L.lean_fails) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, ua);
+    }
+    return launch();
 }
 
 template <class T, class F, bool MIXED, bool WIDE, int V, int THRLOG>
@@ -1272,32 +1242,30 @@ static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua =
 // The same at element alignment (round 6): odd extents, odd row strides, views that begin inside a vector.  Every operand still runs
 // along its unit axis; the one partial vector at the end of a row (extent not a multiple of V) is moved element by element by the
 // workgroups of the ragged last tile.  Elements of 4 or 8 bytes.
-template <class T>
-static bool vector_ok_ua(const Plan& plan, const OpTab& tab, int V) {
+static bool vector_ok_ua(const Plan& plan, const OpTab& tab, int V, int esize) {
     const Canon& c = plan.c;
     const TilePlan& t = plan.tile;
     int vlog = 0;
     while ((1 << vlog) < V) ++vlog;
-    if (sizeof(T) < 4) return false;
+    if (esize < 4) return false;
     for (int k = 0; k < c.M; ++k) {
         const bool staged = k > 0 && t.staged[k] >= 0;
         const int j0 = staged ? t.order[k][0] : 0;
         const int d0 = t.tdim[j0];
         if (t.tlog[j0] < vlog) return false;
         if (c.strides[k][d0] != 1 || c.dims[d0] < V) return false;
-        if (((uintptr_t)tab.base[k]) % sizeof(T)) return false;
+        if (((uintptr_t)tab.base[k]) % esize) return false;
     }
     return true;
 }
 
 // Can every operand be accessed V elements at a time (V * sizeof(T) <= 16 bytes)?
-template <class T>
-static bool vector_ok(const Plan& plan, const OpTab& tab, int V) {
+static bool vector_ok(const Plan& plan, const OpTab& tab, int V, int esize) {
     const Canon& c = plan.c;
     const TilePlan& t = plan.tile;
     int vlog = 0;
     while ((1 << vlog) < V) ++vlog;
-    const size_t vb = (size_t)V * sizeof(T);
+    const size_t vb = (size_t)V * esize;
     for (int k = 0; k < c.M; ++k) {
         const bool staged = k > 0 && t.staged[k] >= 0;
         const int j0 = staged ? t.order[k][0] : 0;  // first axis of this operand's enumeration
@@ -1319,8 +1287,8 @@ static int go_tl(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool na
     if constexpr (!MIXED && sizeof(T) < 16) {
         // a lane's 4 elements as 16-byte vectors (8-byte for 1/2-byte element types)
         constexpr int VMAX = (16 / sizeof(T)) > 4 ? 4 : (int)(16 / sizeof(T));
-        if (options().tiled_vec && vector_ok<T>(plan, tab, VMAX)) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab);
-        if (options().tiled_vec && options().tiled_uavec && vector_ok_ua<T>(plan, tab, VMAX)) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab, true);
+        if (options().tiled_vec && vector_ok(plan, tab, VMAX, (int)sizeof(T))) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab);
+        if (options().tiled_vec && options().tiled_uavec && vector_ok_ua(plan, tab, VMAX, (int)sizeof(T))) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab, true);
     }
     return go3<T, F, MIXED, false, 1, THRLOG>(plan, s, f, tab);
 }
@@ -1447,16 +1415,9 @@ static int try_xpose_big(const Plan& plan, hipStream_t s, F f, const OpTab& tab)
         }
         a.ng = ng;
         if (grid < 1 || grid > 0x7fffffffLL) return SMR_EUNSUPPORTED;
-        if (jit_no_launch()) return SMR_OK;  // (prepare mode: this form has no tables to build)
         const size_t lds = (size_t)T0 * (TQ + 2) * sizeof(T);
         auto kern = k_xpose_big<T, F, V, T0, TQ>;
-        clear_sticky_error();
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return hip_error(e, "hipFuncSetAttribute(lds)");
-        }
-        SMR_LAUNCH(kern, dim3((unsigned)grid), dim3(1024), lds, s, a, f);
-        return check_launch("k_xpose_big");
+        return launch_native((const void*)kern, lds, "k_xpose_big", [&] { SMR_LAUNCH(kern, dim3((unsigned)grid), dim3(1024), lds, s, a, f); });
     }
 }
 
@@ -1491,19 +1452,7 @@ template <>
 int launch_tiled_map_ct<SMR_CT>(const Plan& plan, void* const* bases, hipStream_t s) {
     typedef ct_type<SMR_CT>::type T;
     const Canon& c = plan.c;
-    if (c.bitcopy) {
-#if SMR_CT == SMR_F32
-        switch (c.esize[0]) {
-            case 1: return go<b8, FIdent<b8>, false>(plan, bases, s, FIdent<b8>{});
-            case 2: return go<b16, FIdent<b16>, false>(plan, bases, s, FIdent<b16>{});
-            case 4: return go<float, FIdent<float>, false>(plan, bases, s, FIdent<float>{});
-            case 8: return go<double, FIdent<double>, false>(plan, bases, s, FIdent<double>{});
-            default: return go<c64, FIdent<c64>, false>(plan, bases, s, FIdent<c64>{});
-        }
-#else
-        return set_error(SMR_EINVAL, "bitcopy is dispatched through the f32 object");
-#endif
-    }
+    if (c.bitcopy) return with_bitcopy<SMR_CT>(c, [&](auto f) { return go<typename ident_elem<decltype(f)>::type, decltype(f), false>(plan, bases, s, f); });
     if (c.mixed) return with_prog<T>(c, [&](auto f) { return go<T, decltype(f), true>(plan, bases, s, f); });
     switch (c.fkind) {  // natively compiled functors of this family; everything else is compiled at run time
         case FK_IDENT: return go<T, FIdent<T>, false>(plan, bases, s, FIdent<T>{});
