@@ -356,6 +356,19 @@ int canonicalise(const smr_problem* p, Canon& c);
 int make_plan(const smr_problem* p, Plan& plan);
 void describe(Plan& plan);
 
+// REDUCE_ALL / REDUCE_PART: what one execution of a reduction plan launches for the given operand bases (nullptr: the bases the
+// plan was made with).  The launchers (smr_k_reduce.hip: go_all, go_part) and describe() both take it from here.
+enum RedFold { RED_FOLD_EPILOGUE = 0, RED_FOLD_IN_LAUNCH = 1, RED_FOLD_SECOND_LAUNCH = 2 };
+struct RedLaunch {
+    int vec = 1;          // elements per vector load (1: the scalar path)
+    int fold = RED_FOLD_EPILOGUE;  // how the partials reach the destination: one workgroup's epilogue, the last workgroup to
+                                   // arrive, or a second launch (k_reduce_final / k_reduce_part_final)
+    int nparts = 1;       // REDUCE_ALL: workgroups (= partials); REDUCE_PART: chunks of the reduced range per output
+    i64 groups = 0;       // REDUCE_PART: workgroups along the outputs
+    int ctx = 0, cty = 0, cy0 = 0, cy1 = 0;  // COL: lanes along kept dim 0 x rows (cy0 along the inner reduced dim x cy1 along q)
+};
+RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch);
+
 // ---- runtime compilation of f-programs without a natively compiled functor (smr_jit.cpp) ------------
 // The kernel family's own source file is compiled by hiprtc with the f-program turned into a
 // C++ functor (straight-line code over the same mathx<T> primitives the interpreter calls, so

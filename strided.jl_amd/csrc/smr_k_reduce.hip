@@ -856,32 +856,22 @@ static int go_all(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     RedArgs a;
     fill_args(plan, bases, a);
     a.linear = (c.N == 1) ? 1 : 0;
-    int blocks = plan.red_blocks;
-    if (blocks > 1 && !plan.scratch) blocks = 1;
+    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width and fold form (smr_plan.cpp)
+    const int blocks = r.nparts;
     a.nparts = blocks;
-    // up to 64 partials are folded inside the launch (1 MiB: 4.9 -> 4.1 us; tools/reduce_all_sweep.py) -- the arrivals of ONE
-    // counter serialise, so larger reductions keep the second launch (8 MiB with 256 workgroups: 6.6 vs 5.4 us)
-    const i64 rs = options().reduce_single;
-    a.single = (blocks > 1 && rs > 0 && blocks <= std::max<i64>(rs, 64)) ? 1 : 0;
-    // vector path: one fused dim, every input unit stride / broadcast, 16-B aligned
+    a.single = r.fold == RED_FOLD_IN_LAUNCH ? 1 : 0;
     constexpr int VMAX = (sizeof(T) >= 16) ? 1 : (int)(16 / sizeof(T));
-    bool vec = !MIXED && VMAX > 1 && c.N == 1 && (c.total % VMAX == 0) && c.total >= 4096;
-    for (int k = 1; k < c.M && vec; ++k) {
-        if (c.strides[k][0] == 0) continue;
-        if (c.strides[k][0] != 1) vec = false;
-        if (((uintptr_t)a.ops.base[k]) % 16) vec = false;
-    }
     int rc = SMR_OK;
     bool done = false;
     if constexpr (!MIXED && VMAX > 1) {
-        if (vec) {
+        if (r.vec == VMAX) {
             rc = launch_all<T, F, false, VMAX>(c, a, blocks, s, f);
             done = true;
         }
     }
     if (!done) rc = launch_all<T, F, MIXED, 1>(c, a, blocks, s, f);
     if (rc) return rc;
-    if (blocks > 1 && !a.single) rc = launch_native(nullptr, 0, "k_reduce_final", [&] { SMR_LAUNCH((k_reduce_final<T, MIXED>), dim3(1), dim3(256), 0, s, a); });
+    if (r.fold == RED_FOLD_SECOND_LAUNCH) rc = launch_native(nullptr, 0, "k_reduce_final", [&] { SMR_LAUNCH((k_reduce_final<T, MIXED>), dim3(1), dim3(256), 0, s, a); });
     return rc;
 }
 
@@ -908,25 +898,22 @@ static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     const Canon& c = plan.c;
     RedArgs a;
     fill_args(plan, bases, a);
-    const bool have_scratch = plan.scratch != nullptr;
-    int nsplit = (plan.part_split > 1 && have_scratch) ? plan.part_split : 1;
+    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width, fold form, groups (smr_plan.cpp)
+    const int nsplit = r.nparts;
     a.nsplit = nsplit;
-    a.single = (nsplit > 1 && nsplit <= options().reduce_single) ? 1 : 0;
+    a.single = r.fold == RED_FOLD_IN_LAUNCH ? 1 : 0;
     a.xsplit = a.qsplit = 1;
-    i64 blocks = 0;
+    const i64 groups = r.groups;
+    a.ngroups = (int32_t)groups;
+    const i64 blocks = groups * nsplit;
+    if (blocks > 0x7fffffffLL || groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
     int rc;
     constexpr int VMAX = (MIXED || sizeof(T) >= 16) ? 1 : (int)(16 / sizeof(T));
     if (plan.part_kind == 0) {
         a.tr = plan.part_tr;
         a.trlog = 0;
         while ((1 << a.trlog) < a.tr) ++a.trlog;
-        const int ob = 256 / a.tr;
-        const i64 groups = (c.nout + ob - 1) / ob;
-        a.ngroups = (int32_t)groups;
-        if (groups > RED_COUNTERS) a.single = 0;
         a.chunk = ((a.nred + nsplit - 1) / nsplit + a.tr - 1) / a.tr * a.tr;
-        blocks = groups * nsplit;
-        if (blocks > 0x7fffffffLL || groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
         rc = launch_part<T, F, MIXED, 0, 1>(c, a, blocks, s, f);
     } else {
         a.g0log = plan.part_g0log;
@@ -939,28 +926,14 @@ static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
             a.qsplit = plan.part_qsplit;
         }
         a.qchunk = (a.Q + a.qsplit - 1) / a.qsplit;
-        // vector width: the vector axis must divide, every vector-loaded operand must be aligned
-        const int vax = plan.part_kind == 1 ? c.NK : 0;  // axis the vectors run along
-        bool vec = VMAX > 1 && (c.dims[vax] % VMAX == 0);
-        for (int k = 1; k < c.M && vec; ++k) {
-            if (c.strides[k][vax] != 1) continue;
-            if (((uintptr_t)a.ops.base[k]) % 16) vec = false;
-            for (int d = 0; d < c.N; ++d)
-                if (d != vax && (c.strides[k][d] % VMAX)) vec = false;
-        }
-        const int V = vec ? VMAX : 1;
+        const int V = r.vec;
+        rc = SMR_OK;
+        bool done = false;
         if (plan.part_kind == 1) {
             const i64 unit = ((i64)V) << a.g0log;
             a.xchunk = ((a.L0 + a.xsplit - 1) / a.xsplit + unit - 1) / unit * unit;
-            const i64 groups = (c.nout + (256 >> (a.g0log + a.g1log)) - 1) / (256 >> (a.g0log + a.g1log));
-            a.ngroups = (int32_t)groups;
-            if (groups > RED_COUNTERS) a.single = 0;
-            blocks = groups * nsplit;
-            if (blocks > 0x7fffffffLL || groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
-            rc = SMR_OK;
-            bool done = false;
             if constexpr (VMAX > 1) {
-                if (vec) {
+                if (V == VMAX) {
                     rc = launch_part<T, F, MIXED, 1, VMAX>(c, a, blocks, s, f);
                     done = true;
                 }
@@ -968,29 +941,15 @@ static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
             if (!done) rc = launch_part<T, F, MIXED, 1, 1>(c, a, blocks, s, f);
         } else {
             a.xchunk = (a.L0 + a.xsplit - 1) / a.xsplit;
-            a.ctx = 1 << a.txlog;
-            a.cty = 256 >> a.txlog;
-            a.cy0 = 1 << a.g0log;
-            a.cy1 = 1 << a.g1log;
-            if (plan.part_col_tx > 0 && plan.part_col_v == V) {  // exact lane map (smr_plan.cpp), planned for this vector width
-                a.ctx = plan.part_col_tx;
-                a.cty = 256 / a.ctx;
-                a.cy0 = plan.part_col_y0;
-                a.cy1 = plan.part_col_y1;
-            }
+            a.ctx = r.ctx;
+            a.cty = r.cty;
+            a.cy0 = r.cy0;
+            a.cy1 = r.cy1;
             a.ctx_m = (65536u + (uint32_t)a.ctx - 1u) / (uint32_t)a.ctx;
             a.cy0_m = (65536u + (uint32_t)a.cy0 - 1u) / (uint32_t)a.cy0;
-            const i64 per = (i64)V * a.ctx;
-            a.nkb0 = (c.dims[0] + per - 1) / per;
-            const i64 groups = a.nkb0 * (c.nout / c.dims[0]);
-            a.ngroups = (int32_t)groups;
-            if (groups > RED_COUNTERS) a.single = 0;
-            blocks = groups * nsplit;
-            if (blocks > 0x7fffffffLL || groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
-            rc = SMR_OK;
-            bool done = false;
+            a.nkb0 = (c.dims[0] + (i64)V * a.ctx - 1) / ((i64)V * a.ctx);
             if constexpr (VMAX > 1) {
-                if (vec) {
+                if (V == VMAX) {
                     rc = launch_part<T, F, MIXED, 2, VMAX>(c, a, blocks, s, f);
                     done = true;
                 }
@@ -998,7 +957,7 @@ static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
             if (!done) rc = launch_part<T, F, MIXED, 2, 1>(c, a, blocks, s, f);
         }
     }
-    if (rc || nsplit == 1 || a.single || jit_no_launch()) return rc;
+    if (rc || r.fold != RED_FOLD_SECOND_LAUNCH || jit_no_launch()) return rc;
     // lanes per output of the folding pass: as many as there are partials (up to a wave), fewer
     // when there are plenty of outputs anyway
     int lpolog = 0;

@@ -2172,6 +2172,75 @@ int make_plan(const smr_problem* p, Plan& plan) {
     return SMR_OK;
 }
 
+RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch) {
+    const Canon& c = plan.c;
+    RedLaunch r;
+    const int es = dtype_size(c.ct);
+    auto aligned16 = [&](int k) {  // operand k's element-offset base (as make_optab computes it) is 16-byte aligned
+        const uintptr_t b = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]);
+        return b % 16 == 0;
+    };
+    const i64 rs = options().reduce_single;
+    if (plan.family == FAM_REDUCE_ALL) {
+        int blocks = plan.red_blocks;
+        if (blocks > 1 && !have_scratch) blocks = 1;
+        r.nparts = blocks;
+        // up to 64 partials are folded inside the launch (1 MiB: 4.9 -> 4.1 us; tools/reduce_all_sweep.py) -- the arrivals of ONE
+        // counter serialise, so larger reductions keep the second launch (8 MiB with 256 workgroups: 6.6 vs 5.4 us)
+        const bool single = blocks > 1 && rs > 0 && blocks <= std::max<i64>(rs, 64);
+        r.fold = blocks == 1 ? RED_FOLD_EPILOGUE : (single ? RED_FOLD_IN_LAUNCH : RED_FOLD_SECOND_LAUNCH);
+        // vector path: one fused dim, every input unit stride / broadcast, 16-B aligned
+        const int vmax = es >= 16 ? 1 : 16 / es;
+        bool vec = !c.mixed && vmax > 1 && c.N == 1 && (c.total % vmax == 0) && c.total >= 4096;
+        for (int k = 1; k < c.M && vec; ++k) {
+            if (c.strides[k][0] == 0) continue;
+            if (c.strides[k][0] != 1) vec = false;
+            if (!aligned16(k)) vec = false;
+        }
+        r.vec = vec ? vmax : 1;
+        return r;
+    }
+    if (plan.family != FAM_REDUCE_PART) return r;
+    const int nsplit = (plan.part_split > 1 && have_scratch) ? plan.part_split : 1;
+    r.nparts = nsplit;
+    const int vmax = (c.mixed || es >= 16) ? 1 : 16 / es;
+    if (plan.part_kind == 0) {
+        const int ob = 256 / plan.part_tr;
+        r.groups = (c.nout + ob - 1) / ob;
+    } else {
+        // vector width: the vector axis must divide, every vector-loaded operand must be aligned
+        const int vax = plan.part_kind == 1 ? c.NK : 0;  // axis the vectors run along
+        bool vec = vmax > 1 && (c.dims[vax] % vmax == 0);
+        for (int k = 1; k < c.M && vec; ++k) {
+            if (c.strides[k][vax] != 1) continue;
+            if (!aligned16(k)) vec = false;
+            for (int d = 0; d < c.N; ++d)
+                if (d != vax && (c.strides[k][d] % vmax)) vec = false;
+        }
+        r.vec = vec ? vmax : 1;
+        if (plan.part_kind == 1) {
+            const int ob = 256 >> (plan.part_g0log + plan.part_g1log);
+            r.groups = (c.nout + ob - 1) / ob;
+        } else {
+            r.ctx = 1 << plan.part_txlog;
+            r.cty = 256 >> plan.part_txlog;
+            r.cy0 = 1 << plan.part_g0log;
+            r.cy1 = 1 << plan.part_g1log;
+            if (plan.part_col_tx > 0 && plan.part_col_v == r.vec) {  // exact lane map (make_plan), planned for this vector width
+                r.ctx = plan.part_col_tx;
+                r.cty = 256 / r.ctx;
+                r.cy0 = plan.part_col_y0;
+                r.cy1 = plan.part_col_y1;
+            }
+            const i64 per = (i64)r.vec * r.ctx;
+            r.groups = ((c.dims[0] + per - 1) / per) * (c.nout / c.dims[0]);
+        }
+    }
+    const bool single = nsplit > 1 && nsplit <= rs && r.groups <= RED_COUNTERS;
+    r.fold = nsplit == 1 ? RED_FOLD_EPILOGUE : (single ? RED_FOLD_IN_LAUNCH : RED_FOLD_SECOND_LAUNCH);
+    return r;
+}
+
 void describe(Plan& plan) {
     const Canon& c = plan.c;
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat"};
@@ -2218,6 +2287,12 @@ void describe(Plan& plan) {
         n += std::snprintf(buf + n, sizeof buf - n, " nout=%lld form=%s lanes_per_out=%d split=%d", (long long)c.nout, kinds[plan.part_kind],
                            plan.part_tr, plan.part_split);
         if (plan.part_kind == 2 && plan.part_col_tx) n += std::snprintf(buf + n, sizeof buf - n, " lanes=%dx%d", plan.part_col_tx, 256 / plan.part_col_tx);
+    }
+    if (plan.family == FAM_REDUCE_ALL || plan.family == FAM_REDUCE_PART) {
+        // as launched with the bases the plan was made with (the partials buffer is allocated on the first execution)
+        static const char* folds[] = {"epilogue", "in-launch", "second-launch"};
+        const RedLaunch r = reduce_launch(plan, nullptr, true);
+        n += std::snprintf(buf + n, sizeof buf - n, " vec=%d fold=%s", r.vec, folds[r.fold]);
     }
     if (c.int_wraps) n += std::snprintf(buf + n, sizeof buf - n, " int_wraps=%d", c.int_wraps);
     std::snprintf(buf + n, sizeof buf - n, " algbytes=%lld", (long long)c.algbytes);
