@@ -152,7 +152,7 @@ typedef enum {
                             (`B32 .= A32 .* 0.1` multiplies in Float64 in Julia and rounds once on store) */
     /* 23..28 are the library's own: a user program holding one is malformed (SMR_EINVAL).  The integer class inserts them where
        Julia would have observed a narrow intermediate result at its own width (Int32 a .* b into an Int64 destination, UInt8
-       min(a - b, c), ...): the 64-bit value is reduced to its low 8 / 16 / 32 bits, sign- or zero-extended (csrc/smr_plan.cpp) */
+       min(a - b, c), ...): the 64-bit value is reduced to its low 8 / 16 / 32 bits, sign- or zero-extended (csrc/smr_canon.cpp) */
     SMR_OP_WRAP_I8 = 23,
     SMR_OP_WRAP_I16 = 24,
     SMR_OP_WRAP_I32 = 25,

@@ -1033,7 +1033,7 @@ void julia_int_types(const smr_problem* p, Prog& prog) {
 }
 
 // the integer class applies when every operand is an integer type and f is closed over the integers (the same rule as
-// the device planner, csrc/smr_plan.cpp: canonicalise)
+// the device planner, csrc/smr_canon.cpp: canonicalise)
 bool integer_class(const smr_problem* p, const Prog& prog) {
     bool has_u64 = false, has_signed = false, has_const = false, eqne = false;
     for (int k = 0; k < p->M; ++k) {

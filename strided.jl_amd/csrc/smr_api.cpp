@@ -288,8 +288,8 @@ static int plan_build(const smr_problem* p, smr_plan** out) {
 // reduction partials are allocated on first execution (planning itself needs no device)
 static int ensure_scratch(smr_plan* h) {
     std::lock_guard<std::mutex> g(*h->plan.build_mu);
-    if (h->plan.scratch || h->plan.scratch_bytes == 0 || h->plan.red_blocks <= 1) return SMR_OK;
-    const size_t coff = (h->plan.scratch_bytes + 255) & ~(size_t)255;
+    if (h->plan.scratch || h->plan.red.scratch_bytes == 0) return SMR_OK;
+    const size_t coff = (h->plan.red.scratch_bytes + 255) & ~(size_t)255;
     void* buf = nullptr;
     hipError_t e = hipMalloc(&buf, coff + RED_COUNTERS * sizeof(unsigned));
     if (e != hipSuccess) return hip_error(e, "hipMalloc(reduction partials)");

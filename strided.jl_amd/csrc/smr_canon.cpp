@@ -1,0 +1,626 @@
+// smr_canon.cpp -- what planning starts from and what knows nothing of kernel families: the options, the f-program checks and
+// typing, and canonicalise(), the GPU analogue of _mapreduce_fuse! (src/mapreduce.jl:98-117): drop / sort / flip / fuse / dedupe.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "smr_internal.h"
+
+namespace smr {
+
+Options& options() {
+    static Options o = [] {
+        Options d;
+        if (const char* e = std::getenv("SMR_JIT")) d.jit = std::atoll(e);  // SMR_JIT=0: always interpret
+        return d;
+    }();
+    return o;
+}
+
+// ---- f-program validation / recognition -------------------------------------------------------
+static int check_prog(const ProgD& p, int M, int& maxdepth) {
+    int sp = 0;
+    maxdepth = 0;
+    for (int pc = 0; pc < p.len; ++pc) {
+        int op = p.code[2 * pc], imm = p.code[2 * pc + 1];
+        if (op == SMR_OP_ARG) {
+            if (imm < 1 || imm >= M) return -1;
+            ++sp;
+        } else if (op == SMR_OP_CONST) {
+            if (imm >= p.nconst) return -1;
+            ++sp;
+        } else if (op >= SMR_OP_NEG && op <= SMR_OP_WIDEN) {
+            if (sp < 1) return -1;
+        } else if (op >= SMR_OP_POWI && op <= SMR_OP_NOT) {
+            if (sp < 1) return -1;
+        } else if ((op >= SMR_OP_ADD && op <= SMR_OP_NE) || (op >= SMR_OP_POW && op <= SMR_OP_XOR)) {
+            if (sp < 2) return -1;
+            --sp;
+        } else if (op == SMR_OP_SELECT || op == SMR_OP_FMA) {
+            if (sp < 3) return -1;
+            sp -= 2;
+        } else {
+            return -1;
+        }
+        maxdepth = std::max(maxdepth, sp);
+    }
+    return sp == 1 ? 0 : -1;
+}
+
+// Julia types every integer operation by its operands (Int32 * Int32 wraps at 32 bits, Int8 - Int8 at 8, a literal is Int64), the
+// integer class computes everything in one 64-bit domain.  The two agree exactly when no value that Julia would have wrapped at a
+// narrower width is ever OBSERVED at a wider one.  Per stack slot: (`bits`, `sgn`) = Julia's type of the value, `cong` = the device
+// value is congruent to Julia's modulo 2^cong (64: identical; otherwise cong >= bits).  Ring operations (+ - * neg abs2) keep
+// congruences modulo the width of their result, order and equality (min max abs < <= == select's condition ...) need identical
+// operands, and the destination (width wd) observes the low wd bits.
+// Round 5: where an observer needs more than the slot offers, the value is re-wrapped to its Julia type right after the instruction
+// that produced it (SMR_OP_WRAP_*: sign- or zero-extension of the low bits, one or two VALU instructions) -- lazily, so
+// `Int32 a .* b .+ c` into an Int32 destination stays the three-instruction program it was, `Int32 a .* b` into an Int64 destination
+// gets one wrap at the end, and UInt8 `min(a - b, c)` one after the subtraction.  (Before: both were refused with SMR_EUNSUPPORTED,
+// ADVICE r3 / VERDICT r4 "missing #4".)  Returns false only for what cannot be typed statically: arithmetic on the result of an
+// ifelse whose branches have different types.
+static bool int_class_fit_julia(const smr_problem* p, const bool* isbool, ProgD& prog, int* nwraps) {
+    auto width = [](int dt) { return 8 << ((dt - SMR_I8) & 3); };  // I8 I16 I32 I64 U8 U16 U32 U64
+    struct Slot {
+        int bits;
+        bool sgn;
+        int cong;
+        int prod;  // the instruction that produced the value
+        bool amb;  // one of two differently typed ifelse branches: Julia's type depends on the data
+    };
+    Slot st[STACK + 4];
+    int sp = 0, wrap_after[SMR_MAXPROG] = {0}, nw = 0;
+    auto promote = [](const Slot& a, const Slot& b, int& bits, bool& sgn) {
+        if (a.bits == 1) { bits = b.bits; sgn = b.sgn; return; }
+        if (b.bits == 1) { bits = a.bits; sgn = a.sgn; return; }
+        if (a.bits != b.bits) { const Slot& w = a.bits > b.bits ? a : b; bits = w.bits; sgn = w.sgn; return; }
+        bits = a.bits; sgn = a.sgn && b.sgn;
+    };
+    auto exact = [&](Slot& s) {  // cong < 64 implies 8 <= bits <= cong < 64
+        if (s.cong == 64) return;
+        static const int code[2][3] = {{SMR_OP_WRAP_U8, SMR_OP_WRAP_U16, SMR_OP_WRAP_U32}, {SMR_OP_WRAP_I8, SMR_OP_WRAP_I16, SMR_OP_WRAP_I32}};
+        wrap_after[s.prod] = code[s.sgn ? 1 : 0][s.bits == 8 ? 0 : s.bits == 16 ? 1 : 2];
+        s.cong = 64;
+        ++nw;
+    };
+    for (int pc = 0; pc < prog.len; ++pc) {
+        const int op = prog.code[2 * pc], imm = prog.code[2 * pc + 1];
+        switch (op) {
+            case SMR_OP_ARG:
+                if (isbool[imm]) st[sp++] = {1, false, 64, pc, false};
+                else st[sp++] = {width(p->ops[imm].dtype), p->ops[imm].dtype < SMR_U8, 64, pc, false};
+                break;
+            case SMR_OP_CONST: st[sp++] = {64, true, 64, pc, false}; break;
+            case SMR_OP_CONJ: case SMR_OP_REAL: st[sp - 1].prod = pc; break;
+            case SMR_OP_IMAG: st[sp - 1] = {64, true, 64, pc, false}; break;
+            case SMR_OP_WIDEN:
+                exact(st[sp - 1]);
+                st[sp - 1] = {64, true, 64, pc, false};
+                break;
+            case SMR_OP_NEG: case SMR_OP_ABS2: {
+                Slot& a = st[sp - 1];
+                if (a.amb) return false;
+                a.prod = pc;
+                if (a.bits == 1) {  // Bool: -true is an Int, abs2(true) is true
+                    if (op == SMR_OP_NEG) { a.bits = 64; a.sgn = true; }
+                    break;
+                }
+                a.cong = std::min(a.cong, a.bits);
+                break;
+            }
+            case SMR_OP_ABS: {
+                Slot& a = st[sp - 1];
+                if (a.amb) return false;
+                exact(a);
+                a.prod = pc;
+                if (a.bits > 1 && a.sgn) a.cong = a.bits;  // abs(typemin) wraps at the operand's width
+                break;
+            }
+            case SMR_OP_ADD: case SMR_OP_SUB: case SMR_OP_MUL: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb) return false;
+                int w;
+                bool sg;
+                promote(a, b, w, sg);
+                if (a.bits == 1 && b.bits == 1) {  // Bool * Bool is a Bool, Bool (+,-) Bool an Int
+                    if (op != SMR_OP_MUL) { w = 64; sg = true; }
+                }
+                // an operand Julia converts to a wider type first must be identical, not merely congruent at its own width
+                if (a.cong < w) exact(a);
+                if (b.cong < w) { exact(b); }
+                a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                break;
+            }
+            // math opcodes (strided_hip.h 65, 96.., 128..): x ^ n (n >= 0), ~ and & | xor are ring operations; floor ceil trunc round
+            // are identities; sign, rem and mod need exact operands (rem / mod by an Int64 literal: the result is an Int64)
+            case SMR_OP_POWI: case SMR_OP_NOT: {
+                Slot& a = st[sp - 1];
+                if (a.amb) return false;
+                a.prod = pc;
+                if (a.bits == 1) {  // Bool ^ n is a Bool (0 or 1 either way; true ^ 0 = true); ~true would be -2: the front ends send XOR
+                    if (op == SMR_OP_NOT) return false;
+                    break;
+                }
+                a.cong = std::min(a.cong, a.bits);
+                break;
+            }
+            case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: st[sp - 1].prod = pc; break;
+            case SMR_OP_SIGN: {
+                Slot& a = st[sp - 1];
+                exact(a);
+                a.prod = pc;
+                break;
+            }
+            case SMR_OP_REM: case SMR_OP_MOD: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb) return false;
+                exact(a);
+                exact(b);
+                a = {64, true, 64, pc, false};
+                break;
+            }
+            case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb) return false;
+                int w;
+                bool sg;
+                promote(a, b, w, sg);  // Bool & Bool is a Bool
+                if (a.cong < w) exact(a);
+                if (b.cong < w) exact(b);
+                a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                break;
+            }
+            case SMR_OP_FMA: {  // a*b + c, typed as that expression; the product cannot be re-wrapped on its own
+                Slot c = st[--sp], b = st[--sp];
+                Slot& a = st[sp - 1];
+                if (a.amb || b.amb || c.amb) return false;
+                int w, w2;
+                bool sg, sg2;
+                promote(a, b, w, sg);
+                if (a.cong < w) exact(a);
+                if (b.cong < w) exact(b);
+                Slot m = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
+                promote(m, c, w2, sg2);
+                if (m.bits == 1 && c.bits == 1) { w2 = 64; sg2 = true; }
+                if (m.cong < w2) return false;
+                if (c.cong < w2) exact(c);
+                a = {w2, sg2, w2 == 1 ? 64 : std::min({m.cong, c.cong, w2}), pc, false};
+                break;
+            }
+            case SMR_OP_MIN: case SMR_OP_MAX: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                exact(a);
+                exact(b);
+                int w;
+                bool sg;
+                promote(a, b, w, sg);
+                // min(::Int8, ::UInt32) promotes to UInt32 and throws for a negative value in Julia; the oracle keeps the mathematical
+                // value.  Either way it is not a value of the promoted type: never re-wrapped, no arithmetic on it.
+                a = {w, sg, 64, pc, a.amb || b.amb || (!sg && ((a.sgn && a.bits > 1) || (b.sgn && b.bits > 1)))};
+                break;
+            }
+            case SMR_OP_LT: case SMR_OP_LE: case SMR_OP_GT: case SMR_OP_GE: case SMR_OP_EQ: case SMR_OP_NE: {
+                Slot b = st[--sp];
+                Slot& a = st[sp - 1];
+                exact(a);
+                exact(b);
+                a = {1, false, 64, pc, false};  // Bool
+                break;
+            }
+            case SMR_OP_SELECT: {
+                Slot c = st[--sp], b = st[--sp];
+                Slot& a = st[sp - 1];
+                exact(a);
+                const bool same = b.bits == c.bits && b.sgn == c.sgn && !b.amb && !c.amb;  // (a data-dependent type is never re-wrapped: it stays identical)
+                if (!same) { exact(b); exact(c); }
+                int w;
+                bool sg;
+                promote(b, c, w, sg);
+                a = {w, sg, std::min(b.cong, c.cong), pc, !same || b.amb || c.amb};
+                break;
+            }
+            default: return false;
+        }
+    }
+    const int wd = width(p->ops[0].dtype);
+    const bool ring = p->redop == SMR_RED_NONE || p->redop == SMR_RED_ADD || p->redop == SMR_RED_MUL;
+    if (!(ring ? st[0].cong >= wd : st[0].cong == 64)) exact(st[0]);
+    if (nwraps) *nwraps = nw;
+    if (nw == 0) return true;
+    if (prog.len + nw > SMR_MAXPROG) return false;
+    uint8_t code[2 * SMR_MAXPROG];
+    int n = 0;
+    for (int pc = 0; pc < prog.len; ++pc) {
+        code[2 * n] = prog.code[2 * pc];
+        code[2 * n + 1] = prog.code[2 * pc + 1];
+        ++n;
+        if (wrap_after[pc]) {
+            code[2 * n] = (uint8_t)wrap_after[pc];
+            code[2 * n + 1] = 0;
+            ++n;
+        }
+    }
+    std::memcpy(prog.code, code, sizeof(uint8_t) * 2 * (size_t)n);
+    prog.len = n;
+    return true;
+}
+
+static void recognise(Canon& c) {
+    const ProgD& p = c.prog;
+    auto op = [&](int i) { return (int)p.code[2 * i]; };
+    auto im = [&](int i) { return (int)p.code[2 * i + 1]; };
+    auto isarg = [&](int i, int k) { return op(i) == SMR_OP_ARG && im(i) == k; };
+    auto isconst = [&](int i) { return op(i) == SMR_OP_CONST; };
+    auto cre = [&](int i) { return p.consts[2 * im(i)]; };
+    auto cim = [&](int i) { return p.consts[2 * im(i) + 1]; };
+    c.fkind = FK_PROG;
+    const int n = p.len, nin = c.M - 1;
+    if (n == 1 && isarg(0, 1) && nin == 1) { c.fkind = FK_IDENT; return; }
+    if (n == 3 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && nin == 2) { c.fkind = FK_ADD2; return; }
+    if (n == 5 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isarg(3, 3) && op(4) == SMR_OP_ADD && nin == 3) {
+        c.fkind = FK_ADD3; return;
+    }
+    if (n == 7 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isarg(3, 3) && op(4) == SMR_OP_ADD &&
+        isarg(5, 4) && op(6) == SMR_OP_ADD && nin == 4) {
+        c.fkind = FK_ADD4; return;
+    }
+    if (n == 3 && nin == 1 && op(2) == SMR_OP_MUL &&
+        ((isarg(0, 1) && isconst(1)) || (isconst(0) && isarg(1, 1)))) {
+        int ci = isconst(0) ? 0 : 1;
+        c.fkind = FK_SCALE; c.fc[0] = cre(ci); c.fc[1] = cim(ci); return;
+    }
+    if (n == 5 && nin == 2 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isconst(3) && op(4) == SMR_OP_DIV) {
+        c.fkind = FK_SYM; c.fc[0] = cre(3); c.fc[1] = cim(3); return;
+    }
+    if (n == 5 && nin == 2 && isconst(0) && isarg(1, 1) && op(2) == SMR_OP_MUL && isarg(3, 2) && op(4) == SMR_OP_ADD) {
+        c.fkind = FK_AXPY; c.fc[0] = cre(0); c.fc[1] = cim(0); return;
+    }
+    if (n == 7 && nin == 2 && isconst(0) && isarg(1, 1) && op(2) == SMR_OP_MUL && isconst(3) && isarg(4, 2) &&
+        op(5) == SMR_OP_MUL && op(6) == SMR_OP_ADD) {
+        c.fkind = FK_AXPBY; c.fc[0] = cre(0); c.fc[1] = cim(0); c.fc[2] = cre(3); c.fc[3] = cim(3); return;
+    }
+    if (n == 2 && nin == 1 && isarg(0, 1) && op(1) == SMR_OP_ABS2) { c.fkind = FK_ABS2; return; }
+    if (n == 3 && nin == 2 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_MUL) { c.fkind = FK_MUL2; return; }
+    // a .* exp.(c .* a) .+ sin.(a .* a)   (real types)
+    if (n == 11 && nin == 1 && (c.ct == SMR_F32 || c.ct == SMR_F64) && isarg(0, 1) && isconst(1) && isarg(2, 1) &&
+        op(3) == SMR_OP_MUL && op(4) == SMR_OP_EXP && op(5) == SMR_OP_MUL && isarg(6, 1) && isarg(7, 1) &&
+        op(8) == SMR_OP_MUL && op(9) == SMR_OP_SIN && op(10) == SMR_OP_ADD && cim(1) == 0.0) {
+        c.fkind = FK_EXPR5; c.fc[0] = cre(1); return;
+    }
+}
+
+// ---- canonicalisation ---------------------------------------------------------------------------
+int canonicalise(const smr_problem* p0, Canon& c) {
+    if (!p0) return set_error(SMR_EINVAL, "null problem");
+    // Bool operands are UInt8 operands for every kernel; only the typing of an integer f-program tells them apart
+    smr_problem pcopy = *p0;
+    bool isbool[MAXM] = {false};
+    if (pcopy.M >= 1 && pcopy.M <= MAXM)
+        for (int k = 0; k < pcopy.M; ++k)
+            if (pcopy.ops[k].dtype == SMR_BOOL) {
+                isbool[k] = true;
+                pcopy.ops[k].dtype = SMR_U8;
+            }
+    const smr_problem* p = &pcopy;
+    const int N0 = p->N, M0 = p->M;
+    if (N0 < 1 || N0 > MAXN) return set_error(SMR_EINVAL, "rank N out of range 1..8");
+    if (M0 < 1 || M0 > MAXM) return set_error(SMR_EINVAL, "operand count M out of range 1..8");
+    for (int i = 0; i < N0; ++i)
+        if (p->dims[i] < 1) return set_error(SMR_EINVAL, "every dim must be >= 1 (zero-size is handled by the caller, src/mapreduce.jl:48,88)");
+    for (int k = 0; k < M0; ++k) {
+        if (!p->ops[k].base) return set_error(SMR_EINVAL, "null operand base pointer");
+        if (dtype_size(p->ops[k].dtype) == 0) return set_error(SMR_EINVAL, "bad operand dtype");
+    }
+    if (p->redop < SMR_RED_NONE || p->redop > SMR_RED_OR) return set_error(SMR_EINVAL, "bad redop");
+    if (p->initop < SMR_INIT_NONE || p->initop > SMR_INIT_CONJ) return set_error(SMR_EINVAL, "bad initop");
+    if (p->redop == SMR_RED_NONE && p->initop != SMR_INIT_NONE)
+        return set_error(SMR_EINVAL, "initop requires a reduction op (src/mapreduce.jl:310-316)");
+
+    // program
+    ProgD& prog = c.prog;
+    std::memset(&prog, 0, sizeof(prog));
+    if (!p->fprog || p->fprog_len == 0) {
+        if (M0 < 2) return set_error(SMR_EINVAL, "identity program needs an input");
+        prog.len = 1;
+        prog.code[0] = SMR_OP_ARG;
+        prog.code[1] = 1;
+    } else {
+        if (p->fprog_len < 0 || p->fprog_len > SMR_MAXPROG) return set_error(SMR_EINVAL, "f-program too long");
+        prog.len = p->fprog_len;
+        std::memcpy(prog.code, p->fprog, (size_t)(2 * p->fprog_len));
+    }
+    if (p->nconsts < 0 || p->nconsts > SMR_MAXCONST) return set_error(SMR_EINVAL, "too many constants");
+    if (p->nconsts > 0 && !p->fconsts) return set_error(SMR_EINVAL, "null fconsts");
+    prog.nconst = p->nconsts;
+    for (int i = 0; i < 2 * p->nconsts; ++i) prog.consts[i] = p->fconsts[i];
+    int depth = 0;
+    if (check_prog(prog, std::max(M0, 1), depth) != 0) return set_error(SMR_EINVAL, "malformed f-program");
+    if (depth > STACK) return set_error(SMR_EUNSUPPORTED, "f-program needs more than 8 stack slots");
+    if (!options().jit && prog_uses_math(prog))
+        return set_error(SMR_EUNSUPPORTED, "f-program with a math opcode (pow, fma, tan, rem, &, ...) with option \"jit\" = 0: the interpreter does not run them");
+
+    // compute class (Julia promote_type over the operand eltypes, restricted to the four
+    // float classes of the reference tests)
+    bool dbl = false, cplx = false, anyint = false;
+    for (int k = 0; k < M0; ++k) {
+        int dt = p->ops[k].dtype;
+        if (dt == SMR_F64 || dt == SMR_C64) dbl = true;
+        if (dt == SMR_C32 || dt == SMR_C64) cplx = true;
+        if (dt >= SMR_I8) { anyint = true; dbl = true; }
+    }
+    for (int i = 0; i < prog.nconst; ++i)
+        if (prog.consts[2 * i + 1] != 0.0) cplx = true;
+    for (int pc = 0; pc < prog.len; ++pc)
+        if (prog.code[2 * pc] == SMR_OP_WIDEN) dbl = true;  // a 64-bit scalar takes part (strided_hip.h)
+    c.ct = cplx ? (dbl ? SMR_C64 : SMR_C32) : (dbl ? SMR_F64 : SMR_F32);
+    // The integer class (round 3): every operand has an integer eltype and f stays inside the integers -> wrapping
+    // 64-bit arithmetic like Julia's (typeof(op(...)) is the accumulator type, src/mapreduce.jl:55-72); narrower
+    // destinations truncate on store.  UInt64 takes part in ring operations only (no order on the device).
+    {
+        bool allint = true, has_u64 = false, has_signed = false, has_const = false, eqne = false;
+        for (int k = 0; k < M0; ++k) {
+            if (p->ops[k].dtype < SMR_I8) allint = false;
+            if (p->ops[k].dtype == SMR_U64) has_u64 = true;
+            if (p->ops[k].dtype >= SMR_I8 && p->ops[k].dtype <= SMR_I64) has_signed = true;
+        }
+        bool closed = true, ordered = p->redop == SMR_RED_MIN || p->redop == SMR_RED_MAX, negpow = false, baddiv = false;
+        for (int pc = 0; pc < prog.len && closed; ++pc) {
+            const int op = prog.code[2 * pc];
+            switch (op) {
+                case SMR_OP_ARG: case SMR_OP_NEG: case SMR_OP_ABS2: case SMR_OP_CONJ: case SMR_OP_REAL: case SMR_OP_IMAG:
+                case SMR_OP_ADD: case SMR_OP_SUB: case SMR_OP_MUL: case SMR_OP_SELECT: case SMR_OP_WIDEN: break;
+                case SMR_OP_ABS: case SMR_OP_MIN: case SMR_OP_MAX: case SMR_OP_LT: case SMR_OP_LE: case SMR_OP_GT: case SMR_OP_GE:
+                    ordered = true;
+                    break;
+                // == and !=: equality of bit patterns IS Julia's equality as long as nothing signed can meet a UInt64 -- Julia
+                // compares a UInt64 with a signed value mathematically (-1 != 0xffff...ff), a 64-bit domain compares the patterns.
+                // Signed values come from signed operands and from constants (integer literals are Int64: UInt8 - 10 is an Int64).
+                case SMR_OP_EQ: case SMR_OP_NE:
+                    eqne = true;
+                    break;
+                // math opcodes that stay in the integers (the rest -- pow, the transcendentals -- compute in Float64 like sqrt)
+                case SMR_OP_NOT: case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: case SMR_OP_FMA:
+                case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: break;
+                case SMR_OP_POWI:
+                    if ((int8_t)prog.code[2 * pc + 1] < 0) negpow = true;
+                    break;
+                case SMR_OP_SIGN: ordered = true; break;
+                case SMR_OP_REM: case SMR_OP_MOD: {
+                    ordered = true;
+                    const bool cdiv = pc > 0 && prog.code[2 * (pc - 1)] == SMR_OP_CONST;
+                    if (!cdiv || prog.consts[2 * prog.code[2 * pc - 1]] == 0.0) baddiv = true;
+                    break;
+                }
+                case SMR_OP_CONST: {
+                    has_const = true;
+                    const double re = prog.consts[2 * prog.code[2 * pc + 1]], im = prog.consts[2 * prog.code[2 * pc + 1] + 1];
+                    // integer-valued (or a +-Inf seed of a min / max reduction, which saturates to typemax / typemin)
+                    if (im != 0.0 || !(re == std::floor(re) || std::isinf(re)) || (std::fabs(re) > 9223372036854775808.0 && !std::isinf(re))) closed = false;
+                    break;
+                }
+                default: closed = false;
+            }
+        }
+        if (p->initop == SMR_INIT_SCALE || p->initop == SMR_INIT_CONST) {
+            const double re = p->initarg[0], im = p->initarg[1];
+            if (im != 0.0 || re != std::floor(re) || std::fabs(re) > 9223372036854775808.0) closed = false;
+        }
+        if (eqne && has_u64 && (has_signed || has_const)) ordered = true;  // (round 5: all-unsigned equality tests are exact and stay on the device)
+        if (allint && negpow)
+            return set_error(SMR_EUNSUPPORTED, "integer x ^ n with a negative literal n (Julia throws DomainError)");
+        if (allint && baddiv)
+            return set_error(SMR_EUNSUPPORTED, "integer rem / mod with a divisor that is not a non-zero constant (Julia throws DivideError on a zero divisor)");
+        if (allint && closed && !(has_u64 && ordered)) {
+            if (!int_class_fit_julia(p, isbool, prog, &c.int_wraps))
+                return set_error(SMR_EUNSUPPORTED,
+                                 "integer f-program that cannot be typed statically (arithmetic on an ifelse whose branches have different integer "
+                                 "types), or too long once narrow intermediate results are re-wrapped to their Julia types");
+            c.ct = SMR_I64;
+        }
+    }
+    c.redop = p->redop;
+    c.initop = p->initop;
+    c.initarg[0] = p->initarg[0];
+    c.initarg[1] = p->initarg[1];
+    c.bitcopy = false;
+    if (anyint && c.ct == SMR_I64 && p->redop == SMR_RED_NONE && M0 == 2 && p->ops[0].dtype == p->ops[1].dtype && prog.len == 1 &&
+        prog.code[0] == SMR_OP_ARG) {
+        c.bitcopy = true;  // a pure move stays a bit copy of opaque elements (any width, vectorised)
+        c.ct = SMR_F64;
+    }
+    if (anyint && c.ct != SMR_I64 && !c.bitcopy) {
+        bool pure = p->redop == SMR_RED_NONE && M0 == 2 && p->ops[0].dtype == p->ops[1].dtype && prog.len == 1 &&
+                    prog.code[0] == SMR_OP_ARG;
+        if (pure) c.bitcopy = true;
+        // Integer data that is not merely moved is computed in Float64 (the four float classes are the device
+        // scope): exact for every value of an 8/16/32-bit type and for sums / counts below
+        // 2^53, which is what the reference's integer tests need (counting reductions, test/othertests.jl:116,123).
+        // 64-bit integer INPUTS can hold values a double cannot: refuse them instead of rounding silently -- the
+        // reference-side binding falls back to the CPU method (Julia's wrapping Int64 arithmetic).
+        if (!pure)
+            for (int k = 1; k < M0; ++k)
+                if (p->ops[k].dtype == SMR_I64 || p->ops[k].dtype == SMR_U64)
+                    return set_error(SMR_EUNSUPPORTED,
+                                     "64-bit integer inputs outside the integer class (all operands integer, f built from + - * neg abs abs2 min max "
+                                     "comparisons select and integer constants): the arithmetic would run in Float64, which is exact only below 2^53");
+    }
+
+    // working copies
+    int N = 0;
+    i64 dims[MAXN];
+    i64 str[MAXM][MAXN];
+    int M = M0;
+    for (int i = 0; i < N0; ++i) {
+        if (p->dims[i] == 1) continue;  // size-1 dims carry no information
+        dims[N] = p->dims[i];
+        for (int k = 0; k < M0; ++k) str[k][N] = p->ops[k].strides[i];
+        ++N;
+    }
+    i64 off[MAXM];
+    void* base[MAXM];
+    int dtype[MAXM], conj[MAXM];
+    for (int k = 0; k < M0; ++k) {
+        off[k] = p->ops[k].offset;
+        base[k] = p->ops[k].base;
+        dtype[k] = p->ops[k].dtype;
+        conj[k] = (p->ops[k].conj && (dtype[k] == SMR_C32 || dtype[k] == SMR_C64)) ? 1 : 0;
+    }
+
+    // dedupe identical inputs (capturestridedargs does not: src/broadcast.jl:41-46), and
+    // drop inputs the program never reads
+    {
+        int remap[MAXM];
+        bool used[MAXM] = {false};
+        for (int pc = 0; pc < prog.len; ++pc)
+            if (prog.code[2 * pc] == SMR_OP_ARG) used[prog.code[2 * pc + 1]] = true;
+        int newM = 1;
+        int keep[MAXM];
+        keep[0] = 0;
+        for (int k = 1; k < M; ++k) {
+            remap[k] = -1;
+            if (!used[k]) continue;
+            for (int j = 1; j < newM; ++j) {
+                int q = keep[j];
+                bool same = base[q] == base[k] && off[q] == off[k] && dtype[q] == dtype[k] && conj[q] == conj[k];
+                for (int i = 0; i < N && same; ++i) same = str[q][i] == str[k][i];
+                if (same) { remap[k] = j; break; }
+            }
+            if (remap[k] < 0) { keep[newM] = k; remap[k] = newM; ++newM; }
+        }
+        for (int pc = 0; pc < prog.len; ++pc)
+            if (prog.code[2 * pc] == SMR_OP_ARG) prog.code[2 * pc + 1] = (uint8_t)remap[prog.code[2 * pc + 1]];
+        i64 s2[MAXM][MAXN], o2[MAXM];
+        void* b2[MAXM];
+        int d2[MAXM], c2[MAXM];
+        for (int j = 0; j < newM; ++j) {
+            int q = keep[j];
+            for (int i = 0; i < N; ++i) s2[j][i] = str[q][i];
+            o2[j] = off[q]; b2[j] = base[q]; d2[j] = dtype[q]; c2[j] = conj[q];
+            c.orig[j] = q;
+        }
+        M = newM;
+        for (int j = 0; j < M; ++j) {
+            for (int i = 0; i < N; ++i) str[j][i] = s2[j][i];
+            off[j] = o2[j]; base[j] = b2[j]; dtype[j] = d2[j]; conj[j] = c2[j];
+        }
+    }
+
+    // a pure map must not alias destination elements (the reference would serialise the
+    // writes; on a GPU that is a race)
+    if (p->redop == SMR_RED_NONE)
+        for (int i = 0; i < N; ++i)
+            if (str[0][i] == 0) return set_error(SMR_EUNSUPPORTED, "map into a destination with a zero stride");
+
+    // flip dims so that destination strides (kept dims) / first-input strides (reduced dims)
+    // are positive; iteration direction is irrelevant for map and for associative reductions
+    for (int i = 0; i < N; ++i) {
+        i64 lead = str[0][i];
+        if (lead == 0)
+            for (int k = 1; k < M && lead == 0; ++k) lead = str[k][i];
+        if (lead < 0)
+            for (int k = 0; k < M; ++k) {
+                off[k] += (dims[i] - 1) * str[k][i];
+                str[k][i] = -str[k][i];
+            }
+    }
+
+    // sort: kept dims by destination stride, then reduced dims by smallest input stride
+    std::vector<int> perm(N);
+    for (int i = 0; i < N; ++i) perm[i] = i;
+    auto minin = [&](int i) {
+        i64 m = INT64_MAX;
+        for (int k = 1; k < M; ++k)
+            if (str[k][i] != 0) m = std::min<i64>(m, std::llabs(str[k][i]));
+        return m;
+    };
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
+        bool ra = str[0][a] == 0, rb = str[0][b] == 0;
+        if (ra != rb) return !ra;
+        if (!ra) return str[0][a] < str[0][b];
+        return minin(a) < minin(b);
+    });
+    i64 sd[MAXN], ss[MAXM][MAXN];
+    for (int i = 0; i < N; ++i) {
+        sd[i] = dims[perm[i]];
+        for (int k = 0; k < M; ++k) ss[k][i] = str[k][perm[i]];
+    }
+    // fuse adjacent dims that are jointly contiguous in every operand (same rule as
+    // src/mapreduce.jl:103-115, applied after sorting so it fires more often); never across
+    // the kept/reduced boundary
+    int NF = 0;
+    i64 fd[MAXN], fs[MAXM][MAXN];
+    for (int i = 0; i < N; ++i) {
+        bool merged = false;
+        if (NF > 0) {
+            bool kb = fs[0][NF - 1] != 0, ka = ss[0][i] != 0;
+            bool ok = (kb == ka);
+            for (int k = 0; k < M && ok; ++k) ok = ss[k][i] == fd[NF - 1] * fs[k][NF - 1];
+            if (ok) {
+                fd[NF - 1] *= sd[i];
+                merged = true;
+            }
+        }
+        if (!merged) {
+            fd[NF] = sd[i];
+            for (int k = 0; k < M; ++k) fs[k][NF] = ss[k][i];
+            ++NF;
+        }
+    }
+    if (NF == 0) {  // every dim had size 1: a single element
+        NF = 1;
+        fd[0] = 1;
+        for (int k = 0; k < M; ++k) fs[k][0] = (k == 0 && p->redop == SMR_RED_NONE) ? 1 : 0;
+        if (p->redop != SMR_RED_NONE) fs[0][0] = 0;
+    }
+    c.N = NF;
+    c.M = M;
+    c.NK = 0;
+    c.total = 1;
+    c.nout = 1;
+    for (int i = 0; i < NF; ++i) {
+        c.dims[i] = fd[i];
+        c.total *= fd[i];
+        if (fs[0][i] != 0) { c.NK = i + 1; c.nout *= fd[i]; }
+    }
+    if (p->redop == SMR_RED_NONE) { c.NK = NF; }
+    c.mixed = false;
+    for (int k = 0; k < M; ++k) {
+        for (int i = 0; i < NF; ++i) c.strides[k][i] = fs[k][i];
+        for (int i = NF; i < MAXN; ++i) c.strides[k][i] = 0;
+        c.offsets[k] = off[k];
+        c.base[k] = base[k];
+        c.dtype[k] = dtype[k];
+        c.conj[k] = conj[k];
+        c.esize[k] = dtype_size(dtype[k]);
+        if (dtype[k] != c.ct) c.mixed = true;
+    }
+    for (int i = NF; i < MAXN; ++i) c.dims[i] = 1;
+    if (c.bitcopy) c.mixed = false;
+
+    // algorithmic bytes: every distinct buffer once
+    {
+        std::map<void*, i64> foot;
+        for (int k = 0; k < M; ++k) {
+            i64 n = 1;
+            for (int i = 0; i < NF; ++i)
+                if (c.strides[k][i] != 0) n *= c.dims[i];
+            i64 bytes = n * c.esize[k];
+            auto it = foot.find(c.base[k]);
+            if (it == foot.end()) foot[c.base[k]] = bytes;
+            else it->second = std::max(it->second, bytes);
+        }
+        c.algbytes = 0;
+        for (auto& kv : foot) c.algbytes += kv.second;
+    }
+    recognise(c);
+    return SMR_OK;
+}
+
+}  // namespace smr

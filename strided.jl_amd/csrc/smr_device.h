@@ -258,7 +258,7 @@ struct mathx_real {
     static SMR_DEV bool truthy(R a) { return a != R(0); }
 
     // The math opcodes (strided_hip.h: 65, 96..127, 128..159).  Runtime-compiled kernels only: FJit calls them with the opcode and
-    // the exponent as template arguments, the interpreter never does (its switch stays as small as it is, csrc/smr_plan.cpp refuses
+    // the exponent as template arguments, the interpreter never does (its switch stays as small as it is, csrc/smr_canon.cpp refuses
     // to interpret such a program).  Float32 calls the Float32 entry points of the device math library.
     template <int N>
     static SMR_DEV R powi(R a) {
@@ -314,7 +314,7 @@ template <> struct mathx<float> : mathx_real<float> {};
 template <> struct mathx<double> : mathx_real<double> {};
 
 // integer class: every operation is closed over Int64 and wraps (unsigned arithmetic underneath: no UB);
-// the planner admits only these opcodes (csrc/smr_plan.cpp: canonicalise)
+// the planner admits only these opcodes (csrc/smr_canon.cpp: canonicalise)
 template <> struct mathx<ix64> {
     typedef unsigned long long U;
     static SMR_DEV ix64 un(int op, ix64 a) {
@@ -323,7 +323,7 @@ template <> struct mathx<ix64> {
             case SMR_OP_ABS: return a < 0 ? (ix64)(U(0) - (U)a) : a;  // abs(typemin) = typemin, like Julia
             case SMR_OP_ABS2: return (ix64)((U)a * (U)a);
             case SMR_OP_IMAG: return 0;
-            // Julia's narrow integer types, where their wrapping would be observed (inserted by the planner, csrc/smr_plan.cpp)
+            // Julia's narrow integer types, where their wrapping would be observed (inserted by the planner, csrc/smr_canon.cpp)
             case SMR_OP_WRAP_I8: return (ix64)(signed char)a;
             case SMR_OP_WRAP_I16: return (ix64)(short)a;
             case SMR_OP_WRAP_I32: return (ix64)(int)a;

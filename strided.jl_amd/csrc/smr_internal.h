@@ -217,6 +217,28 @@ struct FlatBPlan {
     uint16_t srcoff[FLATB_MAXP];  // input offset (inside the block) of destination position r
 };
 
+// Description for FAM_STREAM (smr_k_stream.hip); the row packing is derived per launch (build_stream_args).
+struct StreamPlan {
+    int vec = 1;          // elements per vector access
+    bool vec_ua = false;  // `vec` elements per access at ELEMENT alignment, rows end in a partial vector (round 5)
+};
+
+// Description for FAM_REDUCE_ALL / FAM_REDUCE_PART (smr_k_reduce.hip); reduce_launch() derives what one execution launches.
+struct ReducePlan {
+    int nparts = 1;  // partials: REDUCE_ALL: workgroups; REDUCE_PART: chunks of the reduced range per output (two-pass when > 1)
+    size_t scratch_bytes = 0;  // size of the partials buffer (0: none; allocated on the plan's first execution, Plan::scratch)
+    int tr = 1;      // REDUCE_PART: lanes cooperating on one output
+    // REDUCE_PART, vectorised forms (see smr_k_reduce.hip): 1 = ROW (inputs unit-stride along the
+    // first reduced dim), 2 = COL (inputs unit-stride along kept dim 0), 0 = general
+    int kind = 0;
+    int g0log = 0, g1log = 0;  // ROW: lanes of a group along the inner reduced dim / the outer index
+                               // COL: rows of a workgroup along the inner reduced dim / the outer index
+    int txlog = 0;             // COL: lanes along kept dim 0
+    int col_tx = 0, col_v = 1; // COL, exact lane map (round 6): lanes along kept dim 0 (0 = the power of two above), valid for this vector width
+    int col_y0 = 1, col_y1 = 1; //   rows of a workgroup along the inner reduced dim x along the outer index (TY = 256 / tx = y0 * y1)
+    int xsplit = 1, qsplit = 1;  // split of the inner / outer reduced range over workgroups
+};
+
 struct Plan {
     Canon c;
     int family = FAM_GENERIC;
@@ -225,26 +247,11 @@ struct Plan {
     OrbitPlan orbit;
     FlatPlan flat;
     Flat2Plan flat2;
-    // STREAM
-    int vec = 1;        // elements per vector access
-    // reductions
-    bool vec_ua = false;      // STREAM: `vec` elements per access at ELEMENT alignment, rows end in a partial vector (round 5)
+    StreamPlan stream;
+    ReducePlan red;
     mutable bool eager_seen = false;  // the plan's device tables (uploaded by hipMemcpy on its first execution) have been made visible to the direct queues
-    void* scratch = nullptr;  // partials (owned), followed by RED_COUNTERS arrival counters (zero between launches)
-    size_t scratch_bytes = 0;
+    void* scratch = nullptr;  // reductions: partials (owned, ReducePlan::scratch_bytes), followed by RED_COUNTERS arrival counters (zero between launches)
     size_t counter_off = 0;   // byte offset of the counters inside `scratch` (set when it is allocated)
-    int red_blocks = 0;
-    int part_tr = 1;    // REDUCE_PART: lanes cooperating on one output
-    int part_split = 1; // REDUCE_PART: chunks of the reduced range (two-pass when > 1)
-    // REDUCE_PART, vectorised forms (see smr_k_reduce.hip): 1 = ROW (inputs unit-stride along the
-    // first reduced dim), 2 = COL (inputs unit-stride along kept dim 0), 0 = general
-    int part_kind = 0;
-    int part_g0log = 0, part_g1log = 0;  // ROW: lanes of a group along the inner reduced dim / the outer index
-                                         // COL: rows of a workgroup along the inner reduced dim / the outer index
-    int part_txlog = 0;                  // COL: lanes along kept dim 0
-    int part_col_tx = 0, part_col_v = 1; // COL, exact lane map (round 6): lanes along kept dim 0 (0 = the power of two above), valid for this vector width
-    int part_col_y0 = 1, part_col_y1 = 1; //   rows of a workgroup along the inner reduced dim x along the outer index (TY = 256 / tx = y0 * y1)
-    int part_xsplit = 1, part_qsplit = 1;  // split of the inner / outer reduced range over workgroups
     // TILED / ORBIT: a kernel form's arguments, built by the family's argument builder (smr_k_tiled.hip: build_tiled_args,
     // smr_k_orbit.hip: build_orbit_args / build_pair_args) on the plan's first execution of that form, together with the device
     // table it reads; later executions patch the operand addresses only.  Nothing is cached or uploaded by a dry run (jit_dry_run).
@@ -352,8 +359,8 @@ Options& options();
 // SMR_STAMP builds: the region (2 words per wave) of the next launch, or nullptr when no buffer is set / it is full
 unsigned long long* stamp_next(size_t waves);
 
-int canonicalise(const smr_problem* p, Canon& c);
-int make_plan(const smr_problem* p, Plan& plan);
+int canonicalise(const smr_problem* p, Canon& c);  // smr_canon.cpp (with options())
+int make_plan(const smr_problem* p, Plan& plan);  // smr_plan.cpp: selects the family and calls its planner
 void describe(Plan& plan);
 
 // REDUCE_ALL / REDUCE_PART: what one execution of a reduction plan launches for the given operand bases (nullptr: the bases the

@@ -893,75 +893,72 @@ static int launch_part(const Canon& c, const RedArgs& a, i64 blocks, hipStream_t
     }
 }
 
+// Fills the arguments of a partial reduction as reduce_launch() (smr_plan.cpp) says this execution runs: chunks per output, fold form,
+// vector width and -- COL -- the lane map.
+static int build_part_args(const Plan& plan, void* const* bases, const RedLaunch& r, RedArgs& a) {
+    const Canon& c = plan.c;
+    const ReducePlan& rp = plan.red;
+    fill_args(plan, bases, a);
+    a.nsplit = r.nparts;
+    a.single = r.fold == RED_FOLD_IN_LAUNCH ? 1 : 0;
+    a.xsplit = a.qsplit = 1;
+    a.ngroups = (int32_t)r.groups;
+    if (r.groups * r.nparts > 0x7fffffffLL || r.groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
+    if (rp.kind == 0) {
+        a.tr = rp.tr;
+        a.trlog = 0;
+        while ((1 << a.trlog) < a.tr) ++a.trlog;
+        a.chunk = ((a.nred + a.nsplit - 1) / a.nsplit + a.tr - 1) / a.tr * a.tr;
+        return SMR_OK;
+    }
+    a.g0log = rp.g0log;
+    a.g1log = rp.g1log;
+    a.txlog = rp.txlog;
+    a.L0 = c.dims[c.NK];
+    a.Q = a.nred / a.L0;
+    if (a.nsplit > 1) {
+        a.xsplit = rp.xsplit;
+        a.qsplit = rp.qsplit;
+    }
+    a.qchunk = (a.Q + a.qsplit - 1) / a.qsplit;
+    if (rp.kind == 1) {
+        const i64 unit = ((i64)r.vec) << a.g0log;
+        a.xchunk = ((a.L0 + a.xsplit - 1) / a.xsplit + unit - 1) / unit * unit;
+    } else {
+        a.xchunk = (a.L0 + a.xsplit - 1) / a.xsplit;
+        a.ctx = r.ctx;
+        a.cty = r.cty;
+        a.cy0 = r.cy0;
+        a.cy1 = r.cy1;
+        a.ctx_m = (65536u + (uint32_t)a.ctx - 1u) / (uint32_t)a.ctx;
+        a.cy0_m = (65536u + (uint32_t)a.cy0 - 1u) / (uint32_t)a.cy0;
+        a.nkb0 = (c.dims[0] + (i64)r.vec * a.ctx - 1) / ((i64)r.vec * a.ctx);
+    }
+    return SMR_OK;
+}
+
 template <class T, class F, bool MIXED>
 static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     const Canon& c = plan.c;
-    RedArgs a;
-    fill_args(plan, bases, a);
     const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width, fold form, groups (smr_plan.cpp)
-    const int nsplit = r.nparts;
-    a.nsplit = nsplit;
-    a.single = r.fold == RED_FOLD_IN_LAUNCH ? 1 : 0;
-    a.xsplit = a.qsplit = 1;
-    const i64 groups = r.groups;
-    a.ngroups = (int32_t)groups;
-    const i64 blocks = groups * nsplit;
-    if (blocks > 0x7fffffffLL || groups > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "reduce grid too large");
-    int rc;
+    RedArgs a;
+    if (int rc = build_part_args(plan, bases, r, a)) return rc;
+    const i64 blocks = r.groups * r.nparts;
     constexpr int VMAX = (MIXED || sizeof(T) >= 16) ? 1 : (int)(16 / sizeof(T));
-    if (plan.part_kind == 0) {
-        a.tr = plan.part_tr;
-        a.trlog = 0;
-        while ((1 << a.trlog) < a.tr) ++a.trlog;
-        a.chunk = ((a.nred + nsplit - 1) / nsplit + a.tr - 1) / a.tr * a.tr;
+    const bool vec = VMAX > 1 && r.vec == VMAX;
+    int rc;
+    if (plan.red.kind == 0) {
         rc = launch_part<T, F, MIXED, 0, 1>(c, a, blocks, s, f);
+    } else if (plan.red.kind == 1) {
+        rc = vec ? launch_part<T, F, MIXED, 1, VMAX>(c, a, blocks, s, f) : launch_part<T, F, MIXED, 1, 1>(c, a, blocks, s, f);
     } else {
-        a.g0log = plan.part_g0log;
-        a.g1log = plan.part_g1log;
-        a.txlog = plan.part_txlog;
-        a.L0 = c.dims[c.NK];
-        a.Q = a.nred / a.L0;
-        if (nsplit > 1) {
-            a.xsplit = plan.part_xsplit;
-            a.qsplit = plan.part_qsplit;
-        }
-        a.qchunk = (a.Q + a.qsplit - 1) / a.qsplit;
-        const int V = r.vec;
-        rc = SMR_OK;
-        bool done = false;
-        if (plan.part_kind == 1) {
-            const i64 unit = ((i64)V) << a.g0log;
-            a.xchunk = ((a.L0 + a.xsplit - 1) / a.xsplit + unit - 1) / unit * unit;
-            if constexpr (VMAX > 1) {
-                if (V == VMAX) {
-                    rc = launch_part<T, F, MIXED, 1, VMAX>(c, a, blocks, s, f);
-                    done = true;
-                }
-            }
-            if (!done) rc = launch_part<T, F, MIXED, 1, 1>(c, a, blocks, s, f);
-        } else {
-            a.xchunk = (a.L0 + a.xsplit - 1) / a.xsplit;
-            a.ctx = r.ctx;
-            a.cty = r.cty;
-            a.cy0 = r.cy0;
-            a.cy1 = r.cy1;
-            a.ctx_m = (65536u + (uint32_t)a.ctx - 1u) / (uint32_t)a.ctx;
-            a.cy0_m = (65536u + (uint32_t)a.cy0 - 1u) / (uint32_t)a.cy0;
-            a.nkb0 = (c.dims[0] + (i64)V * a.ctx - 1) / ((i64)V * a.ctx);
-            if constexpr (VMAX > 1) {
-                if (V == VMAX) {
-                    rc = launch_part<T, F, MIXED, 2, VMAX>(c, a, blocks, s, f);
-                    done = true;
-                }
-            }
-            if (!done) rc = launch_part<T, F, MIXED, 2, 1>(c, a, blocks, s, f);
-        }
+        rc = vec ? launch_part<T, F, MIXED, 2, VMAX>(c, a, blocks, s, f) : launch_part<T, F, MIXED, 2, 1>(c, a, blocks, s, f);
     }
     if (rc || r.fold != RED_FOLD_SECOND_LAUNCH || jit_no_launch()) return rc;
     // lanes per output of the folding pass: as many as there are partials (up to a wave), fewer
     // when there are plenty of outputs anyway
     int lpolog = 0;
-    while (lpolog < 6 && (4 << lpolog) < nsplit && (c.nout << lpolog) < 256 * 1024) ++lpolog;
+    while (lpolog < 6 && (4 << lpolog) < r.nparts && (c.nout << lpolog) < 256 * 1024) ++lpolog;
     a.trlog = lpolog;
     const i64 fthreads = c.nout << lpolog;
     SMR_LAUNCH((k_reduce_part_final<T, MIXED>), dim3((unsigned)((fthreads + 255) / 256)), dim3(256), 0, s, a);

@@ -194,12 +194,10 @@ __global__ void __launch_bounds__(256) k_stream_map(StreamArgs a, F f SMR_STAMP_
     SMR_STAMP_END
 }
 
-template <class T, class F, bool MIXED, int V>
-static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
+// Fills the kernel arguments of one launch: V elements per access, U accesses in flight per lane.  Sets the grid and the kernel form
+// (0: one row segment per workgroup; 1: packed short rows; 2: packed rows of several column chunks).
+static int build_stream_args(const Plan& plan, void* const* bases, int V, int U, StreamArgs& a, i64& grid, int& form) {
     const Canon& c = plan.c;
-    // vectors in flight per lane: measured on 256-512 MiB maps, 2 x 16 B beats 4 (2-3 %) and 8 (5-8 % worse)
-    constexpr int U = (sizeof(T) * V >= 16) ? 2 : 8;
-    StreamArgs a;
     std::memset(&a, 0, sizeof a);
     a.ops = make_optab(c, bases);
     a.N = c.N;
@@ -245,11 +243,22 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     for (int i = 0; i < MAXN; ++i) a.dims[i] = (i < c.N) ? c.dims[i] : 1;
     for (int k = 0; k < MAXM; ++k)
         for (int i = 0; i < MAXN; ++i) a.strides[k][i] = (k < c.M && i < c.N) ? c.strides[k][i] : 0;
-    const i64 grid = a.bpr * a.rows;
+    grid = a.bpr * a.rows;
     if (grid > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, "stream grid too large");
-    const int form = !a.packed ? 0 : (a.txlog < 8 ? 1 : 2);
+    form = !a.packed ? 0 : (a.txlog < 8 ? 1 : 2);
+    return SMR_OK;
+}
+
+template <class T, class F, bool MIXED, int V>
+static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
+    // vectors in flight per lane: measured on 256-512 MiB maps, 2 x 16 B beats 4 (2-3 %) and 8 (5-8 % worse)
+    constexpr int U = (sizeof(T) * V >= 16) ? 2 : 8;
+    StreamArgs a;
+    i64 grid;
+    int form;
+    if (int rc = build_stream_args(plan, bases, V, U, a, grid, form)) return rc;
     if constexpr (is_jit<F>::value) {
-        return launch_jit<T>(c, s, "stream", "smr::StreamArgs", "stream_map_body", "", (unsigned)grid, 256, 0, a, MIXED, V, U, form);
+        return launch_jit<T>(plan.c, s, "stream", "smr::StreamArgs", "stream_map_body", "", (unsigned)grid, 256, 0, a, MIXED, V, U, form);
     } else {
         return launch_native(nullptr, 0, "k_stream_map", [&] {
             if (form == 0)
@@ -262,21 +271,21 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     }
 }
 
+// The plan chose 16-byte vectors for the pointers it was created with: do rebound ones allow them too?  (Element-aligned vectors --
+// StreamPlan::vec_ua -- take any element address.)
+static bool stream_vec_ok(const Plan& plan, void* const* bases) {
+    if (!bases || plan.stream.vec_ua) return true;
+    const OpTab tab = make_optab(plan.c, bases);
+    for (int k = 0; k < plan.c.M; ++k)
+        if (plan.c.strides[k][0] != 0 && ((uintptr_t)tab.base[k]) % 16) return false;
+    return true;
+}
+
 template <class T, class F>
 static int go_vec(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     constexpr int VMAX = (sizeof(T) >= 16) ? 1 : (int)(16 / sizeof(T));
     if constexpr (VMAX > 1) {
-        if (plan.vec == VMAX) {
-            // the plan chose vectors for the pointers it was created with; re-check rebound ones (element-aligned vectors --
-            // Plan::vec_ua -- take any element address)
-            bool aligned = true;
-            if (bases && !plan.vec_ua) {
-                const OpTab tab = make_optab(plan.c, bases);
-                for (int k = 0; k < plan.c.M; ++k)
-                    if (plan.c.strides[k][0] != 0 && ((uintptr_t)tab.base[k]) % 16) aligned = false;
-            }
-            if (aligned) return go<T, F, false, VMAX>(plan, bases, s, f);
-        }
+        if (plan.stream.vec == VMAX && stream_vec_ok(plan, bases)) return go<T, F, false, VMAX>(plan, bases, s, f);
     }
     return go<T, F, false, 1>(plan, bases, s, f);
 }

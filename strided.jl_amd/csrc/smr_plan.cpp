@@ -2,6 +2,7 @@
 //
 // GPU analogue of the reference's planning chain
 //   _mapreduce_fuse!  (src/mapreduce.jl:98-117)   -> canonicalise(): drop/sort/flip/fuse/dedupe
+//                                                    (smr_canon.cpp, with the f-program checks)
 //   _mapreduce_order! (src/mapreduce.jl:119-139)  -> canonical dim order (destination-stride
 //                                                    sorted) + kernel-family classification
 //   _mapreduce_block!/_computeblocks (:142-180, :452-500)
@@ -13,635 +14,49 @@
 // lives in oracle/ as test infrastructure.
 #include <algorithm>
 #include <array>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
 #include <vector>
 
 #include "smr_internal.h"
 
 namespace smr {
 
-Options& options() {
-    static Options o = [] {
-        Options d;
-        if (const char* e = std::getenv("SMR_JIT")) d.jit = std::atoll(e);  // SMR_JIT=0: always interpret
-        return d;
-    }();
-    return o;
-}
-
 constexpr i64 FLAT_GROUP_MAX = 64;
 
-static int nextpow2_log(i64 v) {
+// ---- helpers shared by the family planners -----------------------------------------------------------
+// bytes per element as the kernels move them: the operands' own for a bit copy, else the compute class's
+static int elem_bytes(const Canon& c) { return c.bitcopy ? c.esize[0] : dtype_size(c.ct); }
+
+// ceil(log2(v)); 0 for v <= 1
+static int ceil_log2(i64 v) {
     int l = 0;
     while (((i64)1 << l) < v) ++l;
     return l;
 }
 
-// ---- f-program validation / recognition -------------------------------------------------------
-static int check_prog(const ProgD& p, int M, int& maxdepth) {
-    int sp = 0;
-    maxdepth = 0;
-    for (int pc = 0; pc < p.len; ++pc) {
-        int op = p.code[2 * pc], imm = p.code[2 * pc + 1];
-        if (op == SMR_OP_ARG) {
-            if (imm < 1 || imm >= M) return -1;
-            ++sp;
-        } else if (op == SMR_OP_CONST) {
-            if (imm >= p.nconst) return -1;
-            ++sp;
-        } else if (op >= SMR_OP_NEG && op <= SMR_OP_WIDEN) {
-            if (sp < 1) return -1;
-        } else if (op >= SMR_OP_POWI && op <= SMR_OP_NOT) {
-            if (sp < 1) return -1;
-        } else if ((op >= SMR_OP_ADD && op <= SMR_OP_NE) || (op >= SMR_OP_POW && op <= SMR_OP_XOR)) {
-            if (sp < 2) return -1;
-            --sp;
-        } else if (op == SMR_OP_SELECT || op == SMR_OP_FMA) {
-            if (sp < 3) return -1;
-            sp -= 2;
-        } else {
-            return -1;
-        }
-        maxdepth = std::max(maxdepth, sp);
-    }
-    return sp == 1 ? 0 : -1;
+// number of chunks an index range of `n` is cut into when about `want` are asked for: all of n when that is
+// within 2x (a trailing dim of 7 cut 6 ways would leave chunks of 2,2,2,1 and two idle workgroups), else a
+// count that leaves no chunk empty
+static i64 even_cut(i64 want, i64 n) {
+    if (n <= 1 || want <= 1) return 1;
+    if (n <= 2 * want) return n;
+    const i64 per = (n + want - 1) / want;
+    return (n + per - 1) / per;
 }
 
-// Julia types every integer operation by its operands (Int32 * Int32 wraps at 32 bits, Int8 - Int8 at 8, a literal is Int64), the
-// integer class computes everything in one 64-bit domain.  The two agree exactly when no value that Julia would have wrapped at a
-// narrower width is ever OBSERVED at a wider one.  Per stack slot: (`bits`, `sgn`) = Julia's type of the value, `cong` = the device
-// value is congruent to Julia's modulo 2^cong (64: identical; otherwise cong >= bits).  Ring operations (+ - * neg abs2) keep
-// congruences modulo the width of their result, order and equality (min max abs < <= == select's condition ...) need identical
-// operands, and the destination (width wd) observes the low wd bits.
-// Round 5: where an observer needs more than the slot offers, the value is re-wrapped to its Julia type right after the instruction
-// that produced it (SMR_OP_WRAP_*: sign- or zero-extension of the low bits, one or two VALU instructions) -- lazily, so
-// `Int32 a .* b .+ c` into an Int32 destination stays the three-instruction program it was, `Int32 a .* b` into an Int64 destination
-// gets one wrap at the end, and UInt8 `min(a - b, c)` one after the subtraction.  (Before: both were refused with SMR_EUNSUPPORTED,
-// ADVICE r3 / VERDICT r4 "missing #4".)  Returns false only for what cannot be typed statically: arithmetic on the result of an
-// ifelse whose branches have different types.
-static bool int_class_fit_julia(const smr_problem* p, const bool* isbool, ProgD& prog, int* nwraps) {
-    auto width = [](int dt) { return 8 << ((dt - SMR_I8) & 3); };  // I8 I16 I32 I64 U8 U16 U32 U64
-    struct Slot {
-        int bits;
-        bool sgn;
-        int cong;
-        int prod;  // the instruction that produced the value
-        bool amb;  // one of two differently typed ifelse branches: Julia's type depends on the data
-    };
-    Slot st[STACK + 4];
-    int sp = 0, wrap_after[SMR_MAXPROG] = {0}, nw = 0;
-    auto promote = [](const Slot& a, const Slot& b, int& bits, bool& sgn) {
-        if (a.bits == 1) { bits = b.bits; sgn = b.sgn; return; }
-        if (b.bits == 1) { bits = a.bits; sgn = a.sgn; return; }
-        if (a.bits != b.bits) { const Slot& w = a.bits > b.bits ? a : b; bits = w.bits; sgn = w.sgn; return; }
-        bits = a.bits; sgn = a.sgn && b.sgn;
-    };
-    auto exact = [&](Slot& s) {  // cong < 64 implies 8 <= bits <= cong < 64
-        if (s.cong == 64) return;
-        static const int code[2][3] = {{SMR_OP_WRAP_U8, SMR_OP_WRAP_U16, SMR_OP_WRAP_U32}, {SMR_OP_WRAP_I8, SMR_OP_WRAP_I16, SMR_OP_WRAP_I32}};
-        wrap_after[s.prod] = code[s.sgn ? 1 : 0][s.bits == 8 ? 0 : s.bits == 16 ? 1 : 2];
-        s.cong = 64;
-        ++nw;
-    };
-    for (int pc = 0; pc < prog.len; ++pc) {
-        const int op = prog.code[2 * pc], imm = prog.code[2 * pc + 1];
-        switch (op) {
-            case SMR_OP_ARG:
-                if (isbool[imm]) st[sp++] = {1, false, 64, pc, false};
-                else st[sp++] = {width(p->ops[imm].dtype), p->ops[imm].dtype < SMR_U8, 64, pc, false};
-                break;
-            case SMR_OP_CONST: st[sp++] = {64, true, 64, pc, false}; break;
-            case SMR_OP_CONJ: case SMR_OP_REAL: st[sp - 1].prod = pc; break;
-            case SMR_OP_IMAG: st[sp - 1] = {64, true, 64, pc, false}; break;
-            case SMR_OP_WIDEN:
-                exact(st[sp - 1]);
-                st[sp - 1] = {64, true, 64, pc, false};
-                break;
-            case SMR_OP_NEG: case SMR_OP_ABS2: {
-                Slot& a = st[sp - 1];
-                if (a.amb) return false;
-                a.prod = pc;
-                if (a.bits == 1) {  // Bool: -true is an Int, abs2(true) is true
-                    if (op == SMR_OP_NEG) { a.bits = 64; a.sgn = true; }
-                    break;
-                }
-                a.cong = std::min(a.cong, a.bits);
-                break;
-            }
-            case SMR_OP_ABS: {
-                Slot& a = st[sp - 1];
-                if (a.amb) return false;
-                exact(a);
-                a.prod = pc;
-                if (a.bits > 1 && a.sgn) a.cong = a.bits;  // abs(typemin) wraps at the operand's width
-                break;
-            }
-            case SMR_OP_ADD: case SMR_OP_SUB: case SMR_OP_MUL: {
-                Slot b = st[--sp];
-                Slot& a = st[sp - 1];
-                if (a.amb || b.amb) return false;
-                int w;
-                bool sg;
-                promote(a, b, w, sg);
-                if (a.bits == 1 && b.bits == 1) {  // Bool * Bool is a Bool, Bool (+,-) Bool an Int
-                    if (op != SMR_OP_MUL) { w = 64; sg = true; }
-                }
-                // an operand Julia converts to a wider type first must be identical, not merely congruent at its own width
-                if (a.cong < w) exact(a);
-                if (b.cong < w) { exact(b); }
-                a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
-                break;
-            }
-            // math opcodes (strided_hip.h 65, 96.., 128..): x ^ n (n >= 0), ~ and & | xor are ring operations; floor ceil trunc round
-            // are identities; sign, rem and mod need exact operands (rem / mod by an Int64 literal: the result is an Int64)
-            case SMR_OP_POWI: case SMR_OP_NOT: {
-                Slot& a = st[sp - 1];
-                if (a.amb) return false;
-                a.prod = pc;
-                if (a.bits == 1) {  // Bool ^ n is a Bool (0 or 1 either way; true ^ 0 = true); ~true would be -2: the front ends send XOR
-                    if (op == SMR_OP_NOT) return false;
-                    break;
-                }
-                a.cong = std::min(a.cong, a.bits);
-                break;
-            }
-            case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: st[sp - 1].prod = pc; break;
-            case SMR_OP_SIGN: {
-                Slot& a = st[sp - 1];
-                exact(a);
-                a.prod = pc;
-                break;
-            }
-            case SMR_OP_REM: case SMR_OP_MOD: {
-                Slot b = st[--sp];
-                Slot& a = st[sp - 1];
-                if (a.amb || b.amb) return false;
-                exact(a);
-                exact(b);
-                a = {64, true, 64, pc, false};
-                break;
-            }
-            case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: {
-                Slot b = st[--sp];
-                Slot& a = st[sp - 1];
-                if (a.amb || b.amb) return false;
-                int w;
-                bool sg;
-                promote(a, b, w, sg);  // Bool & Bool is a Bool
-                if (a.cong < w) exact(a);
-                if (b.cong < w) exact(b);
-                a = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
-                break;
-            }
-            case SMR_OP_FMA: {  // a*b + c, typed as that expression; the product cannot be re-wrapped on its own
-                Slot c = st[--sp], b = st[--sp];
-                Slot& a = st[sp - 1];
-                if (a.amb || b.amb || c.amb) return false;
-                int w, w2;
-                bool sg, sg2;
-                promote(a, b, w, sg);
-                if (a.cong < w) exact(a);
-                if (b.cong < w) exact(b);
-                Slot m = {w, sg, w == 1 ? 64 : std::min({a.cong, b.cong, w}), pc, false};
-                promote(m, c, w2, sg2);
-                if (m.bits == 1 && c.bits == 1) { w2 = 64; sg2 = true; }
-                if (m.cong < w2) return false;
-                if (c.cong < w2) exact(c);
-                a = {w2, sg2, w2 == 1 ? 64 : std::min({m.cong, c.cong, w2}), pc, false};
-                break;
-            }
-            case SMR_OP_MIN: case SMR_OP_MAX: {
-                Slot b = st[--sp];
-                Slot& a = st[sp - 1];
-                exact(a);
-                exact(b);
-                int w;
-                bool sg;
-                promote(a, b, w, sg);
-                // min(::Int8, ::UInt32) promotes to UInt32 and throws for a negative value in Julia; the oracle keeps the mathematical
-                // value.  Either way it is not a value of the promoted type: never re-wrapped, no arithmetic on it.
-                a = {w, sg, 64, pc, a.amb || b.amb || (!sg && ((a.sgn && a.bits > 1) || (b.sgn && b.bits > 1)))};
-                break;
-            }
-            case SMR_OP_LT: case SMR_OP_LE: case SMR_OP_GT: case SMR_OP_GE: case SMR_OP_EQ: case SMR_OP_NE: {
-                Slot b = st[--sp];
-                Slot& a = st[sp - 1];
-                exact(a);
-                exact(b);
-                a = {1, false, 64, pc, false};  // Bool
-                break;
-            }
-            case SMR_OP_SELECT: {
-                Slot c = st[--sp], b = st[--sp];
-                Slot& a = st[sp - 1];
-                exact(a);
-                const bool same = b.bits == c.bits && b.sgn == c.sgn && !b.amb && !c.amb;  // (a data-dependent type is never re-wrapped: it stays identical)
-                if (!same) { exact(b); exact(c); }
-                int w;
-                bool sg;
-                promote(b, c, w, sg);
-                a = {w, sg, std::min(b.cong, c.cong), pc, !same || b.amb || c.amb};
-                break;
-            }
-            default: return false;
-        }
-    }
-    const int wd = width(p->ops[0].dtype);
-    const bool ring = p->redop == SMR_RED_NONE || p->redop == SMR_RED_ADD || p->redop == SMR_RED_MUL;
-    if (!(ring ? st[0].cong >= wd : st[0].cong == 64)) exact(st[0]);
-    if (nwraps) *nwraps = nw;
-    if (nw == 0) return true;
-    if (prog.len + nw > SMR_MAXPROG) return false;
-    uint8_t code[2 * SMR_MAXPROG];
-    int n = 0;
-    for (int pc = 0; pc < prog.len; ++pc) {
-        code[2 * n] = prog.code[2 * pc];
-        code[2 * n + 1] = prog.code[2 * pc + 1];
-        ++n;
-        if (wrap_after[pc]) {
-            code[2 * n] = (uint8_t)wrap_after[pc];
-            code[2 * n + 1] = 0;
-            ++n;
-        }
-    }
-    std::memcpy(prog.code, code, sizeof(uint8_t) * 2 * (size_t)n);
-    prog.len = n;
+// is every operand k >= k0 (0: the destination too, 1: the inputs) unit-stride or broadcast along dim d?
+static bool unit_or_bcast(const Canon& c, int d, int k0) {
+    for (int k = k0; k < c.M; ++k)
+        if (c.strides[k][d] != 1 && c.strides[k][d] != 0) return false;
     return true;
 }
 
-static void recognise(Canon& c) {
-    const ProgD& p = c.prog;
-    auto op = [&](int i) { return (int)p.code[2 * i]; };
-    auto im = [&](int i) { return (int)p.code[2 * i + 1]; };
-    auto isarg = [&](int i, int k) { return op(i) == SMR_OP_ARG && im(i) == k; };
-    auto isconst = [&](int i) { return op(i) == SMR_OP_CONST; };
-    auto cre = [&](int i) { return p.consts[2 * im(i)]; };
-    auto cim = [&](int i) { return p.consts[2 * im(i) + 1]; };
-    c.fkind = FK_PROG;
-    const int n = p.len, nin = c.M - 1;
-    if (n == 1 && isarg(0, 1) && nin == 1) { c.fkind = FK_IDENT; return; }
-    if (n == 3 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && nin == 2) { c.fkind = FK_ADD2; return; }
-    if (n == 5 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isarg(3, 3) && op(4) == SMR_OP_ADD && nin == 3) {
-        c.fkind = FK_ADD3; return;
-    }
-    if (n == 7 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isarg(3, 3) && op(4) == SMR_OP_ADD &&
-        isarg(5, 4) && op(6) == SMR_OP_ADD && nin == 4) {
-        c.fkind = FK_ADD4; return;
-    }
-    if (n == 3 && nin == 1 && op(2) == SMR_OP_MUL &&
-        ((isarg(0, 1) && isconst(1)) || (isconst(0) && isarg(1, 1)))) {
-        int ci = isconst(0) ? 0 : 1;
-        c.fkind = FK_SCALE; c.fc[0] = cre(ci); c.fc[1] = cim(ci); return;
-    }
-    if (n == 5 && nin == 2 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_ADD && isconst(3) && op(4) == SMR_OP_DIV) {
-        c.fkind = FK_SYM; c.fc[0] = cre(3); c.fc[1] = cim(3); return;
-    }
-    if (n == 5 && nin == 2 && isconst(0) && isarg(1, 1) && op(2) == SMR_OP_MUL && isarg(3, 2) && op(4) == SMR_OP_ADD) {
-        c.fkind = FK_AXPY; c.fc[0] = cre(0); c.fc[1] = cim(0); return;
-    }
-    if (n == 7 && nin == 2 && isconst(0) && isarg(1, 1) && op(2) == SMR_OP_MUL && isconst(3) && isarg(4, 2) &&
-        op(5) == SMR_OP_MUL && op(6) == SMR_OP_ADD) {
-        c.fkind = FK_AXPBY; c.fc[0] = cre(0); c.fc[1] = cim(0); c.fc[2] = cre(3); c.fc[3] = cim(3); return;
-    }
-    if (n == 2 && nin == 1 && isarg(0, 1) && op(1) == SMR_OP_ABS2) { c.fkind = FK_ABS2; return; }
-    if (n == 3 && nin == 2 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_MUL) { c.fkind = FK_MUL2; return; }
-    // a .* exp.(c .* a) .+ sin.(a .* a)   (real types)
-    if (n == 11 && nin == 1 && (c.ct == SMR_F32 || c.ct == SMR_F64) && isarg(0, 1) && isconst(1) && isarg(2, 1) &&
-        op(3) == SMR_OP_MUL && op(4) == SMR_OP_EXP && op(5) == SMR_OP_MUL && isarg(6, 1) && isarg(7, 1) &&
-        op(8) == SMR_OP_MUL && op(9) == SMR_OP_SIN && op(10) == SMR_OP_ADD && cim(1) == 0.0) {
-        c.fkind = FK_EXPR5; c.fc[0] = cre(1); return;
-    }
-}
-
-// ---- canonicalisation ---------------------------------------------------------------------------
-int canonicalise(const smr_problem* p0, Canon& c) {
-    if (!p0) return set_error(SMR_EINVAL, "null problem");
-    // Bool operands are UInt8 operands for every kernel; only the typing of an integer f-program tells them apart
-    smr_problem pcopy = *p0;
-    bool isbool[MAXM] = {false};
-    if (pcopy.M >= 1 && pcopy.M <= MAXM)
-        for (int k = 0; k < pcopy.M; ++k)
-            if (pcopy.ops[k].dtype == SMR_BOOL) {
-                isbool[k] = true;
-                pcopy.ops[k].dtype = SMR_U8;
-            }
-    const smr_problem* p = &pcopy;
-    const int N0 = p->N, M0 = p->M;
-    if (N0 < 1 || N0 > MAXN) return set_error(SMR_EINVAL, "rank N out of range 1..8");
-    if (M0 < 1 || M0 > MAXM) return set_error(SMR_EINVAL, "operand count M out of range 1..8");
-    for (int i = 0; i < N0; ++i)
-        if (p->dims[i] < 1) return set_error(SMR_EINVAL, "every dim must be >= 1 (zero-size is handled by the caller, src/mapreduce.jl:48,88)");
-    for (int k = 0; k < M0; ++k) {
-        if (!p->ops[k].base) return set_error(SMR_EINVAL, "null operand base pointer");
-        if (dtype_size(p->ops[k].dtype) == 0) return set_error(SMR_EINVAL, "bad operand dtype");
-    }
-    if (p->redop < SMR_RED_NONE || p->redop > SMR_RED_OR) return set_error(SMR_EINVAL, "bad redop");
-    if (p->initop < SMR_INIT_NONE || p->initop > SMR_INIT_CONJ) return set_error(SMR_EINVAL, "bad initop");
-    if (p->redop == SMR_RED_NONE && p->initop != SMR_INIT_NONE)
-        return set_error(SMR_EINVAL, "initop requires a reduction op (src/mapreduce.jl:310-316)");
-
-    // program
-    ProgD& prog = c.prog;
-    std::memset(&prog, 0, sizeof(prog));
-    if (!p->fprog || p->fprog_len == 0) {
-        if (M0 < 2) return set_error(SMR_EINVAL, "identity program needs an input");
-        prog.len = 1;
-        prog.code[0] = SMR_OP_ARG;
-        prog.code[1] = 1;
-    } else {
-        if (p->fprog_len < 0 || p->fprog_len > SMR_MAXPROG) return set_error(SMR_EINVAL, "f-program too long");
-        prog.len = p->fprog_len;
-        std::memcpy(prog.code, p->fprog, (size_t)(2 * p->fprog_len));
-    }
-    if (p->nconsts < 0 || p->nconsts > SMR_MAXCONST) return set_error(SMR_EINVAL, "too many constants");
-    if (p->nconsts > 0 && !p->fconsts) return set_error(SMR_EINVAL, "null fconsts");
-    prog.nconst = p->nconsts;
-    for (int i = 0; i < 2 * p->nconsts; ++i) prog.consts[i] = p->fconsts[i];
-    int depth = 0;
-    if (check_prog(prog, std::max(M0, 1), depth) != 0) return set_error(SMR_EINVAL, "malformed f-program");
-    if (depth > STACK) return set_error(SMR_EUNSUPPORTED, "f-program needs more than 8 stack slots");
-    if (!options().jit && prog_uses_math(prog))
-        return set_error(SMR_EUNSUPPORTED, "f-program with a math opcode (pow, fma, tan, rem, &, ...) with option \"jit\" = 0: the interpreter does not run them");
-
-    // compute class (Julia promote_type over the operand eltypes, restricted to the four
-    // float classes of the reference tests)
-    bool dbl = false, cplx = false, anyint = false;
-    for (int k = 0; k < M0; ++k) {
-        int dt = p->ops[k].dtype;
-        if (dt == SMR_F64 || dt == SMR_C64) dbl = true;
-        if (dt == SMR_C32 || dt == SMR_C64) cplx = true;
-        if (dt >= SMR_I8) { anyint = true; dbl = true; }
-    }
-    for (int i = 0; i < prog.nconst; ++i)
-        if (prog.consts[2 * i + 1] != 0.0) cplx = true;
-    for (int pc = 0; pc < prog.len; ++pc)
-        if (prog.code[2 * pc] == SMR_OP_WIDEN) dbl = true;  // a 64-bit scalar takes part (strided_hip.h)
-    c.ct = cplx ? (dbl ? SMR_C64 : SMR_C32) : (dbl ? SMR_F64 : SMR_F32);
-    // The integer class (round 3): every operand has an integer eltype and f stays inside the integers -> wrapping
-    // 64-bit arithmetic like Julia's (typeof(op(...)) is the accumulator type, src/mapreduce.jl:55-72); narrower
-    // destinations truncate on store.  UInt64 takes part in ring operations only (no order on the device).
-    {
-        bool allint = true, has_u64 = false, has_signed = false, has_const = false, eqne = false;
-        for (int k = 0; k < M0; ++k) {
-            if (p->ops[k].dtype < SMR_I8) allint = false;
-            if (p->ops[k].dtype == SMR_U64) has_u64 = true;
-            if (p->ops[k].dtype >= SMR_I8 && p->ops[k].dtype <= SMR_I64) has_signed = true;
-        }
-        bool closed = true, ordered = p->redop == SMR_RED_MIN || p->redop == SMR_RED_MAX, negpow = false, baddiv = false;
-        for (int pc = 0; pc < prog.len && closed; ++pc) {
-            const int op = prog.code[2 * pc];
-            switch (op) {
-                case SMR_OP_ARG: case SMR_OP_NEG: case SMR_OP_ABS2: case SMR_OP_CONJ: case SMR_OP_REAL: case SMR_OP_IMAG:
-                case SMR_OP_ADD: case SMR_OP_SUB: case SMR_OP_MUL: case SMR_OP_SELECT: case SMR_OP_WIDEN: break;
-                case SMR_OP_ABS: case SMR_OP_MIN: case SMR_OP_MAX: case SMR_OP_LT: case SMR_OP_LE: case SMR_OP_GT: case SMR_OP_GE:
-                    ordered = true;
-                    break;
-                // == and !=: equality of bit patterns IS Julia's equality as long as nothing signed can meet a UInt64 -- Julia
-                // compares a UInt64 with a signed value mathematically (-1 != 0xffff...ff), a 64-bit domain compares the patterns.
-                // Signed values come from signed operands and from constants (integer literals are Int64: UInt8 - 10 is an Int64).
-                case SMR_OP_EQ: case SMR_OP_NE:
-                    eqne = true;
-                    break;
-                // math opcodes that stay in the integers (the rest -- pow, the transcendentals -- compute in Float64 like sqrt)
-                case SMR_OP_NOT: case SMR_OP_AND: case SMR_OP_OR: case SMR_OP_XOR: case SMR_OP_FMA:
-                case SMR_OP_FLOOR: case SMR_OP_CEIL: case SMR_OP_TRUNC: case SMR_OP_ROUND: break;
-                case SMR_OP_POWI:
-                    if ((int8_t)prog.code[2 * pc + 1] < 0) negpow = true;
-                    break;
-                case SMR_OP_SIGN: ordered = true; break;
-                case SMR_OP_REM: case SMR_OP_MOD: {
-                    ordered = true;
-                    const bool cdiv = pc > 0 && prog.code[2 * (pc - 1)] == SMR_OP_CONST;
-                    if (!cdiv || prog.consts[2 * prog.code[2 * pc - 1]] == 0.0) baddiv = true;
-                    break;
-                }
-                case SMR_OP_CONST: {
-                    has_const = true;
-                    const double re = prog.consts[2 * prog.code[2 * pc + 1]], im = prog.consts[2 * prog.code[2 * pc + 1] + 1];
-                    // integer-valued (or a +-Inf seed of a min / max reduction, which saturates to typemax / typemin)
-                    if (im != 0.0 || !(re == std::floor(re) || std::isinf(re)) || (std::fabs(re) > 9223372036854775808.0 && !std::isinf(re))) closed = false;
-                    break;
-                }
-                default: closed = false;
-            }
-        }
-        if (p->initop == SMR_INIT_SCALE || p->initop == SMR_INIT_CONST) {
-            const double re = p->initarg[0], im = p->initarg[1];
-            if (im != 0.0 || re != std::floor(re) || std::fabs(re) > 9223372036854775808.0) closed = false;
-        }
-        if (eqne && has_u64 && (has_signed || has_const)) ordered = true;  // (round 5: all-unsigned equality tests are exact and stay on the device)
-        if (allint && negpow)
-            return set_error(SMR_EUNSUPPORTED, "integer x ^ n with a negative literal n (Julia throws DomainError)");
-        if (allint && baddiv)
-            return set_error(SMR_EUNSUPPORTED, "integer rem / mod with a divisor that is not a non-zero constant (Julia throws DivideError on a zero divisor)");
-        if (allint && closed && !(has_u64 && ordered)) {
-            if (!int_class_fit_julia(p, isbool, prog, &c.int_wraps))
-                return set_error(SMR_EUNSUPPORTED,
-                                 "integer f-program that cannot be typed statically (arithmetic on an ifelse whose branches have different integer "
-                                 "types), or too long once narrow intermediate results are re-wrapped to their Julia types");
-            c.ct = SMR_I64;
-        }
-    }
-    c.redop = p->redop;
-    c.initop = p->initop;
-    c.initarg[0] = p->initarg[0];
-    c.initarg[1] = p->initarg[1];
-    c.bitcopy = false;
-    if (anyint && c.ct == SMR_I64 && p->redop == SMR_RED_NONE && M0 == 2 && p->ops[0].dtype == p->ops[1].dtype && prog.len == 1 &&
-        prog.code[0] == SMR_OP_ARG) {
-        c.bitcopy = true;  // a pure move stays a bit copy of opaque elements (any width, vectorised)
-        c.ct = SMR_F64;
-    }
-    if (anyint && c.ct != SMR_I64 && !c.bitcopy) {
-        bool pure = p->redop == SMR_RED_NONE && M0 == 2 && p->ops[0].dtype == p->ops[1].dtype && prog.len == 1 &&
-                    prog.code[0] == SMR_OP_ARG;
-        if (pure) c.bitcopy = true;
-        // Integer data that is not merely moved is computed in Float64 (the four float classes are the device
-        // scope): exact for every value of an 8/16/32-bit type and for sums / counts below
-        // 2^53, which is what the reference's integer tests need (counting reductions, test/othertests.jl:116,123).
-        // 64-bit integer INPUTS can hold values a double cannot: refuse them instead of rounding silently -- the
-        // reference-side binding falls back to the CPU method (Julia's wrapping Int64 arithmetic).
-        if (!pure)
-            for (int k = 1; k < M0; ++k)
-                if (p->ops[k].dtype == SMR_I64 || p->ops[k].dtype == SMR_U64)
-                    return set_error(SMR_EUNSUPPORTED,
-                                     "64-bit integer inputs outside the integer class (all operands integer, f built from + - * neg abs abs2 min max "
-                                     "comparisons select and integer constants): the arithmetic would run in Float64, which is exact only below 2^53");
-    }
-
-    // working copies
-    int N = 0;
-    i64 dims[MAXN];
-    i64 str[MAXM][MAXN];
-    int M = M0;
-    for (int i = 0; i < N0; ++i) {
-        if (p->dims[i] == 1) continue;  // size-1 dims carry no information
-        dims[N] = p->dims[i];
-        for (int k = 0; k < M0; ++k) str[k][N] = p->ops[k].strides[i];
-        ++N;
-    }
-    i64 off[MAXM];
-    void* base[MAXM];
-    int dtype[MAXM], conj[MAXM];
-    for (int k = 0; k < M0; ++k) {
-        off[k] = p->ops[k].offset;
-        base[k] = p->ops[k].base;
-        dtype[k] = p->ops[k].dtype;
-        conj[k] = (p->ops[k].conj && (dtype[k] == SMR_C32 || dtype[k] == SMR_C64)) ? 1 : 0;
-    }
-
-    // dedupe identical inputs (capturestridedargs does not: src/broadcast.jl:41-46), and
-    // drop inputs the program never reads
-    {
-        int remap[MAXM];
-        bool used[MAXM] = {false};
-        for (int pc = 0; pc < prog.len; ++pc)
-            if (prog.code[2 * pc] == SMR_OP_ARG) used[prog.code[2 * pc + 1]] = true;
-        int newM = 1;
-        int keep[MAXM];
-        keep[0] = 0;
-        for (int k = 1; k < M; ++k) {
-            remap[k] = -1;
-            if (!used[k]) continue;
-            for (int j = 1; j < newM; ++j) {
-                int q = keep[j];
-                bool same = base[q] == base[k] && off[q] == off[k] && dtype[q] == dtype[k] && conj[q] == conj[k];
-                for (int i = 0; i < N && same; ++i) same = str[q][i] == str[k][i];
-                if (same) { remap[k] = j; break; }
-            }
-            if (remap[k] < 0) { keep[newM] = k; remap[k] = newM; ++newM; }
-        }
-        for (int pc = 0; pc < prog.len; ++pc)
-            if (prog.code[2 * pc] == SMR_OP_ARG) prog.code[2 * pc + 1] = (uint8_t)remap[prog.code[2 * pc + 1]];
-        i64 s2[MAXM][MAXN], o2[MAXM];
-        void* b2[MAXM];
-        int d2[MAXM], c2[MAXM];
-        for (int j = 0; j < newM; ++j) {
-            int q = keep[j];
-            for (int i = 0; i < N; ++i) s2[j][i] = str[q][i];
-            o2[j] = off[q]; b2[j] = base[q]; d2[j] = dtype[q]; c2[j] = conj[q];
-            c.orig[j] = q;
-        }
-        M = newM;
-        for (int j = 0; j < M; ++j) {
-            for (int i = 0; i < N; ++i) str[j][i] = s2[j][i];
-            off[j] = o2[j]; base[j] = b2[j]; dtype[j] = d2[j]; conj[j] = c2[j];
-        }
-    }
-
-    // a pure map must not alias destination elements (the reference would serialise the
-    // writes; on a GPU that is a race)
-    if (p->redop == SMR_RED_NONE)
-        for (int i = 0; i < N; ++i)
-            if (str[0][i] == 0) return set_error(SMR_EUNSUPPORTED, "map into a destination with a zero stride");
-
-    // flip dims so that destination strides (kept dims) / first-input strides (reduced dims)
-    // are positive; iteration direction is irrelevant for map and for associative reductions
-    for (int i = 0; i < N; ++i) {
-        i64 lead = str[0][i];
-        if (lead == 0)
-            for (int k = 1; k < M && lead == 0; ++k) lead = str[k][i];
-        if (lead < 0)
-            for (int k = 0; k < M; ++k) {
-                off[k] += (dims[i] - 1) * str[k][i];
-                str[k][i] = -str[k][i];
-            }
-    }
-
-    // sort: kept dims by destination stride, then reduced dims by smallest input stride
-    std::vector<int> perm(N);
-    for (int i = 0; i < N; ++i) perm[i] = i;
-    auto minin = [&](int i) {
-        i64 m = INT64_MAX;
-        for (int k = 1; k < M; ++k)
-            if (str[k][i] != 0) m = std::min<i64>(m, std::llabs(str[k][i]));
-        return m;
-    };
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
-        bool ra = str[0][a] == 0, rb = str[0][b] == 0;
-        if (ra != rb) return !ra;
-        if (!ra) return str[0][a] < str[0][b];
-        return minin(a) < minin(b);
-    });
-    i64 sd[MAXN], ss[MAXM][MAXN];
-    for (int i = 0; i < N; ++i) {
-        sd[i] = dims[perm[i]];
-        for (int k = 0; k < M; ++k) ss[k][i] = str[k][perm[i]];
-    }
-    // fuse adjacent dims that are jointly contiguous in every operand (same rule as
-    // src/mapreduce.jl:103-115, applied after sorting so it fires more often); never across
-    // the kept/reduced boundary
-    int NF = 0;
-    i64 fd[MAXN], fs[MAXM][MAXN];
-    for (int i = 0; i < N; ++i) {
-        bool merged = false;
-        if (NF > 0) {
-            bool kb = fs[0][NF - 1] != 0, ka = ss[0][i] != 0;
-            bool ok = (kb == ka);
-            for (int k = 0; k < M && ok; ++k) ok = ss[k][i] == fd[NF - 1] * fs[k][NF - 1];
-            if (ok) {
-                fd[NF - 1] *= sd[i];
-                merged = true;
-            }
-        }
-        if (!merged) {
-            fd[NF] = sd[i];
-            for (int k = 0; k < M; ++k) fs[k][NF] = ss[k][i];
-            ++NF;
-        }
-    }
-    if (NF == 0) {  // every dim had size 1: a single element
-        NF = 1;
-        fd[0] = 1;
-        for (int k = 0; k < M; ++k) fs[k][0] = (k == 0 && p->redop == SMR_RED_NONE) ? 1 : 0;
-        if (p->redop != SMR_RED_NONE) fs[0][0] = 0;
-    }
-    c.N = NF;
-    c.M = M;
-    c.NK = 0;
-    c.total = 1;
-    c.nout = 1;
-    for (int i = 0; i < NF; ++i) {
-        c.dims[i] = fd[i];
-        c.total *= fd[i];
-        if (fs[0][i] != 0) { c.NK = i + 1; c.nout *= fd[i]; }
-    }
-    if (p->redop == SMR_RED_NONE) { c.NK = NF; }
-    c.mixed = false;
-    for (int k = 0; k < M; ++k) {
-        for (int i = 0; i < NF; ++i) c.strides[k][i] = fs[k][i];
-        for (int i = NF; i < MAXN; ++i) c.strides[k][i] = 0;
-        c.offsets[k] = off[k];
-        c.base[k] = base[k];
-        c.dtype[k] = dtype[k];
-        c.conj[k] = conj[k];
-        c.esize[k] = dtype_size(dtype[k]);
-        if (dtype[k] != c.ct) c.mixed = true;
-    }
-    for (int i = NF; i < MAXN; ++i) c.dims[i] = 1;
-    if (c.bitcopy) c.mixed = false;
-
-    // algorithmic bytes: every distinct buffer once
-    {
-        std::map<void*, i64> foot;
-        for (int k = 0; k < M; ++k) {
-            i64 n = 1;
-            for (int i = 0; i < NF; ++i)
-                if (c.strides[k][i] != 0) n *= c.dims[i];
-            i64 bytes = n * c.esize[k];
-            auto it = foot.find(c.base[k]);
-            if (it == foot.end()) foot[c.base[k]] = bytes;
-            else it->second = std::max(it->second, bytes);
-        }
-        c.algbytes = 0;
-        for (auto& kv : foot) c.algbytes += kv.second;
-    }
-    recognise(c);
-    return SMR_OK;
+// ... every input, and at least one of them unit-stride: vector loads can run along dim d
+static bool inputs_run_along(const Canon& c, int d) {
+    bool any = false;
+    for (int k = 1; k < c.M; ++k) any = any || c.strides[k][d] == 1;
+    return any && unit_or_bcast(c, d, 1);
 }
 
 // ---- tile planning (FAM_TILED) -------------------------------------------------------------------
@@ -801,7 +216,7 @@ static void plan_tile_order(const Canon& c, TilePlan& t, const int* lg) {
 static void plan_block_order(const Canon& c, TilePlan& t, const int* lg, int blk, bool xcd_runs) {
     if (blk == 0 || blk == 1 || t.grid < 64 || t.grid > ((i64)1 << 22)) return;
     i64 nb[MAXN], blocks = 1, tmul[MAXN], acc = 1, bd[MAXN];
-    const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+    const int es = elem_bytes(c);
     for (int d = 0; d < c.N; ++d) bd[d] = blk > 0 ? blk : 1;
     if (blk < 0) {
         i64 prod = 1;
@@ -947,8 +362,7 @@ static bool plan_orbit(const Canon& c, OrbitPlan& o) {
     for (int d = 0; d < c.N; ++d)
         if (!unit[d]) others *= c.dims[d];
     const int vmax = std::max(1, 16 / es);
-    int vlog = 0;
-    while ((1 << vlog) < vmax) ++vlog;
+    const int vlog = ceil_log2(vmax);
     // 16-byte accesses need aligned operands and vector-multiple strides; element-wise tiles stay <= 1024 elements
     bool vec_ok = vmax > 1;
     for (int d = 1; d < c.N; ++d)
@@ -1278,7 +692,7 @@ static int near_axis(const Canon& c, int k) {
 static bool plan_tiles(const Canon& c, TilePlan& t) {
     if (c.redop != SMR_RED_NONE) return false;
     if (c.N < 2 || c.strides[0][0] != 1) return false;
-    const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+    const int es = elem_bytes(c);
     // which inputs need staging: unit-stride axis exists and differs from the destination's
     bool axis_used[MAXN] = {false};
     axis_used[0] = true;
@@ -1335,7 +749,7 @@ static bool plan_tiles(const Canon& c, TilePlan& t) {
     else if (o.tile_log2 == 0 && na >= 3 && (size_t)nst * 4096 * es <= (size_t)128 * 1024 && c.total >= (i64)4096 * 256) {
         bool fits = true;  // every axis must be able to reach its share of the 12 bits
         int bits = 0;
-        for (int a = 0; a < na; ++a) bits += std::min(nextpow2_log(c.dims[axes[a]]), 12);
+        for (int a = 0; a < na; ++a) bits += std::min(ceil_log2(c.dims[axes[a]]), 12);
         if (bits < 12) fits = false;
         // one round of big tiles (<= 256 CUs, 1024 lanes each) or a long persistent work list: big;
         // in between (measured 48^4: 25.8 vs 32.0 us, 64^4: 73.5 vs 83.3 us) several small workgroups per
@@ -1360,7 +774,7 @@ static bool plan_tiles(const Canon& c, TilePlan& t) {
     int lg[MAXN] = {0};
     int total = 0;
     // grow the axes round-robin towards the run target
-    int want = std::max(1, nextpow2_log(std::max<i64>(1, runbytes / es)));
+    int want = std::max(1, ceil_log2(std::max<i64>(1, runbytes / es)));
     bool forced = false;
     for (int i = 0; i < c.N; ++i)
         if (o.tile_lg[i] >= 0) forced = true;
@@ -1376,7 +790,7 @@ static bool plan_tiles(const Canon& c, TilePlan& t) {
         // big tiles: give the destination axis a full 128-B line first (stores and the direct
         // inputs then move whole lines; measured on the 4-way sum at 32^4: 16x8x8x4 7.7 us,
         // 16x8x4x8 7.6 us, 8x8x8x8 8.0 us), the other axes share the rest
-        const int want0 = big_transpose ? 7 : std::max(1, nextpow2_log(std::max<i64>(1, 128 / es)));
+        const int want0 = big_transpose ? 7 : std::max(1, ceil_log2(std::max<i64>(1, 128 / es)));
         while (lg[0] < want0 && ((i64)1 << lg[0]) < c.dims[0] && total < tl_cap) {
             ++lg[0];
             ++total;
@@ -1627,7 +1041,7 @@ static bool plan_flat_side(const Canon& c, FlatPlan& f, int side, int es) {
 static bool plan_flat(const Canon& c, FlatPlan& f) {
     const Options& o = options();
     if (!o.flat || c.redop != SMR_RED_NONE || c.M < 2 || c.mixed || c.N < 2) return false;
-    const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+    const int es = elem_bytes(c);
     if (es < 4) return false;
     f.kt = flat_transposed_input(c);
     if (f.kt < 0) return false;
@@ -1646,7 +1060,7 @@ static bool plan_flatb(const Canon& c, FlatBPlan& f) {
     const Options& o = options();
     f.on = false;
     if (!o.flatb || !o.flat || c.redop != SMR_RED_NONE || c.M != 2 || c.mixed || c.N < 3) return false;
-    const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+    const int es = elem_bytes(c);
     if (es < 4 || c.total < 65536) return false;
     if (c.strides[0][0] != 1) return false;
     // the longest dense destination prefix that stays within the size limits
@@ -1710,7 +1124,7 @@ static bool plan_flat2(const Canon& c, Flat2Plan& f) {
     const Options& o = options();
     f.on = false;
     if (!o.flat2 || !o.flat || c.redop != SMR_RED_NONE || c.M < 2 || c.mixed || c.N < 2) return false;
-    const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+    const int es = elem_bytes(c);
     if (es < 4 || c.total < 65536) return false;
     f.kt = flat_transposed_input(c);
     if (f.kt < 0) return false;
@@ -1847,7 +1261,249 @@ static bool plan_flat2(const Canon& c, Flat2Plan& f) {
     return true;
 }
 
+// ---- STREAM -----------------------------------------------------------------------------------------
+// Admission: every operand is unit-stride or broadcast along dim 0 -- and, unless the family is forced, rows long enough to
+// keep a workgroup busy.
+static bool stream_fits(const Canon& c, bool forced) {
+    if (!unit_or_bcast(c, 0, 0)) return false;
+    if (forced || c.N < 2) return true;
+    // short rows pack (256 >> txlog) entries of dim 1 into a workgroup; when dim 1 is short too (a permutation
+    // of a 4x4x4x... tensor) most lanes idle -- 8 of 256 for rows of 4 Float64 x 4 -- and the per-element
+    // decode of the GENERIC family wins (measured 4^8 Float64: 9.9 us -> tools/perf_sanity.py)
+    const i64 vmax = std::max<i64>(1, 16 / elem_bytes(c));
+    const i64 n0v = (c.dims[0] % vmax == 0) ? c.dims[0] / vmax : c.dims[0];
+    if (n0v > 128) return true;
+    const i64 used = n0v * std::min<i64>(c.dims[1], (i64)256 >> ceil_log2(n0v));
+    return used * 4 >= 256;
+}
+
+static void plan_stream(const Canon& c, StreamPlan& sp) {
+    const int es = elem_bytes(c);
+    const int vmax = (c.mixed || es >= 16) ? 1 : 16 / es;
+    const bool unit = unit_or_bcast(c, 0, 0);  // (false: the strided form, element accesses)
+    // vector width: 16 B per lane when every unit-stride operand stays 16-B aligned
+    int v = unit ? vmax : 1;
+    while (v > 1) {
+        bool ok = c.dims[0] % v == 0;
+        for (int k = 0; k < c.M && ok; ++k) {
+            if (c.strides[k][0] == 0) continue;
+            if (((uintptr_t)c.base[k] + (uintptr_t)(c.offsets[k] * c.esize[k])) % (size_t)(v * es)) ok = false;
+            for (int i = 1; i < c.N && ok; ++i)
+                if (c.strides[k][i] % v) ok = false;
+        }
+        if (ok) break;
+        v >>= 1;
+    }
+    sp.vec = v;
+    sp.vec_ua = false;
+    // Round 5: rows that are not whole aligned vectors (odd lengths, odd row strides, views starting inside a vector) still move
+    // as 16-byte vectors -- at element alignment, plus one partial vector per row (smr_k_stream.hip: UVec) -- when the elements
+    // are 4 or 8 bytes and a row holds at least four vectors.
+    // (short rows with a long tail lose: rows of 63 Float32 = 15 vectors + 3 single elements 24.9 -> 27.1 us; rows of 17
+    // Float64 = 8 vectors + 1 element gain 9 %: a tail of one element, or at least 32 vectors per row.  tools/stream_ua_ab.py,
+    // profiles/r05_stream_ua_ab.txt: (257,129,65) (0,2,1) 12.3 -> 9.5 us, (999,1001) axpy 4.7 -> 3.1 us, (1001,999,5) f32 10.9 -> 8.0)
+    if (options().stream_ua && v < vmax && unit && es >= 4 && c.dims[0] >= 4 * vmax && (c.dims[0] % vmax <= 1 || c.dims[0] >= 32 * vmax)) {
+        sp.vec = vmax;
+        sp.vec_ua = true;
+    }
+}
+
+// ---- reductions -------------------------------------------------------------------------------------
+static void plan_reduce_all(const Canon& c, ReducePlan& rp) {
+    const i64 per_block = 256 * 16;
+    i64 nb = (c.total + per_block - 1) / per_block;
+    nb = std::max<i64>(1, std::min<i64>(nb, std::max<i64>(1, options().reduce_blocks)));
+    rp.nparts = (int)nb;
+    if (nb > 1) rp.scratch_bytes = (size_t)nb * dtype_size(c.ct);
+}
+
+// What the three forms of REDUCE_PART plan from.  The reduced space is the inner reduced dim NK (extent L0) x the outer index
+// q in [0, Q): red = L0 * Q elements per output; es bytes per element of the compute class, vmax elements per 16-byte vector.
+struct PartShape {
+    i64 red, L0, Q;
+    int es, vmax;
+};
+
+// COL: a workgroup = TX lanes along kept dim 0 (vmax elements each) x TY rows of the
+// reduced space; LDS tree over the rows
+static void plan_part_col(const Canon& c, const PartShape& s, ReducePlan& rp) {
+    const Options& o = options();
+    const i64 red = s.red, L0 = s.L0, K0 = c.dims[0];
+    const int vmax = s.vmax, es = s.es;
+    rp.kind = 2;
+    int txlog = std::min(8, ceil_log2((K0 + vmax - 1) / vmax));
+    // rows of the reduced space per workgroup: fewer when the reduction is short (sum over a trailing dim of 7:
+    // every lane then walks its 7 rows itself instead of 8 lanes sharing them through LDS)
+    txlog = std::min<int>(txlog, std::max<int>((int)o.reduce_col_txlog, 8 - ceil_log2(std::max<i64>(1, red / 8))));
+    // too few workgroups along the kept dims: narrower row segments (down to 128 bytes) give 2-4x as many and more
+    // rows to each -- when that makes the split unnecessary it saves the partials and the second launch
+    // (sum(A; dims=2) of 512x384x64 f32: 16.0 -> 12.4 us, 256^3: 18.4 -> 14.7 us, tools/reduce_sweep.py)
+    auto kb_at = [&](int t) { return ((K0 + (((i64)vmax) << t) - 1) / (((i64)vmax) << t)) * (c.nout / K0); };
+    if (o.reduce_col_narrow && kb_at(txlog) < o.reduce_part_wgs) {
+        int fill = -1;  // the widest segment that still puts a workgroup on every CU (round 6)
+        const int t0 = txlog;
+        for (int t = txlog - 1; t >= 3 && (((i64)vmax << t) * es >= 128); --t) {
+            if ((red >> (8 - t)) < 8) break;  // fewer than 8 rows of the reduced space per lane row
+            if (fill < 0 && kb_at(t) >= 256) fill = t;
+            if (kb_at(t) >= o.reduce_part_wgs) {
+                txlog = t;
+                break;
+            }
+        }
+        // no width reaches the target, but one fills the device without a split: the second launch of a split costs more
+        // than a thinner first one (sum(A; dims=(3,4)) of (100,90,80,7) Float32: 9000 outputs, 560 rows each: 71 workgroups cut
+        // 7 ways + a second pass 8.9 us, 282 workgroups of 8 lanes x 32 rows in one launch: see profiles/r06_sum_cases.txt)
+        if (txlog == t0 && fill >= 0 && o.reduce_col_narrow >= 1 && kb_at(t0) < 256) txlog = fill;
+    }
+    rp.txlog = txlog;
+    const int tylog = 8 - txlog;
+    rp.g0log = std::min(tylog, ceil_log2(L0));
+    rp.g1log = tylog - rp.g0log;
+    i64 kb = kb_at(txlog);  // workgroups along the kept dims
+    i64 rows_per_wg = (i64)1 << tylog, y0 = (i64)1 << rp.g0log, y1 = (i64)1 << rp.g1log;
+    // exact lane map (round 6): a row of 100 Float32 is 25 vectors -- 32 lanes leave 22 % of the workgroup idle, 25 lanes x 10
+    // rows leave 2 % (and 10 rows = 4000 contiguous bytes per step).  Taken when it fills at least 3 % more lanes; the
+    // row may be cut into up to four even segments.  Valid for the vector width assumed here (the launch checks alignment).
+    rp.col_tx = 0;
+    if (o.reduce_col_exact) {
+        bool vdiv = vmax > 1 && K0 % vmax == 0;
+        for (int k = 1; k < c.M && vdiv; ++k)
+            if (c.strides[k][0] == 1)
+                for (int d = 1; d < c.N; ++d)
+                    if (c.strides[k][d] % vmax) vdiv = false;
+        const i64 vv = vdiv ? vmax : 1;
+        const i64 n0v = (K0 + vv - 1) / vv, per2 = vv << txlog, nk2 = (K0 + per2 - 1) / per2;
+        double best = (double)K0 / (double)(nk2 * per2);
+        i64 btx = 0;
+        // (cutting the row into more segments just to put a workgroup on every CU and avoid the split loses: rows of 100 as
+        // 4 x 7 lanes x 36 rows, sum over dims (2,4) of (100,90,80,7) Float32 11.4 us against 9.2 with the split)
+        for (i64 sg = 1; sg <= 4; ++sg) {
+            const i64 tx = (n0v + sg - 1) / sg;
+            if (tx > 256 || tx * vv * es < 64 || (tx & (tx - 1)) == 0) continue;
+            const i64 ty = 256 / tx;
+            if (red < 8 * ty) continue;  // short reductions keep the few-rows rule above
+            const double util = (double)n0v / (double)(sg * tx) * (double)(tx * ty) / 256.0;
+            if (util > best + 0.03) {
+                best = util;
+                btx = tx;
+                if (util >= 0.9) break;  // the fewest segments that fill the workgroup: longer contiguous pieces per row
+            }
+        }
+        if (btx) {
+            rp.col_tx = (int)btx;
+            rp.col_v = (int)vv;
+            rows_per_wg = 256 / btx;
+            // rows along the inner reduced dim: the largest divisor of the row count that it can fill
+            y0 = 1;
+            for (i64 dv = 1; dv <= rows_per_wg; ++dv)
+                if (rows_per_wg % dv == 0 && dv <= std::max<i64>(1, L0)) y0 = dv;
+            y1 = rows_per_wg / y0;
+            rp.col_y0 = (int)y0;
+            rp.col_y1 = (int)y1;
+            kb = ((n0v + btx - 1) / btx) * (c.nout / K0);
+        }
+    }
+    i64 split = 1;
+    // half the ROW form's target: every workgroup leaves TX*V partials per chunk, and the sweep has 512 ahead of 1024-4096
+    const i64 target = std::max<i64>(1, o.reduce_part_wgs / 2);
+    if (kb < target && red >= rows_per_wg * 16) split = std::max<i64>(1, std::min<i64>(target / kb, red / (rows_per_wg * 8)));
+    split = std::min<i64>(split, 4096);
+    // cut the outer reduced index first, the inner reduced dim with what is left (a short Q -- a trailing
+    // dim of 7 -- used to forbid any cut but 2 along L0: 160 workgroups for 19 MiB)
+    rp.qsplit = (int)even_cut(split, s.Q / y1);
+    rp.xsplit = (int)std::max<i64>(1, std::min<i64>(split / rp.qsplit, L0 / (4 * y0)));
+    rp.nparts = rp.xsplit * rp.qsplit;
+    rp.tr = (int)rows_per_wg;
+}
+
+// ROW: G consecutive lanes per output, vector loads along the inner reduced dim
+static void plan_part_row(const Canon& c, const PartShape& s, ReducePlan& rp) {
+    const Options& o = options();
+    const i64 red = s.red, L0 = s.L0, Q = s.Q;
+    const int vmax = s.vmax;
+    rp.kind = 1;
+    int glog = 8;
+    // (no floor on the lanes per output -- rounds 1-3 had 16: sum(A; dims=1) of a 3 x N array then ran on 1 lane in 16
+    // and took 200 us for 33 MB (now 15.4), of 100 x 50400 f32 7.6 us (now 4.75 with 4 lanes of 6 vectors each), of
+    // 32 x 200000 21.5 (now 5.6); tools/reduce_sweep.py, profiles/r03_reduce_sweep.txt)
+    const int gfloor = o.reduce_row_floor >= 0 ? (int)o.reduce_row_floor : 0;
+    while (glog > gfloor && red < ((i64)vmax << glog) * 4) --glog;
+    // a very short inner dim with kept dim 0 right behind it in memory (sum over the channels AND the rows of a
+    // 3 x W x H image): lanes along the outputs read neighbouring segments; lanes along the outer reduced index -- what
+    // the rule above picks when the whole reduction is long -- would each fetch 12 bytes from a line of their own
+    bool dense0 = o.reduce_row_dense && c.NK >= 1 && Q > 1 && c.dims[0] >= 256 && L0 * s.es <= 64;
+    for (int k = 1; k < c.M && dense0; ++k)
+        if (c.strides[k][c.NK] == 1 && c.strides[k][0] != L0) dense0 = false;
+    if (dense0) {
+        glog = 8;
+        while (glog > 0 && L0 < ((i64)vmax << glog) * 4) --glog;
+    }
+    rp.g0log = std::min(glog, ceil_log2((L0 + vmax - 1) / vmax));
+    rp.g1log = glog - rp.g0log;
+    const i64 groups = (c.nout + (256 >> glog) - 1) / (256 >> glog);
+    i64 split = 1;
+    if (groups < o.reduce_part_wgs && red >= ((i64)vmax << glog) * 16) split = std::max<i64>(1, std::min<i64>(o.reduce_part_wgs / groups, red / (((i64)vmax << glog) * 8)));
+    split = std::min<i64>(split, 4096);
+    rp.qsplit = (int)even_cut(split, Q >> rp.g1log);
+    rp.xsplit = (int)std::max<i64>(1, std::min<i64>(split / rp.qsplit, L0 / (((i64)vmax * 4) << rp.g0log)));
+    rp.nparts = rp.xsplit * rp.qsplit;
+    rp.tr = 1 << glog;
+}
+
+// general form: lanes cooperating per output: more when few outputs / long reductions
+static void plan_part_general(const Canon& c, const PartShape& s, ReducePlan& rp) {
+    const i64 red = s.red;
+    rp.kind = 0;
+    int tr = 1;
+    // the inputs' fastest-varying dim is a reduced one -> lanes along it coalesce
+    bool red_fast = false;
+    for (int k = 1; k < c.M; ++k)
+        for (int i = c.NK; i < c.N; ++i)
+            if (std::llabs(c.strides[k][i]) == 1) red_fast = true;
+    if (red_fast || c.nout < 256 * 256) {
+        while (tr < 256 && tr * 2 <= red && (tr < 64 || c.nout * tr < 256 * 1024)) tr <<= 1;
+    }
+    if (red_fast && tr < 16 && red >= 16) tr = 16;
+    rp.tr = tr;
+    // few destination elements, long reductions: cut the reduced range so that ~2048
+    // workgroups are in flight, partials folded by a second launch (also keeps the
+    // serial per-lane accumulation short, which is what bounds the rounding error)
+    const i64 groups = (c.nout + (256 / tr) - 1) / (256 / tr);
+    i64 split = 1;
+    if (groups < 1024 && red >= (i64)tr * 256) {
+        split = std::min<i64>(2048 / std::max<i64>(1, groups), red / ((i64)tr * 64));
+        split = std::max<i64>(1, std::min<i64>(split, 4096));
+    }
+    rp.nparts = (int)split;
+}
+
+static void plan_reduce_part(const Canon& c, ReducePlan& rp) {
+    PartShape s;
+    s.es = dtype_size(c.ct);
+    s.vmax = std::max(1, 16 / s.es);
+    s.red = c.total / std::max<i64>(1, c.nout);
+    // no reduced dim at all (an accumulating map, dest[I] = op(dest[I], f(...)), over up to MAXN kept
+    // dims): nothing to index at position NK -- the general form handles it
+    const bool nored = c.NK >= c.N;
+    s.L0 = nored ? 1 : c.dims[c.NK];  // inner reduced dim
+    s.Q = s.red / s.L0;               // outer reduced index (dims NK+1..)
+    // which vectorisable form applies?
+    bool row = !nored && inputs_run_along(c, c.NK);
+    bool col = !nored && c.strides[0][0] == 1 && inputs_run_along(c, 0);
+    const i64 force = options().reduce_part_kind;
+    if (force >= 0) {  // tuning / testing override
+        row = row && force == 1;
+        col = col && force == 2;
+    }
+    if (col) plan_part_col(c, s, rp);
+    else if (row) plan_part_row(c, s, rp);
+    else plan_part_general(c, s, rp);
+    if (rp.nparts > 1) rp.scratch_bytes = (size_t)c.nout * (size_t)rp.nparts * s.es;  // chunk partials
+}
+
 // ---- family selection -------------------------------------------------------------------------------
+// make_plan only selects: canonicalise, decide the family, call that family's planner (plan_flatb / plan_flat / plan_flat2,
+// plan_tiles, plan_orbit, plan_stream, plan_reduce_all / plan_reduce_part; GENERIC has nothing to plan), describe.
 int make_plan(const smr_problem* p, Plan& plan) {
     int rc = canonicalise(p, plan.c);
     if (rc) return rc;
@@ -1881,35 +1537,11 @@ int make_plan(const smr_problem* p, Plan& plan) {
     } else if (one) {
         fam = FAM_FLAT;
     } else if (c.redop == SMR_RED_NONE) {
-        bool stream = true;
-        for (int k = 0; k < c.M; ++k) {
-            i64 s = c.strides[k][0];
-            if (!(s == 1 || (k > 0 && s == 0))) stream = false;
-        }
-        if (stream && c.N >= 2 && o.force_family != FAM_STREAM) {
-            // short rows pack (256 >> txlog) entries of dim 1 into a workgroup; when dim 1 is short too (a permutation
-            // of a 4x4x4x... tensor) most lanes idle -- 8 of 256 for rows of 4 Float64 x 4 -- and the per-element
-            // decode of the GENERIC family wins (measured 4^8 Float64: 9.9 us -> tools/perf_sanity.py)
-            const int es0 = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
-            const i64 vmax = std::max<i64>(1, 16 / es0);
-            const i64 n0v = (c.dims[0] % vmax == 0) ? c.dims[0] / vmax : c.dims[0];
-            if (n0v <= 128) {
-                int txlog = 0;
-                while (((i64)1 << txlog) < n0v) ++txlog;
-                const i64 used = n0v * std::min<i64>(c.dims[1], (i64)256 >> txlog);
-                if (used * 4 < 256) stream = false;
-            }
-        }
-        if (stream && o.force_family != FAM_STREAM) {
-            const int es0 = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
-            bool transposed = false;
-            for (int k = 1; k < c.M; ++k) transposed = transposed || short_dim0_transposition(c, k, es0);
-            if (transposed && plan_tiles(c, plan.tile)) {
-                stream = false;
-                fam = FAM_TILED;
-            }
-        }
-        if (fam == FAM_TILED) {
+        const bool forced = o.force_family == FAM_STREAM, stream = stream_fits(c, forced);
+        bool transposed = false;  // (short_dim0_transposition: such inputs are staged like transposed ones)
+        for (int k = 1; k < c.M; ++k) transposed = transposed || short_dim0_transposition(c, k, elem_bytes(c));
+        if (stream && !forced && transposed && plan_tiles(c, plan.tile)) {
+            fam = FAM_TILED;
         } else if (stream) {
             fam = FAM_STREAM;
         } else if (o.force_family != FAM_TILED && o.force_family != FAM_GENERIC && orbit_ok()) {
@@ -1924,250 +1556,17 @@ int make_plan(const smr_problem* p, Plan& plan) {
         }
     } else {
         fam = (c.NK == 0) ? FAM_REDUCE_ALL : FAM_REDUCE_PART;
-        if (fam == FAM_REDUCE_ALL && c.N > 1) {
-            // a complete reduction whose dims do not fuse into one run (a sub-box, a permuted sub-box):
-            // the ROW form with a single destination element walks it without a per-element index
-            // decomposition (measured on a 1000x1000x256 box of a 1024x1024x256 array: 0.59 -> 5 TB/s)
-            bool row = true, any = false;
-            for (int k = 1; k < c.M; ++k) {
-                if (c.strides[k][0] == 1) any = true;
-                else if (c.strides[k][0] != 0) row = false;
-            }
-            if (row && any) fam = FAM_REDUCE_PART;
-        }
+        // a complete reduction whose dims do not fuse into one run (a sub-box, a permuted sub-box):
+        // the ROW form with a single destination element walks it without a per-element index
+        // decomposition (measured on a 1000x1000x256 box of a 1024x1024x256 array: 0.59 -> 5 TB/s)
+        if (fam == FAM_REDUCE_ALL && c.N > 1 && inputs_run_along(c, 0)) fam = FAM_REDUCE_PART;
     }
     if (o.force_family == FAM_GENERIC && c.redop == SMR_RED_NONE) fam = FAM_GENERIC;
     if (o.force_family == FAM_TILED && c.redop == SMR_RED_NONE && fam != FAM_TILED && plan_tiles(c, plan.tile)) fam = FAM_TILED;
     plan.family = fam;
-
-    if (fam == FAM_STREAM) {
-        // vector width: 16 B per lane when every unit-stride operand stays 16-B aligned
-        const int es = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
-        int v = (c.mixed || es >= 16) ? 1 : 16 / es;
-        for (int k = 0; k < c.M; ++k)
-            if (c.strides[k][0] != 1 && c.strides[k][0] != 0) v = 1;  // strided form
-        while (v > 1) {
-            bool ok = c.dims[0] % v == 0;
-            for (int k = 0; k < c.M && ok; ++k) {
-                if (c.strides[k][0] == 0) continue;
-                if (((uintptr_t)c.base[k] + (uintptr_t)(c.offsets[k] * c.esize[k])) % (size_t)(v * es)) ok = false;
-                for (int i = 1; i < c.N && ok; ++i)
-                    if (c.strides[k][i] % v) ok = false;
-            }
-            if (ok) break;
-            v >>= 1;
-        }
-        plan.vec = v;
-        plan.vec_ua = false;
-        // Round 5: rows that are not whole aligned vectors (odd lengths, odd row strides, views starting inside a vector) still move
-        // as 16-byte vectors -- at element alignment, plus one partial vector per row (smr_k_stream.hip: UVec) -- when the elements
-        // are 4 or 8 bytes and a row holds at least four vectors.
-        {
-            const int vmax = (c.mixed || es >= 16) ? 1 : 16 / es;
-            bool unit = true;
-            for (int k = 0; k < c.M; ++k)
-                if (c.strides[k][0] != 1 && c.strides[k][0] != 0) unit = false;
-            // (short rows with a long tail lose: rows of 63 Float32 = 15 vectors + 3 single elements 24.9 -> 27.1 us; rows of 17
-            // Float64 = 8 vectors + 1 element gain 9 %: a tail of one element, or at least 32 vectors per row.  tools/stream_ua_ab.py,
-            // profiles/r05_stream_ua_ab.txt: (257,129,65) (0,2,1) 12.3 -> 9.5 us, (999,1001) axpy 4.7 -> 3.1 us, (1001,999,5) f32 10.9 -> 8.0)
-            if (o.stream_ua && v < vmax && unit && es >= 4 && c.dims[0] >= 4 * vmax && (c.dims[0] % vmax <= 1 || c.dims[0] >= 32 * vmax)) {
-                plan.vec = vmax;
-                plan.vec_ua = true;
-            }
-        }
-    }
-    if (fam == FAM_REDUCE_ALL || fam == FAM_REDUCE_PART) {
-        const int es = dtype_size(c.ct);
-        if (fam == FAM_REDUCE_ALL) {
-            i64 per_block = 256 * 16;
-            i64 nb = (c.total + per_block - 1) / per_block;
-            nb = std::max<i64>(1, std::min<i64>(nb, std::max<i64>(1, o.reduce_blocks)));
-            plan.red_blocks = (int)nb;
-            plan.scratch_bytes = (size_t)nb * es;
-        } else {
-            const i64 red = c.total / std::max<i64>(1, c.nout);
-            // no reduced dim at all (an accumulating map, dest[I] = op(dest[I], f(...)), over up to MAXN kept
-            // dims): nothing to index at position NK -- the general form handles it
-            const bool nored = c.NK >= c.N;
-            const i64 L0 = nored ? 1 : c.dims[c.NK];  // inner reduced dim
-            const i64 Q = red / L0;                    // outer reduced index (dims NK+1..)
-            // which vectorisable form applies?
-            bool row = !nored, col = !nored && c.strides[0][0] == 1, any_row = false, any_col = false;
-            for (int k = 1; k < c.M && !nored; ++k) {
-                const i64 sr = c.strides[k][c.NK], sc = c.strides[k][0];
-                if (sr == 1) any_row = true;
-                else if (sr != 0) row = false;
-                if (sc == 1) any_col = true;
-                else if (sc != 0) col = false;
-            }
-            row = row && any_row;
-            col = col && any_col;
-            const int vmax = std::max(1, 16 / es);
-            auto p2ceil = [](i64 v) {
-                int l = 0;
-                while (((i64)1 << l) < v) ++l;
-                return l;
-            };
-            // number of chunks an index range of `n` is cut into when about `want` are asked for: all of n when that is
-            // within 2x (a trailing dim of 7 cut 6 ways would leave chunks of 2,2,2,1 and two idle workgroups), else a
-            // count that leaves no chunk empty
-            auto even_cut = [](i64 want, i64 n) -> i64 {
-                if (n <= 1 || want <= 1) return 1;
-                if (n <= 2 * want) return n;
-                const i64 per = (n + want - 1) / want;
-                return (n + per - 1) / per;
-            };
-            if (o.reduce_part_kind >= 0) {  // tuning / testing override
-                row = row && o.reduce_part_kind == 1;
-                col = col && o.reduce_part_kind == 2;
-            }
-            if (col) {
-                // COL: a workgroup = TX lanes along kept dim 0 (vmax elements each) x TY rows of the
-                // reduced space; LDS tree over the rows
-                plan.part_kind = 2;
-                const i64 K0 = c.dims[0];
-                int txlog = std::min(8, p2ceil((K0 + vmax - 1) / vmax));
-                // rows of the reduced space per workgroup: fewer when the reduction is short (sum over a trailing dim of 7:
-                // every lane then walks its 7 rows itself instead of 8 lanes sharing them through LDS)
-                txlog = std::min<int>(txlog, std::max<int>((int)o.reduce_col_txlog, 8 - p2ceil(std::max<i64>(1, red / 8))));
-                // too few workgroups along the kept dims: narrower row segments (down to 128 bytes) give 2-4x as many and more
-                // rows to each -- when that makes the split unnecessary it saves the partials and the second launch
-                // (sum(A; dims=2) of 512x384x64 f32: 16.0 -> 12.4 us, 256^3: 18.4 -> 14.7 us, tools/reduce_sweep.py)
-                auto kb_at = [&](int t) { return ((K0 + (((i64)vmax) << t) - 1) / (((i64)vmax) << t)) * (c.nout / K0); };
-                if (o.reduce_col_narrow && kb_at(txlog) < o.reduce_part_wgs) {
-                    int fill = -1;  // the widest segment that still puts a workgroup on every CU (round 6)
-                    const int t0 = txlog;
-                    for (int t = txlog - 1; t >= 3 && (((i64)vmax << t) * es >= 128); --t) {
-                        if ((red >> (8 - t)) < 8) break;  // fewer than 8 rows of the reduced space per lane row
-                        if (fill < 0 && kb_at(t) >= 256) fill = t;
-                        if (kb_at(t) >= o.reduce_part_wgs) {
-                            txlog = t;
-                            break;
-                        }
-                    }
-                    // no width reaches the target, but one fills the device without a split: the second launch of a split costs more
-                    // than a thinner first one (sum(A; dims=(3,4)) of (100,90,80,7) Float32: 9000 outputs, 560 rows each: 71 workgroups cut
-                    // 7 ways + a second pass 8.9 us, 282 workgroups of 8 lanes x 32 rows in one launch: see profiles/r06_sum_cases.txt)
-                    if (txlog == t0 && fill >= 0 && o.reduce_col_narrow >= 1 && kb_at(t0) < 256) txlog = fill;
-                }
-                plan.part_txlog = txlog;
-                const int tylog = 8 - txlog;
-                plan.part_g0log = std::min(tylog, p2ceil(L0));
-                plan.part_g1log = tylog - plan.part_g0log;
-                i64 kb = ((K0 + (((i64)vmax) << txlog) - 1) / (((i64)vmax) << txlog)) * (c.nout / K0);
-                i64 rows_per_wg = (i64)1 << tylog, y0 = (i64)1 << plan.part_g0log, y1 = (i64)1 << plan.part_g1log;
-                // exact lane map (round 6): a row of 100 Float32 is 25 vectors -- 32 lanes leave 22 % of the workgroup idle, 25 lanes x 10
-                // rows leave 2 % (and 10 rows = 4000 contiguous bytes per step).  Taken when it fills at least 3 % more lanes; the
-                // row may be cut into up to four even segments.  Valid for the vector width assumed here (the launch checks alignment).
-                plan.part_col_tx = 0;
-                if (o.reduce_col_exact) {
-                    bool vdiv = vmax > 1 && K0 % vmax == 0;
-                    for (int k = 1; k < c.M && vdiv; ++k)
-                        if (c.strides[k][0] == 1)
-                            for (int d = 1; d < c.N; ++d)
-                                if (c.strides[k][d] % vmax) vdiv = false;
-                    const i64 vv = vdiv ? vmax : 1;
-                    const i64 n0v = (K0 + vv - 1) / vv, per2 = vv << txlog, nk2 = (K0 + per2 - 1) / per2;
-                    double best = (double)K0 / (double)(nk2 * per2);
-                    i64 btx = 0;
-                    // (cutting the row into more segments just to put a workgroup on every CU and avoid the split loses: rows of 100 as
-                    // 4 x 7 lanes x 36 rows, sum over dims (2,4) of (100,90,80,7) Float32 11.4 us against 9.2 with the split)
-                    for (i64 sg = 1; sg <= 4; ++sg) {
-                        const i64 tx = (n0v + sg - 1) / sg;
-                        if (tx > 256 || tx * vv * es < 64 || (tx & (tx - 1)) == 0) continue;
-                        const i64 ty = 256 / tx;
-                        if (red < 8 * ty) continue;  // short reductions keep the few-rows rule above
-                        const double util = (double)n0v / (double)(sg * tx) * (double)(tx * ty) / 256.0;
-                        if (util > best + 0.03) {
-                            best = util;
-                            btx = tx;
-                            if (util >= 0.9) break;  // the fewest segments that fill the workgroup: longer contiguous pieces per row
-                        }
-                    }
-                    if (btx) {
-                        plan.part_col_tx = (int)btx;
-                        plan.part_col_v = (int)vv;
-                        rows_per_wg = 256 / btx;
-                        // rows along the inner reduced dim: the largest divisor of the row count that it can fill
-                        y0 = 1;
-                        for (i64 dv = 1; dv <= rows_per_wg; ++dv)
-                            if (rows_per_wg % dv == 0 && dv <= std::max<i64>(1, L0)) y0 = dv;
-                        y1 = rows_per_wg / y0;
-                        plan.part_col_y0 = (int)y0;
-                        plan.part_col_y1 = (int)y1;
-                        kb = ((n0v + btx - 1) / btx) * (c.nout / K0);
-                    }
-                }
-                i64 split = 1;
-                // half the ROW form's target: every workgroup leaves TX*V partials per chunk, and the sweep has 512 ahead of 1024-4096
-                const i64 target = std::max<i64>(1, o.reduce_part_wgs / 2);
-                if (kb < target && red >= rows_per_wg * 16) split = std::max<i64>(1, std::min<i64>(target / kb, red / (rows_per_wg * 8)));
-                split = std::min<i64>(split, 4096);
-                // cut the outer reduced index first, the inner reduced dim with what is left (a short Q -- a trailing
-                // dim of 7 -- used to forbid any cut but 2 along L0: 160 workgroups for 19 MiB)
-                plan.part_qsplit = (int)even_cut(split, Q / y1);
-                plan.part_xsplit = (int)std::max<i64>(1, std::min<i64>(split / plan.part_qsplit, L0 / (4 * y0)));
-                plan.part_split = plan.part_xsplit * plan.part_qsplit;
-                plan.part_tr = (int)rows_per_wg;
-            } else if (row) {
-                // ROW: G consecutive lanes per output, vector loads along the inner reduced dim
-                plan.part_kind = 1;
-                int glog = 8;
-                // (no floor on the lanes per output -- rounds 1-3 had 16: sum(A; dims=1) of a 3 x N array then ran on 1 lane in 16
-                // and took 200 us for 33 MB (now 15.4), of 100 x 50400 f32 7.6 us (now 4.75 with 4 lanes of 6 vectors each), of
-                // 32 x 200000 21.5 (now 5.6); tools/reduce_sweep.py, profiles/r03_reduce_sweep.txt)
-                const int gfloor = o.reduce_row_floor >= 0 ? (int)o.reduce_row_floor : 0;
-                while (glog > gfloor && red < ((i64)vmax << glog) * 4) --glog;
-                // a very short inner dim with kept dim 0 right behind it in memory (sum over the channels AND the rows of a
-                // 3 x W x H image): lanes along the outputs read neighbouring segments; lanes along the outer reduced index -- what
-                // the rule above picks when the whole reduction is long -- would each fetch 12 bytes from a line of their own
-                bool dense0 = o.reduce_row_dense && c.NK >= 1 && Q > 1 && c.dims[0] >= 256 && L0 * es <= 64;
-                for (int k = 1; k < c.M && dense0; ++k)
-                    if (c.strides[k][c.NK] == 1 && c.strides[k][0] != L0) dense0 = false;
-                if (dense0) {
-                    glog = 8;
-                    while (glog > 0 && L0 < ((i64)vmax << glog) * 4) --glog;
-                }
-                plan.part_g0log = std::min(glog, p2ceil((L0 + vmax - 1) / vmax));
-                plan.part_g1log = glog - plan.part_g0log;
-                const i64 groups = (c.nout + (256 >> glog) - 1) / (256 >> glog);
-                i64 split = 1;
-                if (groups < o.reduce_part_wgs && red >= ((i64)vmax << glog) * 16) split = std::max<i64>(1, std::min<i64>(o.reduce_part_wgs / groups, red / (((i64)vmax << glog) * 8)));
-                split = std::min<i64>(split, 4096);
-                plan.part_qsplit = (int)even_cut(split, Q >> plan.part_g1log);
-                plan.part_xsplit = (int)std::max<i64>(1, std::min<i64>(split / plan.part_qsplit, L0 / (((i64)vmax * 4) << plan.part_g0log)));
-                plan.part_split = plan.part_xsplit * plan.part_qsplit;
-                plan.part_tr = 1 << glog;
-            } else {
-                // general form: lanes cooperating per output: more when few outputs / long reductions
-                int tr = 1;
-                // the inputs' fastest-varying dim is a reduced one -> lanes along it coalesce
-                bool red_fast = false;
-                for (int k = 1; k < c.M; ++k)
-                    for (int i = c.NK; i < c.N; ++i)
-                        if (std::llabs(c.strides[k][i]) == 1) red_fast = true;
-                if (red_fast || c.nout < 256 * 256) {
-                    while (tr < 256 && tr * 2 <= red && (tr < 64 || c.nout * tr < 256 * 1024)) tr <<= 1;
-                }
-                if (red_fast && tr < 16 && red >= 16) tr = 16;
-                plan.part_tr = tr;
-                // few destination elements, long reductions: cut the reduced range so that ~2048
-                // workgroups are in flight, partials folded by a second launch (also keeps the
-                // serial per-lane accumulation short, which is what bounds the rounding error)
-                const i64 groups = (c.nout + (256 / tr) - 1) / (256 / tr);
-                i64 split = 1;
-                if (groups < 1024 && red >= (i64)tr * 256) {
-                    split = std::min<i64>(2048 / std::max<i64>(1, groups), red / ((i64)tr * 64));
-                    split = std::max<i64>(1, std::min<i64>(split, 4096));
-                }
-                plan.part_split = (int)split;
-            }
-            if (plan.part_split > 1) {
-                plan.scratch_bytes = (size_t)c.nout * (size_t)plan.part_split * es;  // chunk partials
-                plan.red_blocks = plan.part_split;  // > 1: the API allocates the partials buffer
-            }
-        }
-    }
+    if (fam == FAM_STREAM) plan_stream(c, plan.stream);
+    if (fam == FAM_REDUCE_ALL) plan_reduce_all(c, plan.red);
+    if (fam == FAM_REDUCE_PART) plan_reduce_part(c, plan.red);
     describe(plan);
     return SMR_OK;
 }
@@ -2182,7 +1581,7 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
     };
     const i64 rs = options().reduce_single;
     if (plan.family == FAM_REDUCE_ALL) {
-        int blocks = plan.red_blocks;
+        int blocks = plan.red.nparts;
         if (blocks > 1 && !have_scratch) blocks = 1;
         r.nparts = blocks;
         // up to 64 partials are folded inside the launch (1 MiB: 4.9 -> 4.1 us; tools/reduce_all_sweep.py) -- the arrivals of ONE
@@ -2201,15 +1600,15 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
         return r;
     }
     if (plan.family != FAM_REDUCE_PART) return r;
-    const int nsplit = (plan.part_split > 1 && have_scratch) ? plan.part_split : 1;
+    const int nsplit = (plan.red.nparts > 1 && have_scratch) ? plan.red.nparts : 1;
     r.nparts = nsplit;
     const int vmax = (c.mixed || es >= 16) ? 1 : 16 / es;
-    if (plan.part_kind == 0) {
-        const int ob = 256 / plan.part_tr;
+    if (plan.red.kind == 0) {
+        const int ob = 256 / plan.red.tr;
         r.groups = (c.nout + ob - 1) / ob;
     } else {
         // vector width: the vector axis must divide, every vector-loaded operand must be aligned
-        const int vax = plan.part_kind == 1 ? c.NK : 0;  // axis the vectors run along
+        const int vax = plan.red.kind == 1 ? c.NK : 0;  // axis the vectors run along
         bool vec = vmax > 1 && (c.dims[vax] % vmax == 0);
         for (int k = 1; k < c.M && vec; ++k) {
             if (c.strides[k][vax] != 1) continue;
@@ -2218,19 +1617,19 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
                 if (d != vax && (c.strides[k][d] % vmax)) vec = false;
         }
         r.vec = vec ? vmax : 1;
-        if (plan.part_kind == 1) {
-            const int ob = 256 >> (plan.part_g0log + plan.part_g1log);
+        if (plan.red.kind == 1) {
+            const int ob = 256 >> (plan.red.g0log + plan.red.g1log);
             r.groups = (c.nout + ob - 1) / ob;
         } else {
-            r.ctx = 1 << plan.part_txlog;
-            r.cty = 256 >> plan.part_txlog;
-            r.cy0 = 1 << plan.part_g0log;
-            r.cy1 = 1 << plan.part_g1log;
-            if (plan.part_col_tx > 0 && plan.part_col_v == r.vec) {  // exact lane map (make_plan), planned for this vector width
-                r.ctx = plan.part_col_tx;
+            r.ctx = 1 << plan.red.txlog;
+            r.cty = 256 >> plan.red.txlog;
+            r.cy0 = 1 << plan.red.g0log;
+            r.cy1 = 1 << plan.red.g1log;
+            if (plan.red.col_tx > 0 && plan.red.col_v == r.vec) {  // exact lane map (plan_part_col), planned for this vector width
+                r.ctx = plan.red.col_tx;
                 r.cty = 256 / r.ctx;
-                r.cy0 = plan.part_col_y0;
-                r.cy1 = plan.part_col_y1;
+                r.cy0 = plan.red.col_y0;
+                r.cy1 = plan.red.col_y1;
             }
             const i64 per = (i64)r.vec * r.ctx;
             r.groups = ((c.dims[0] + per - 1) / per) * (c.nout / c.dims[0]);
@@ -2279,14 +1678,14 @@ void describe(Plan& plan) {
         n += std::snprintf(buf + n, sizeof buf - n, " flat_side=%s run=%dx%d(d%d)%s line=d%d:%d", fp.dir == 0 ? "dest" : "input", fp.R, 1 << fp.tplog, fp.p,
                            fp.fuse ? "+line" : (fp.lshare ? " shared-lead" : ""), fp.q, 1 << fp.tqlog);
     } else if (plan.family == FAM_STREAM) {
-        n += std::snprintf(buf + n, sizeof buf - n, " vec=%d%s", plan.vec, plan.vec_ua ? "(element-aligned+tail)" : "");
+        n += std::snprintf(buf + n, sizeof buf - n, " vec=%d%s", plan.stream.vec, plan.stream.vec_ua ? "(element-aligned+tail)" : "");
     } else if (plan.family == FAM_REDUCE_ALL) {
-        n += std::snprintf(buf + n, sizeof buf - n, " blocks=%d", plan.red_blocks);
+        n += std::snprintf(buf + n, sizeof buf - n, " blocks=%d", plan.red.nparts);
     } else if (plan.family == FAM_REDUCE_PART) {
         static const char* kinds[] = {"general", "row", "col"};
-        n += std::snprintf(buf + n, sizeof buf - n, " nout=%lld form=%s lanes_per_out=%d split=%d", (long long)c.nout, kinds[plan.part_kind],
-                           plan.part_tr, plan.part_split);
-        if (plan.part_kind == 2 && plan.part_col_tx) n += std::snprintf(buf + n, sizeof buf - n, " lanes=%dx%d", plan.part_col_tx, 256 / plan.part_col_tx);
+        n += std::snprintf(buf + n, sizeof buf - n, " nout=%lld form=%s lanes_per_out=%d split=%d", (long long)c.nout, kinds[plan.red.kind],
+                           plan.red.tr, plan.red.nparts);
+        if (plan.red.kind == 2 && plan.red.col_tx) n += std::snprintf(buf + n, sizeof buf - n, " lanes=%dx%d", plan.red.col_tx, 256 / plan.red.col_tx);
     }
     if (plan.family == FAM_REDUCE_ALL || plan.family == FAM_REDUCE_PART) {
         // as launched with the bases the plan was made with (the partials buffer is allocated on the first execution)

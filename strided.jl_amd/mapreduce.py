@@ -175,7 +175,7 @@ def _serialized(f, M, dts):
     e = E.trace(f, M - 1)
     if E.max_arg(e) > M - 1:
         raise ValueError("f uses more arguments than arrays were given")
-    # the library computes the call in the widest float class among ALL operands (csrc/smr_plan.cpp:
+    # the library computes the call in the widest float class among ALL operands (csrc/smr_canon.cpp:
     # canonicalise); operations Julia would carry out in Float32 get a ROUND32 when that class is wider
     wide = any(d in (np.dtype(np.float64), np.dtype(np.complex128)) or np.issubdtype(d, np.integer) or d == np.bool_ for d in dts)
     # ... or a strongly typed 64-bit scalar inside f (`A32 .* 0.1`: Julia multiplies in Float64): SMR_OP_WIDEN
