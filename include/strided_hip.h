@@ -266,7 +266,7 @@ int smr_stream_sync(void* stream);
  * packet on one of four HSA queues it owns, choosing the queue by the data -- a launch that conflicts with nothing in flight goes to
  * the least loaded queue and runs concurrently with its predecessors, one that conflicts with launches on one queue follows them
  * there, one that conflicts with several queues waits for them through a barrier-AND packet; completion signals retire the ranges
- * (csrc/smr_seq.cpp: eager direct dispatch; ~1 us of host time per launch instead of HIP's 3.6-4 us).  Results are those of in-order
+ * (csrc/smr_eager.cpp: eager direct dispatch; ~1 us of host time per launch instead of HIP's 3.6-4 us).  Results are those of in-order
  * execution.  The library fences by itself (waits for its queues) before every copy / synchronisation / sequence replay it performs on
  * such a stream (smr_memcpy_*, smr_stream_sync, smr_mapreduce_scalar, smr_seq_run, smr_free, smr_plan_destroy) and drains the HIP
  * work it queued there before the next direct launch.  Option "eager_direct" = 0 sends the launches through HIP instead, in stream
@@ -348,6 +348,16 @@ int smr_debug_kernarg_layout(const void* elf, size_t bytes, const char* symbol, 
    the end -- unused and repeated operands are dropped); *nwraps the number of added instructions, *compute_class the SMR_* dtype
    computed in (-1: a bit copy).  Output pointers may be null.  Returns the length in instructions, or the (negative) error code. */
 int smr_debug_canon_prog(const smr_problem* problem, uint8_t* code, int cap, int* nwraps, int* compute_class, int32_t* orig);
+/* Test hook, host-only: the replay scheduler of recorded sequences (csrc/smr_sched.cpp) on `nexec` synthetic executions.  Per
+   execution i: nspans[2i], nspans[2i+1] = how many byte ranges it reads / writes; `spans` holds them all in that order as [lo, hi)
+   pairs; launches[5i..] = number of launches, grid of the first, first launch sliceable?, every launch self-released?, same_as (index
+   of the first execution with the same plan and base pointers).  knobs = max_queues, slices, all_ordered, self_release_max_total,
+   number of (component, slices) pairs in comp_slices.  Results: per_exec[4i..] = component, acquire, first queue, slices;
+   totals[0..3] = components, sliced components, queues, cache_resident; *footprint = bytes of the union of all ranges;
+   packets[8n..] = queue, execution, launch, slice, lo, hi, barrier, acquire of packet n, queue by queue in submission order (at most
+   packet_cap rows).  Output pointers may be null.  Returns the number of packets, or the (negative) error code. */
+int smr_debug_seq_schedule(int nexec, const int32_t* nspans, const int64_t* spans, const int32_t* launches, const int64_t* knobs, const int32_t* comp_slices,
+                           int32_t* per_exec, int32_t* totals, int64_t* footprint, int32_t* packets, int packet_cap);
 
 
 /* ---- the hot path --------------------------------------------------------------------- */

@@ -141,7 +141,7 @@ static int execute_family(const Plan& plan, void* const* bases, hipStream_t s);
 
 static int execute(const Plan& plan, void* const* bases, hipStream_t s) {
     if (!jit_no_launch() && !recorder()) {
-        // a library-owned stream: the library submits the launch itself (smr_seq.cpp: eager direct dispatch), on the hardware queue its
+        // a library-owned stream: the library submits the launch itself (smr_eager.cpp: eager direct dispatch), on the hardware queue its
         // data dependencies select -- independent executions run concurrently, host cost ~1 us instead of HIP's 3.6-4 us
         hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
         if (options().eager_direct && stream_is_owned(s) && eager_available(s) &&
@@ -316,7 +316,7 @@ static void plan_free(smr_plan* h) {
     delete h;
 }
 
-// ---- hooks for smr_seq.cpp (the smr_plan struct is private to this file) ------------------------------------------------
+// ---- hooks for smr_seq.cpp, declared in smr_direct.h (the smr_plan struct is private to this file) --------------------------------------
 namespace smr {
 int seq_execute_plan(smr_plan* plan, void* const* bases, hipStream_t s, bool prepare_only) {
     if (prepare_only) return smr_plan_prepare(plan);

@@ -272,7 +272,7 @@ struct Plan {
         return {&tiled_cache[0].tab, &tiled_cache[1].tab, &tiled_cache[2].tab, &tiled_cache[3].tab, &tiled_order,
                 &orbit_cache[0].tab, &orbit_cache[1].tab, &orbit_list, &pair_cache.tab};
     }
-    // eager direct dispatch (smr_seq.cpp): argument blocks of this plan's launches that are resident in device memory, keyed by their
+    // eager direct dispatch (smr_eager.cpp): argument blocks of this plan's launches that are resident in device memory, keyed by their
     // bytes -- a repeated execution (same base pointers) reuses the block: no write through the BAR, no read-back round trip
     struct ArgBlock {
         int launch = 0;
@@ -415,14 +415,14 @@ JitStats jit_stats();
 // other streams.
 int fence_for_foreign_work(hipStream_t s);
 
-// Recording (smr_seq.cpp): while a sequence records, SMR_LAUNCH / jit_launch append what they WOULD launch instead of launching it
+// Recording (the recorder: smr_direct.cpp): while a sequence records, SMR_LAUNCH / jit_launch append what they WOULD launch instead of launching it
 struct RecLaunch {
     const void* hostfn = nullptr;  // host stub of a precompiled kernel; nullptr = runtime-compiled: found by `kname`
     std::string kname;             // runtime-compiled: the (per-program unique) entry point of the loaded code object
     std::shared_ptr<void> keep;    // runtime-compiled: owner of the loaded module (it must outlive the packets that name its code)
     unsigned grid = 0, block = 0, lds = 0;
     // The launcher's statement that the workgroups of this launch are independent and that a contiguous block range [lo, hi) can be
-    // launched on its own (smr_seq.cpp cuts single-launch components into such ranges, one hardware queue each):
+    // launched on its own (smr_sched.cpp cuts single-launch components into such ranges, one hardware queue each):
     //   1: the 32-bit field at byte `slice_off` of the argument block is added to blockIdx.x by the kernel (set it to lo);
     //   2: the pointer at byte `slice_off` addresses a table with one row of `slice_row` bytes per workgroup (advance it by lo rows).
     int slice_kind = 0;
@@ -434,7 +434,7 @@ struct RecLaunch {
     std::vector<unsigned char> args;  // the explicit kernel arguments in kernarg-segment layout
 };
 std::vector<RecLaunch>* recorder();  // thread-local, nullptr when nothing records
-// eager direct dispatch on library-owned streams (smr_seq.cpp)
+// eager direct dispatch on library-owned streams (smr_eager.cpp)
 struct Plan;
 int eager_submit(const Plan& plan, std::vector<RecLaunch>& launches, const std::vector<std::pair<uintptr_t, uintptr_t>>& rd,
                  const std::vector<std::pair<uintptr_t, uintptr_t>>& wr, hipStream_t s);
@@ -447,7 +447,7 @@ void eager_request_sys_acquire(hipStream_t s);
 long eager_stat(int which);
 bool eager_available(hipStream_t s);              // (of the stream's device)
 int eager_fence_if_active();
-bool eager_recent_writes_fit(uintptr_t dest_lo, uintptr_t dest_hi);  // smr_seq.cpp: the eager path's "are the recent destinations cache-resident" estimate
+bool eager_recent_writes_fit(uintptr_t dest_lo, uintptr_t dest_hi);  // smr_eager.cpp: the eager path's "are the recent destinations cache-resident" estimate
 void mark_sliceable(int kind, unsigned off, unsigned row);  // applies to the NEXT recorded launch of the calling thread (no-op when nothing records)
 void mark_self_released();                                  // likewise: RecLaunch::self_released
 void take_slice_mark(RecLaunch& r);

@@ -1,6 +1,6 @@
 // smr_kmeta.h -- kernarg layout of a kernel, read from the code object's own metadata.
 //
-// Direct dispatch (smr_seq.cpp) writes the kernel-argument block itself: the explicit arguments followed by the hidden ("implicit")
+// Direct dispatch (smr_direct.cpp) writes the kernel-argument block itself: the explicit arguments followed by the hidden ("implicit")
 // arguments the compiler reads blockDim / gridDim / the dynamic LDS size from.  Where those hidden fields live is recorded by the
 // compiler in the code object: ELF note NT_AMDGPU_METADATA (owner "AMDGPU", type 32), a MessagePack document whose
 // amdhsa.kernels[].args[] entries carry .offset / .size / .value_kind.  This file parses exactly that (ELF64 little endian, the
@@ -41,7 +41,7 @@ void kmeta_fill_hidden(const KernargLayout& layout, unsigned char* block, uint32
 
 // The layout code-object-v5 prescribes for a kernel whose explicit arguments end at `explicit_end` (hidden block at the next multiple
 // of 8: block counts +0, group sizes +12, remainders +18, global offsets +40, grid dims +64, dynamic LDS size +120).  Used when the
-// metadata cannot be read (and then only after the self-test kernel confirmed it, smr_seq.cpp).
+// metadata cannot be read (and then only after the self-test kernel confirmed it, smr_direct.cpp).
 KernargLayout kmeta_v5_default(size_t explicit_end, size_t kernarg_size);
 
 }  // namespace smr

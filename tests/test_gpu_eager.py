@@ -1,4 +1,4 @@
-"""GPU: eager direct dispatch on a library-owned stream (smr_stream_create; csrc/smr_seq.cpp).  The library submits every launch itself
+"""GPU: eager direct dispatch on a library-owned stream (smr_stream_create; csrc/smr_eager.cpp).  The library submits every launch itself
 as an AQL packet on one of four HSA queues, chosen by the data dependencies: independent executions run concurrently, conflicting
 ones are ordered (same queue, or a barrier-AND packet across queues).  The contract under test is the reference's
 (/root/reference/src/mapreduce.jl:203-223: spawn what is independent, wait where it must): whatever overlaps, the results are

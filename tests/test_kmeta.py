@@ -1,6 +1,6 @@
 """Kernarg layout from the code object's metadata (csrc/smr_kmeta.cpp) -- CPU tests on the BUILT library's own code objects.
 
-Direct dispatch (csrc/smr_seq.cpp) fills the hidden kernel arguments (block counts, group sizes, grid dims, dynamic LDS size) at the
+Direct dispatch (csrc/smr_direct.cpp) fills the hidden kernel arguments (block counts, group sizes, grid dims, dynamic LDS size) at the
 offsets the compiler recorded in the code object's NT_AMDGPU_METADATA note instead of hard-coding the code-object-v5 layout (VERDICT r4,
 next-round item 4a).  Here the parser runs over every gfx950 code object embedded in libstrided_hip.so: the fat binary section is cut
 into its compressed bundles, each is unbundled with clang-offload-bundler, and every kernel's layout is checked against
