@@ -422,6 +422,45 @@ int64_t smr_plan_flat_side(const smr_plan* plan, int64_t* out, size_t cap);
  *   then N dims, N destination strides, N input strides, P offsets srcoff[r] (input offset inside the block of destination position r) */
 int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
 
+/* ---- grouped launches: many small independent maps as ONE kernel launch --------------------------------
+ * A launch cannot finish in under about 2 us on MI355X, so K small maps issued one by one cost K launches however little each
+ * moves (the blocks of a block-sparse tensor contraction: permutedims!, axpby!, copy! on dozens to hundreds of sub-views of a few
+ * parents).  A GROUP is K maps ("members") that run as one launch of one kernel (csrc/smr_k_group.hip): every workgroup finds its
+ * member in a device table and runs it.  No reference counterpart (the reference spawns one task tree per call).
+ * smr_group_create accepts the members when all of this holds; anything else that is valid returns SMR_EUNSUPPORTED with a message
+ * naming the first offending member, malformed input SMR_EINVAL:
+ *   - 1 <= count <= 65535, and every member is a valid map (redop == SMR_RED_NONE);
+ *   - once canonicalised, all members compute in the same class, agree on whether they are bit copies and whether operand types
+ *     are converted, have the same number M of distinct operands, the same dtype and conj flag per operand position and the same
+ *     f-program including its constants: the kernel is instantiated once, f is ONE functor for the whole launch.  Members may
+ *     differ in rank, dims, strides, base pointers and offsets;
+ *   - every member has at most 2^31 - 1 box elements;
+ *   - independence: without SMR_GROUP_INDEPENDENT the bounding byte range [lo, hi) of a member's destination must not intersect
+ *     the range of ANOTHER member's destination or inputs (the same ranges a recorded sequence compares); a member's destination
+ *     may alias that member's own inputs under the rules of a single call.  With SMR_GROUP_INDEPENDENT the check is skipped and
+ *     the CALLER asserts that no member writes an element another member reads or writes.  The flag is the only way to group
+ *     interleaved blocks of one parent array, whose byte ranges overlap although their elements do not.
+ * smr_group_create and smr_group_layout are host arithmetic only and need no device (like smr_plan_create).  smr_group_prepare
+ * uploads the two device tables and compiles + loads the kernel of a runtime-compiled f without launching; the first
+ * smr_group_execute does the same when prepare was not called (the uploads are synchronous copies: prepare before capturing
+ * an execute into a hipGraph).  smr_group_execute is ONE kernel launch, asynchronous on `stream` (NULL = the stream of member 0);
+ * its result is bit-identical to smr_mapreduce on each member in order.  The launch goes through HIP; on a library-owned stream
+ * (smr_stream_create) it is ordered behind the library's direct launches and the stream's next direct launch waits for it.  The base
+ * pointers are fixed at creation (no rebinding), and a group cannot be recorded into a sequence.
+ * smr_group_describe: one line, "family=group members=K grid=G linear=a transposing=b f=<functor> jit=0/1 bytes=...".
+ * smr_group_layout: per member 4 values -- form (0 linear, 1 transposing), first workgroup, workgroups, canonical rank; returns
+ * 4 * count and writes min(that, cap) values.  The members' workgroup ranges tile [0, grid) in member order.                     */
+typedef struct smr_group smr_group;
+#define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
+int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out);
+int smr_group_prepare(smr_group* g);
+int smr_group_execute(smr_group* g, void* stream);
+int smr_group_describe(const smr_group* g, char* buf, size_t buflen);
+/* Sum of the members' algorithmic bytes (smr_plan_algorithmic_bytes). */
+int64_t smr_group_algorithmic_bytes(const smr_group* g);
+int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap);
+int smr_group_destroy(smr_group* g);
+
 /* Runtime compilation.  An `f` without a natively compiled functor is specialised the way
  * Julia specialises the reference's @generated kernel per closure (src/mapreduce.jl:229-425):
  * the f-program is turned into a C++ functor and the plan's kernel is compiled for it with
@@ -520,6 +559,8 @@ int smr_mapreduce_sharded_ex(const smr_problem* problem, uint32_t local_ops);
  *     "self_release_max_total" (128 MiB: largest footprint of a whole sequence / of the recently written
  *     destinations).
  *   Sharding: "allreduce_f64" (0; 1: Float32 / ComplexF32 sums cross the ranks as Float64).
+ *   Groups: "group_max_bytes" (16 MiB: largest member, in algorithmic bytes, that a front end still defers into a group; read by the
+ *     front ends only: setting it keeps the plan cache).
  *   Debug builds with device-side wall-clock stamps (csrc/smr_device.h): "stamp_base" / "stamp_cap" /
  *     "stamp_used"; read-only "stamp_build".
  *   Read-only counters: "launches" (kernel launches the library issued, through HIP or directly),

@@ -82,6 +82,7 @@ EXPORTS = [
     "smr_comm_destroy", "smr_mapreduce_sharded", "smr_mapreduce_sharded_ex", "smr_shard", "smr_shard_ex", "smr_init_reduction", "smr_set_option",
     "smr_get_option", "smr_overlap_begin", "smr_overlap_end", "smr_overlap_fence", "smr_stream_create", "smr_stream_destroy",
     "smr_seq_create", "smr_seq_add", "smr_seq_run", "smr_seq_wait", "smr_seq_info", "smr_seq_components", "smr_seq_fences", "smr_seq_set", "smr_seq_destroy", "smr_debug_kernarg_layout", "smr_debug_canon_prog", "smr_debug_seq_schedule",
+    "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_destroy",
 ]
 
 
@@ -187,6 +188,15 @@ def load():
     lib.smr_seq_components.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t]
     lib.smr_seq_fences.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.smr_seq_destroy.argtypes = [C.c_void_p]
+    lib.smr_group_create.argtypes = [C.POINTER(smr_problem), C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.smr_group_prepare.argtypes = [C.c_void_p]
+    lib.smr_group_execute.argtypes = [C.c_void_p, C.c_void_p]
+    lib.smr_group_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    lib.smr_group_algorithmic_bytes.argtypes = [C.c_void_p]
+    lib.smr_group_algorithmic_bytes.restype = C.c_int64
+    lib.smr_group_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_size_t]
+    lib.smr_group_layout.restype = C.c_int64
+    lib.smr_group_destroy.argtypes = [C.c_void_p]
     if lib.smr_abi_version() != 1:
         raise ImportError("libstrided_hip.so ABI version mismatch; rebuild")
     _lib = lib
@@ -436,6 +446,61 @@ class Plan:
     def close(self):
         if self._h:
             self._lib.smr_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SMR_GROUP_INDEPENDENT = 1
+
+
+class Group:
+    """smr_group handle: K small independent maps (one f, one operand-type signature; rank, dims, strides, pointers and offsets
+    of their own) that execute as ONE kernel launch.  `problems` is a sequence of smr_problem; creating a group is host arithmetic
+    (no device).  `independent=True` passes SMR_GROUP_INDEPENDENT: the caller asserts that no member writes an element another
+    member reads or writes, and the byte-range check is skipped (interleaved blocks of one parent)."""
+
+    def __init__(self, problems, independent: bool = False, keepalive=()):
+        self._lib = load()
+        self._h = C.c_void_p()
+        self.count = len(problems)
+        arr = (smr_problem * max(1, self.count))()
+        for i, p in enumerate(problems):
+            C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(smr_problem))
+        self._keep = (arr, problems, keepalive)
+        check(self._lib.smr_group_create(arr, self.count, SMR_GROUP_INDEPENDENT if independent else 0, C.byref(self._h)))
+
+    def execute(self, stream: int | None = None):
+        check(self._lib.smr_group_execute(self._h, C.c_void_p(stream or 0)))
+
+    def prepare(self):
+        """Upload the device tables / compile + load the kernel of a runtime-compiled f, without launching."""
+        check(self._lib.smr_group_prepare(self._h))
+
+    def describe(self) -> str:
+        buf = C.create_string_buffer(1024)
+        check(self._lib.smr_group_describe(self._h, buf, 1024))
+        return buf.value.decode()
+
+    def layout(self):
+        """Per member (form, first workgroup, workgroups, canonical rank); form 0 = linear, 1 = transposing."""
+        n = int(self._lib.smr_group_layout(self._h, None, 0))
+        buf = (C.c_int64 * max(1, n))()
+        self._lib.smr_group_layout(self._h, buf, n)
+        v = list(buf)[:n]
+        return [tuple(v[i:i + 4]) for i in range(0, n, 4)]
+
+    @property
+    def algorithmic_bytes(self) -> int:
+        return int(self._lib.smr_group_algorithmic_bytes(self._h))
+
+    def close(self):
+        if self._h:
+            self._lib.smr_group_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

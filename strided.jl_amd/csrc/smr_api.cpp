@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "smr_dispatch.h"
+#include "smr_group.h"
 
 namespace smr {
 
@@ -93,13 +94,8 @@ Windows& windows() {
 void footprint(const Plan& plan, void* const* bases, std::vector<Span>& rd, std::vector<Span>& wr) {
     const Canon& c = plan.c;
     for (int k = 0; k < c.M; ++k) {
-        i64 lo = c.offsets[k], hi = c.offsets[k];
-        for (int d = 0; d < c.N; ++d) {
-            const i64 ext = (c.dims[d] - 1) * c.strides[k][d];
-            (ext < 0 ? lo : hi) += ext;
-        }
-        const uintptr_t b = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]);
-        const Span sp{b + (uintptr_t)(lo * (i64)c.esize[k]), b + (uintptr_t)((hi + 1) * (i64)c.esize[k])};
+        Span sp;
+        operand_span(c, k, bases ? bases[c.orig[k]] : c.base[k], sp.lo, sp.hi);
         if (k == 0) {
             wr.push_back(sp);
             if (c.redop != SMR_RED_NONE) rd.push_back(sp);  // reductions accumulate into the destination
@@ -197,7 +193,7 @@ unsigned long long* stamp_next(size_t waves) {
 }
 
 static bool g_device_checked = false;
-static int ensure_device() {
+int ensure_device() {
     if (g_device_checked) return SMR_OK;
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -910,6 +906,11 @@ int smr_set_option(const char* name, int64_t value) {
         (n == "stamp_base" ? o.stamp_base : (n == "stamp_cap" ? o.stamp_cap : o.stamp_used)) = value;
         return SMR_OK;
     }
+    if (n == "group_max_bytes") {  // read by the front ends only (smr_group.cpp): no plan depends on it either
+        if (value < 0) return set_error(SMR_EINVAL, "group_max_bytes must be >= 0");
+        group_max_bytes() = value;
+        return SMR_OK;
+    }
     if (i64 Options::*f = option_field(n)) o.*f = value;
     else if (const int d = tile_lg_dim(n); d >= 0) o.tile_lg[d] = value;
     else return set_error(SMR_EINVAL, "unknown option " + n);
@@ -933,6 +934,7 @@ int64_t smr_get_option(const char* name) {
     if (n == "stamp_cap") return o.stamp_cap;
     if (n == "stamp_used") return o.stamp_used;
     if (n == "stamp_build") return SMR_STAMP;
+    if (n == "group_max_bytes") return group_max_bytes();
     // read-only counters
     if (n == "launches") return g_launches.load();
     if (n == "jit_compiles") return jit_stats().compiles;

@@ -1,0 +1,314 @@
+// smr_group.cpp -- grouped launches (include/strided_hip.h: smr_group_*): the group planner and its C ABI.
+// A group is K independent small maps that share one functor f and one operand-type signature and differ in rank, dims, strides,
+// base pointers and offsets; smr_group_execute runs them as ONE launch of the kernel in smr_k_group.hip.  Planning is host
+// arithmetic: every member is canonicalised like a single call, checked against member 0, given one of the kernel's two bodies and
+// a contiguous range of workgroups.  The device tables are uploaded by smr_group_prepare or the first execution.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include "smr_dispatch.h"
+#include "smr_group.h"
+
+namespace smr {
+
+i64& group_max_bytes() {
+    // largest member (algorithmic bytes) the Python front still defers into a group.  16 MiB is the 32^4 Float64 row of
+    // profiles/group_launch.txt: the largest measured member at which one group of 8 beats the 8 single calls it replaces in the
+    // front (it beats a recorded sequence only from K = 32 small members on)
+    static i64 v = (i64)16 << 20;
+    return v;
+}
+
+namespace {
+
+std::string member_tag(int i) { return "smr_group_create: member " + std::to_string(i); }
+
+// does member `c` run the same kernel instantiation with the same functor as member 0 (`r`)?  Empty = yes, else what differs.
+std::string mismatch(const Canon& r, const Canon& c) {
+    if (c.bitcopy != r.bitcopy || (!c.bitcopy && c.ct != r.ct)) return "computes in another class than member 0";
+    if (c.mixed != r.mixed) return "differs from member 0 in whether operand types are converted";
+    if (c.M != r.M) return "has another number of distinct operands than member 0 (" + std::to_string(c.M) + " != " + std::to_string(r.M) + ")";
+    for (int k = 0; k < c.M; ++k) {
+        if (c.dtype[k] != r.dtype[k]) return "operand " + std::to_string(c.orig[k]) + " has another dtype than in member 0";
+        if (c.conj[k] != r.conj[k]) return "operand " + std::to_string(c.orig[k]) + " has another conj flag than in member 0";
+    }
+    const ProgD &p = c.prog, &q = r.prog;
+    if (p.len != q.len || p.nconst != q.nconst || std::memcmp(p.code, q.code, (size_t)(2 * p.len)) != 0 ||
+        std::memcmp(p.consts, q.consts, sizeof(double) * (size_t)(2 * p.nconst)) != 0)
+        return "has another f (program or constants) than member 0";
+    return std::string();
+}
+
+// picks the body of one member and fills its descriptor; returns its number of workgroups
+i64 plan_member(const Canon& c, GroupMemberD& m) {
+    std::memset(&m, 0, sizeof m);
+    m.N = c.N;
+    m.total = (uint32_t)c.total;
+    for (int k = 0; k < c.M; ++k) {
+        m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+        for (int d = 0; d < c.N; ++d) m.strides[k][d] = c.strides[k][d];
+    }
+    for (int d = 0; d < MAXN; ++d) m.dims[d] = d < c.N ? (uint32_t)c.dims[d] : 1u;
+    {   // 256 in the mixed radix of the dims (what does not fit is beyond the box and never reached)
+        i64 rem = 256;
+        for (int d = 0; d < c.N; ++d) {
+            m.step[d] = (uint32_t)(rem % c.dims[d]);
+            rem /= c.dims[d];
+        }
+    }
+    // inputs whose unit-stride dim is another one than the destination's fastest dim (canonical dim 0)
+    int ntransposed = 0, kt = 0, q = 0;
+    for (int k = 1; k < c.M; ++k) {
+        const i64 s0 = c.strides[k][0] < 0 ? -c.strides[k][0] : c.strides[k][0];
+        if (s0 <= 1) continue;  // unit-stride or broadcast along dim 0
+        for (int d = 1; d < c.N; ++d)
+            if (c.strides[k][d] == 1 || c.strides[k][d] == -1) {
+                ++ntransposed;
+                kt = k;
+                q = d;
+                break;
+            }
+    }
+    if (ntransposed == 1 && c.dims[0] >= GROUP_TMIN && c.dims[q] >= GROUP_TMIN) {
+        m.form = 1;
+        m.kt = kt;
+        m.q = q;
+        m.tbase = m.base[kt];
+        m.tsp = c.strides[kt][0];
+        m.tsq = c.strides[kt][q];
+        m.tdtype = c.dtype[kt];
+        m.tconj = c.conj[kt];
+        for (int k = 0; k < c.M; ++k) m.qstride[k] = c.strides[k][q];
+        m.ntp = (uint32_t)((c.dims[0] + GROUP_TILE - 1) / GROUP_TILE);
+        m.ntq = (uint32_t)((c.dims[q] + GROUP_TILE - 1) / GROUP_TILE);
+        i64 wgs = (i64)m.ntp * m.ntq;
+        for (int d = 1; d < c.N; ++d)
+            if (d != q) wgs *= c.dims[d];
+        return wgs;
+    }
+    m.form = 0;
+    return (c.total + GROUP_CHUNK - 1) / GROUP_CHUNK;
+}
+
+// Independence: no member's destination range may meet a range of ANOTHER member.  One sweep over the ranges sorted by their
+// start: a range meets an earlier one iff that one ends behind its start, so the two furthest-reaching ends seen so far (of
+// different members) decide -- among all ranges for a destination, among the destinations for an input.
+struct Range {
+    uintptr_t lo, hi;
+    int member;
+    bool write;
+};
+struct Reach {  // the furthest ends seen so far, of two different members
+    uintptr_t hi[2] = {0, 0};
+    int member[2] = {-1, -1};
+    void add(uintptr_t h, int mem) {
+        if (mem == member[0]) hi[0] = std::max(hi[0], h);
+        else if (member[0] < 0 || h > hi[0]) {
+            if (member[0] >= 0) { hi[1] = hi[0]; member[1] = member[0]; }
+            hi[0] = h;
+            member[0] = mem;
+        } else if (mem == member[1]) hi[1] = std::max(hi[1], h);
+        else if (member[1] < 0 || h > hi[1]) { hi[1] = h; member[1] = mem; }
+    }
+    // a member other than `mem` whose range ends behind `lo`, or -1
+    int meets(uintptr_t lo, int mem) const {
+        for (int i = 0; i < 2; ++i)
+            if (member[i] >= 0 && member[i] != mem && hi[i] > lo) return member[i];
+        return -1;
+    }
+};
+
+int check_independent(std::vector<Range>& rs) {
+    std::sort(rs.begin(), rs.end(), [](const Range& a, const Range& b) { return a.lo != b.lo ? a.lo < b.lo : a.member < b.member; });
+    Reach all, writes;
+    for (const Range& r : rs) {
+        const int other = (r.write ? all : writes).meets(r.lo, r.member);
+        if (other >= 0) {
+            const int wm = r.write ? r.member : other, om = r.write ? other : r.member;
+            return set_error(SMR_EUNSUPPORTED, member_tag(std::max(wm, om)) + ": the destination's byte range of member " + std::to_string(wm) +
+                                                   " meets a byte range of member " + std::to_string(om) +
+                                                   " (pass SMR_GROUP_INDEPENDENT if no element is shared, e.g. interleaved blocks of one parent)");
+        }
+        all.add(r.hi, r.member);
+        if (r.write) writes.add(r.hi, r.member);
+    }
+    return SMR_OK;
+}
+
+int launch_group(const GroupPlan& g, hipStream_t s) {
+    switch (g.c.bitcopy ? SMR_F32 : g.c.ct) {
+        case SMR_F32: return launch_group_ct<SMR_F32>(g, s);
+        case SMR_F64: return launch_group_ct<SMR_F64>(g, s);
+        case SMR_C32: return launch_group_ct<SMR_C32>(g, s);
+        case SMR_C64: return launch_group_ct<SMR_C64>(g, s);
+        case SMR_I64: return launch_group_ct<SMR_I64>(g, s);
+    }
+    return set_error(SMR_EINVAL, "bad compute class");
+}
+
+int ensure_tables(const GroupPlan& g) {
+    std::lock_guard<std::mutex> lk(g.build_mu);
+    if (!g.d_members) {
+        if (int rc = upload_table(&g.d_members, g.members.data(), g.members.size() * sizeof(GroupMemberD), "group members")) return rc;
+    }
+    if (!g.d_first) {
+        if (int rc = upload_table(&g.d_first, g.first_wg.data(), g.first_wg.size() * sizeof(uint32_t), "group workgroup ranges")) return rc;
+    }
+    return SMR_OK;
+}
+
+const char* functor_name(const Canon& c) {
+    if (c.bitcopy) return "bitcopy";
+    static const char* names[FK_COUNT] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
+    const int k = (!c.mixed && (GROUP_FMASK & fbit(c.fkind))) ? c.fkind : FK_PROG;
+    return names[k];
+}
+
+}  // namespace
+}  // namespace smr
+
+using namespace smr;
+
+struct smr_group {
+    GroupPlan plan;
+    void* stream = nullptr;  // of member 0: drained before the tables are freed
+};
+
+extern "C" {
+
+int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
+    if (!members || !out) return set_error(SMR_EINVAL, "smr_group_create: null argument");
+    if (count < 1 || count > 65535) return set_error(SMR_EINVAL, "smr_group_create: count must be 1..65535");
+    if (flags & ~SMR_GROUP_INDEPENDENT) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
+    smr_group* h = new (std::nothrow) smr_group();
+    if (!h) return set_error(SMR_ENOMEM, "out of host memory");
+    GroupPlan& g = h->plan;
+    g.members.resize((size_t)count);
+    g.first_wg.assign((size_t)count + 1, 0);
+    g.rank.resize((size_t)count);
+    std::vector<Range> ranges;
+    i64 grid = 0;
+    int rc = SMR_OK;
+    for (int i = 0; i < count && rc == SMR_OK; ++i) {
+        const smr_problem& p = members[i];
+        if (p.redop != SMR_RED_NONE) {
+            rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction; a group holds maps only");
+            break;
+        }
+        Canon ci;
+        Canon& c = i == 0 ? g.c : ci;
+        rc = canonicalise(&p, c);
+        if (rc) {
+            rc = set_error(rc, member_tag(i) + ": " + smr_last_error());
+            break;
+        }
+        if (i > 0) {
+            const std::string why = mismatch(g.c, c);
+            if (!why.empty()) {
+                rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
+                break;
+            }
+        }
+        if (c.total > 0x7fffffffLL) {
+            rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " has more than 2^31 - 1 box elements");
+            break;
+        }
+        const i64 wgs = plan_member(c, g.members[(size_t)i]);
+        g.rank[(size_t)i] = c.N;
+        (g.members[(size_t)i].form ? g.ntrans : g.nlinear) += 1;
+        grid += wgs;
+        if (grid > 0x7fffffffLL) {
+            rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + ": the group needs more than 2^31 - 1 workgroups");
+            break;
+        }
+        g.first_wg[(size_t)i + 1] = (uint32_t)grid;
+        g.algbytes += c.algbytes;
+        if (!(flags & SMR_GROUP_INDEPENDENT))
+            for (int k = 0; k < c.M; ++k) {
+                Range r;
+                operand_span(c, k, c.base[k], r.lo, r.hi);
+                r.member = i;
+                r.write = k == 0;
+                ranges.push_back(r);
+            }
+    }
+    if (rc == SMR_OK && !(flags & SMR_GROUP_INDEPENDENT)) rc = check_independent(ranges);
+    if (rc) {
+        delete h;
+        return rc;
+    }
+    h->stream = members[0].stream;
+    // what launch_group_ct() does: with_prog (runtime compilation first) for a mixed group and for an f without a native functor.
+    // FK_PROG has a bit in GROUP_FMASK like every kind, so the mask alone does not tell
+    g.jit = options().jit && !g.c.bitcopy && (g.c.mixed || g.c.fkind == FK_PROG || !(GROUP_FMASK & fbit(g.c.fkind)));
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "family=group members=%d grid=%lld linear=%d transposing=%d f=%s jit=%d bytes=%lld%s", count, (long long)grid,
+                  g.nlinear, g.ntrans, functor_name(g.c), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "");
+    g.desc = buf;
+    *out = h;
+    return SMR_OK;
+}
+
+int smr_group_prepare(smr_group* g) {
+    if (!g) return set_error(SMR_EINVAL, "null group");
+    int rc = ensure_device();
+    if (rc) return rc;
+    rc = ensure_tables(g->plan);
+    if (rc) return rc;
+    jit_set_prepare(true);
+    rc = launch_group(g->plan, (hipStream_t)g->stream);
+    jit_set_prepare(false);
+    return rc;
+}
+
+int smr_group_execute(smr_group* g, void* stream) {
+    if (!g) return set_error(SMR_EINVAL, "null group");
+    int rc = ensure_device();
+    if (rc) return rc;
+    rc = ensure_tables(g->plan);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)(stream ? stream : g->stream);
+    // the launch goes through HIP: on a library-owned stream it is foreign work (what the library submitted directly completes first,
+    // and the stream's next direct launch drains it)
+    rc = fence_for_foreign_work(s);
+    if (rc) return rc;
+    return launch_group(g->plan, s);
+}
+
+int smr_group_describe(const smr_group* g, char* buf, size_t buflen) {
+    if (!g || !buf || buflen == 0) return set_error(SMR_EINVAL, "null argument");
+    std::snprintf(buf, buflen, "%s", g->plan.desc.c_str());
+    return SMR_OK;
+}
+
+int64_t smr_group_algorithmic_bytes(const smr_group* g) { return g ? g->plan.algbytes : 0; }
+
+int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap) {
+    if (!g) return 0;
+    const GroupPlan& p = g->plan;
+    const size_t n = p.members.size();
+    if (out)
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t v[4] = {p.members[i].form, p.first_wg[i], (int64_t)p.first_wg[i + 1] - (int64_t)p.first_wg[i], p.rank[i]};
+            for (size_t j = 0; j < 4; ++j)
+                if (4 * i + j < cap) out[4 * i + j] = v[j];
+        }
+    return (int64_t)(4 * n);
+}
+
+int smr_group_destroy(smr_group* g) {
+    if (!g) return SMR_OK;
+    if (g->plan.d_members || g->plan.d_first) {
+        (void)eager_fence_if_active();
+        (void)hipDeviceSynchronize();  // a queued launch may still read the tables
+        if (g->plan.d_members) (void)hipFree(g->plan.d_members);
+        if (g->plan.d_first) (void)hipFree(g->plan.d_first);
+        (void)hipGetLastError();
+    }
+    delete g;
+    return SMR_OK;
+}
+
+}  // extern "C"

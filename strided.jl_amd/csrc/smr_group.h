@@ -1,0 +1,70 @@
+// smr_group.h -- grouped launches (smr_group_*): K independent small maps, each with its own rank, dims, strides, pointers and
+// offsets, run as ONE kernel launch (smr_k_group.hip).  Shared by the group planner / C ABI (smr_group.cpp) and the kernel's
+// translation units; the top part is also compiled by hiprtc (SMR_JIT).
+#pragma once
+
+#include "smr_internal.h"
+
+namespace smr {
+
+constexpr int GROUP_U = 4;                   // linear form: elements per lane
+constexpr int GROUP_CHUNK = 256 * GROUP_U;   // ... canonical indices per workgroup
+constexpr int GROUP_TILE = 32;               // transposing form: tile edge (staged through GROUP_TILE x (GROUP_TILE + 1) elements of LDS)
+constexpr int GROUP_TMIN = 16;               // transposing form only when both tiled dims are at least this long (a 32 x 32 tile is then >= 1/4 full)
+
+// One member of a group as the kernel reads it (device table, one entry per member).  Everything in it is wave-uniform.
+struct GroupMemberD {
+    void* base[MAXM];            // operand addresses, element offsets folded in
+    i64 strides[MAXM][MAXN];     // canonical strides (elements)
+    i64 qstride[MAXM];           // transposing form: every operand's stride along dim q
+    void* tbase;                 // transposing form: the staged input's address ...
+    i64 tsp, tsq;                // ... and its strides along dim 0 and dim q (tsq = +-1)
+    uint32_t dims[MAXN];         // canonical dims (a member has at most 2^31 - 1 box elements)
+    uint32_t step[MAXN];         // linear form: the mixed-radix digits of 256 over `dims` (a lane's step between its elements)
+    uint32_t total;              // box elements
+    int32_t N;                   // canonical rank
+    int32_t form;                // 0 linear, 1 transposing
+    int32_t kt, q;               // transposing form: staged input (1..M-1), canonical dim along which it is unit-stride
+    int32_t tdtype, tconj;       // ... its dtype / conj flag
+    uint32_t ntp, ntq;           // ... tiles along dim 0 and along dim q
+};
+
+#ifndef SMR_JIT
+// every recognised functor of f has a natively compiled group kernel (the same functor code a single call runs); any other f is
+// runtime-compiled, or interpreted, as in GENERIC
+constexpr unsigned GROUP_FMASK = 0xffffffffu;
+
+// A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member.
+struct GroupPlan {
+    Canon c;
+    std::vector<GroupMemberD> members;
+    std::vector<uint32_t> first_wg;   // count + 1 prefix sums of the members' workgroups
+    std::vector<int> rank;            // canonical rank per member (smr_group_layout)
+    int nlinear = 0, ntrans = 0;
+    bool jit = false;                 // f runs as a runtime-compiled functor
+    i64 algbytes = 0;
+    std::string desc;
+    // device copies of `members` and `first_wg`, uploaded by prepare / the first execution
+    mutable std::mutex build_mu;
+    mutable void* d_members = nullptr;
+    mutable void* d_first = nullptr;
+};
+
+template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);
+
+int ensure_device();     // smr_api.cpp
+i64& group_max_bytes();  // option "group_max_bytes" (smr_group.cpp)
+
+// Bounding byte range [lo, hi) of operand k of a canonical problem: what footprint() (smr_api.cpp) and the group planner compare.
+inline void operand_span(const Canon& c, int k, const void* base, uintptr_t& lo_out, uintptr_t& hi_out) {
+    i64 lo = c.offsets[k], hi = c.offsets[k];
+    for (int d = 0; d < c.N; ++d) {
+        const i64 ext = (c.dims[d] - 1) * c.strides[k][d];
+        (ext < 0 ? lo : hi) += ext;
+    }
+    lo_out = (uintptr_t)base + (uintptr_t)(lo * (i64)c.esize[k]);
+    hi_out = (uintptr_t)base + (uintptr_t)((hi + 1) * (i64)c.esize[k]);
+}
+#endif  // !SMR_JIT
+
+}  // namespace smr

@@ -9,6 +9,7 @@ argument checking happens before the funnel, with the reference's error types
 """
 from __future__ import annotations
 
+import builtins
 import collections
 import ctypes as C
 import operator
@@ -270,6 +271,11 @@ def _mapreduce_fuse_(f, op, initop, dims, arrays):
             raise RuntimeError(
                 "strided_jl_amd computes on MI355X only: every StridedView must wrap a torch tensor on a "
                 "HIP device (host views are for the test oracle; there is no CPU fallback)")
+    g = _GROUP.cur
+    if g is not None:  # inside `with S.group():` -- maps are deferred, anything else runs after what is pending
+        if op is None and g.defer(f, dims, arrays):
+            return arrays[0]
+        g.flush()
     if _SMR_MAPREDUCE is None:
         _SMR_MAPREDUCE = L.load().smr_mapreduce
     key = _problem_key(f, op, initop, dims, arrays)
@@ -303,6 +309,192 @@ def _mapreduce_fuse_(f, op, initop, dims, arrays):
                     break
     L.check(_SMR_MAPREDUCE(C.byref(p)))
     return arrays[0]
+
+
+# ---- grouped launches: `with S.group():` ------------------------------------------------------------------
+class _GroupState(threading.local):
+    """Per thread: the innermost enclosing `with S.group():` block (None outside one)."""
+
+    def __init__(self):
+        self.cur = None
+
+
+_GROUP = _GroupState()
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, stream); least recently used first
+
+
+def _byte_range(a):
+    """[lo, hi) in bytes of the bounding range of a view (what the library compares: csrc/smr_group.h operand_span)."""
+    lo = hi = a.offset
+    for d, st in zip(a.size, a.strides):
+        e = (d - 1) * st
+        if e < 0:
+            lo += e
+        else:
+            hi += e
+    isz = a.dtype.itemsize
+    return a._base + lo * isz, a._base + (hi + 1) * isz
+
+
+def _view_id(a):
+    return (a._base, a.offset, a.size, a.strides)
+
+
+def _member_bytes(arrays):
+    """Algorithmic bytes of one call the way the library counts them (every distinct buffer once, csrc/smr_canon.cpp)."""
+    foot = {}
+    for a in arrays:
+        n = 1
+        for d, st in zip(a.size, a.strides):
+            if st != 0:
+                n *= d
+        foot[a._base] = max(foot.get(a._base, 0), n * a.dtype.itemsize)
+    return builtins.sum(foot.values())  # (this module defines its own `sum`)
+
+
+class _Deferred:
+    __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key")
+
+
+class group:
+    """`with S.group(independent=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
+    `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, stream) becomes ONE
+    kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
+      * a call whose byte ranges conflict with a pending call (it writes what one reads or writes, or reads what one writes) first
+        flushes everything pending.  With `independent=True` only exact same-view conflicts count -- the caller asserts that
+        different views share no element, which is what lets interleaved blocks of one parent array share a launch;
+      * reductions, members above option "group_max_bytes" and host reads (`toarray`, `item`, `Array`) flush what is pending and
+        then run as usual;
+      * a bucket the library refuses as a group (smr_group_create: SMR_EUNSUPPORTED) runs call by call through the normal path;
+        an error a single call would have raised at once is raised at the flush instead.
+    `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
+
+    MAX_PENDING = 4096
+
+    def __init__(self, independent: bool = False):
+        self.independent = bool(independent)
+        self.pending = []
+        self.groups = []
+        self.singles = 0
+        self._outer = None
+
+    def __enter__(self):
+        self._outer = _GROUP.cur
+        if self._outer is not None:
+            self._outer.flush()
+        _GROUP.cur = self
+        return self
+
+    def __exit__(self, *exc):
+        try:
+            self.flush()
+        finally:
+            _GROUP.cur = self._outer
+        return False
+
+    # -- deferring ------------------------------------------------------------------------------------------
+    def _conflicts(self, c):
+        if self.independent:
+            w = _view_id(c.arrays[0])
+            for q in self.pending:
+                ids = [_view_id(a) for a in q.arrays]
+                if w in ids or ids[0] in [_view_id(a) for a in c.arrays[1:]]:
+                    return True
+            return False
+        for q in self.pending:
+            for lo, hi in [q.wr] + q.rd:
+                if c.wr[0] < hi and lo < c.wr[1]:
+                    return True
+            for lo, hi in c.rd:
+                if lo < q.wr[1] and q.wr[0] < hi:
+                    return True
+        return False
+
+    def defer(self, f, dims, arrays) -> bool:
+        """Takes one map call (destination first).  False: the call is not eligible (too large, too many operands) -- the caller
+        flushes and runs it through the normal path."""
+        arrays = tuple(arrays)
+        if len(arrays) < 2 or len(arrays) > L.SMR_MAXM or len(dims) > L.SMR_MAXN:
+            return False
+        if _member_bytes(arrays) > L.get_option("group_max_bytes"):
+            return False
+        c = _Deferred()
+        c.f, c.dims, c.arrays = f, tuple(int(d) for d in dims), arrays
+        c.stream = _current_stream()
+        dts = tuple(np.dtype(a.dtype) for a in arrays)
+        code, consts = _serialized(f, len(arrays), dts)
+        c.bucket = (bytes(code), tuple(consts), tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), c.stream)
+        c.wr = _byte_range(arrays[0])
+        c.rd = [_byte_range(a) for a in arrays[1:]]
+        c.key = _problem_key(f, None, None, c.dims, arrays)
+        if self.pending and (len(self.pending) >= self.MAX_PENDING or self._conflicts(c)):
+            self.flush()
+        self.pending.append(c)
+        return True
+
+    # -- launching --------------------------------------------------------------------------------------------
+    def flush(self):
+        """Launches everything pending: one group per bucket, buckets in order of their first call."""
+        calls, self.pending = self.pending, []
+        buckets = {}
+        for c in calls:
+            buckets.setdefault(c.bucket, []).append(c)
+        for members in buckets.values():
+            self._launch(members, members[0].stream)
+
+    def _launch(self, calls, stream):
+        key = None
+        if all(c.key is not None for c in calls):
+            key = (tuple(c.key for c in calls), self.independent, stream)
+        grp = None
+        if key is not None:
+            try:
+                grp = _GROUP_CACHE.get(key)
+            except TypeError:
+                key = None
+        if grp is None:
+            built = [build_problem(c.f, None, None, c.dims, c.arrays, stream=stream) for c in calls]
+            try:
+                # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
+                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built])
+            except L.UnsupportedOnDevice:
+                for c in calls:
+                    self._single(c)
+                return
+            if key is not None:
+                _GROUP_CACHE[key] = grp
+                while len(_GROUP_CACHE) > 256:
+                    try:
+                        _GROUP_CACHE.popitem(last=False)
+                    except KeyError:
+                        break
+        else:
+            try:
+                _GROUP_CACHE.move_to_end(key)
+            except KeyError:
+                pass
+        grp.execute(stream)
+        self.groups.append(grp)
+
+    def _single(self, c):
+        cur, _GROUP.cur = _GROUP.cur, None
+        try:
+            self.singles += 1
+            if c.stream != _current_stream():
+                p, keep = build_problem(c.f, None, None, c.dims, c.arrays, stream=c.stream)
+                L.check(L.load().smr_mapreduce(C.byref(p)))
+            else:
+                _mapreduce_fuse_(c.f, None, None, c.dims, c.arrays)
+        finally:
+            _GROUP.cur = cur
+
+
+def flush_group():
+    """Launches what the enclosing `with S.group():` block (if any) has pending: called before the host reads device memory."""
+    g = _GROUP.cur
+    if g is not None:
+        g.flush()
 
 
 def make_plan(f, op, initop, dims, arrays) -> L.Plan:
@@ -496,5 +688,6 @@ def Array(a: StridedView, dtype=None) -> np.ndarray:
     b = a.similar(dtype or a.dtype)
     if len(a) > 0:
         copy_(b, a)
+    flush_group()
     host = b.parent.cpu().numpy()
     return host.reshape(a.size, order="F")

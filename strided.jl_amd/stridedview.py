@@ -284,7 +284,9 @@ class StridedView:
             import torch
             # inside `with S.Stream():` the launches went to a library-owned stream, which torch's streams are not ordered against:
             # finish it before torch gathers (found by tools/fuzz_more.py OWN_STREAM=1, whose harness read stale results)
-            own = importlib.import_module(".mapreduce", __package__)._STREAM_OVERRIDE.stack
+            mr = importlib.import_module(".mapreduce", __package__)
+            mr.flush_group()  # maps deferred by an enclosing `with S.group():` block
+            own = mr._STREAM_OVERRIDE.stack
             if own:
                 L.check(L.load().smr_stream_sync(ctypes.c_void_p(own[-1])))
             p = self.parent.detach()

@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""K small permutedims! calls issued three ways, warm, on one MI355X:
+
+  (a) single   K plan executions one by one on a HIP stream (what a loop over blocks does today)
+  (b) sequence the same K plans recorded into a Sequence and replayed by the library (default 4 queues)
+  (c) group    ONE launch of a group of the K members (smr_group_*, csrc/smr_k_group.hip)
+
+Every member is a Float64 array of its own, permuted with the reversal permutation into an array of its own.  A round times
+`reps` executions of each form between device synchronisations with the host clock (so launch cost on the host counts, as it does
+for a user); rounds alternate the three forms, the table gives the median over the rounds and the spread (min..max) in us per
+execution of all K members.  The results of (c) are compared bit for bit with those of (a) before anything is timed.
+
+    python tools/group_vs_single.py [--rounds 7] [--target-ms 250] [--out profiles/group_launch.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import strided_jl_amd as S  # noqa: E402
+from strided_jl_amd import _lib as L  # noqa: E402
+
+SHAPES = [((8,) * 4, (2, 8, 32, 128)), ((16,) * 4, (2, 8, 32, 128)), ((4,) * 8, (2, 8, 32, 128)), ((32,) * 4, (8,))]
+
+
+def dview(t, shape):
+    st, s = [], 1
+    for d in shape:
+        st.append(s)
+        s *= d
+    return S.StridedView(t, shape, tuple(st), 0)
+
+
+def timed(fn, reps, sync):
+    sync()
+    t0 = time.perf_counter()
+    fn(reps)
+    sync()
+    return (time.perf_counter() - t0) / reps * 1e6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--target-ms", type=float, default=250.0, help="length of one timed window")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("group_vs_single.py needs the MI355X: nothing is measured without it")
+    sync = torch.cuda.synchronize
+    stream = int(torch.cuda.current_stream().cuda_stream)
+    lines = ["# %s, %d rounds of >= %.0f ms per form, us per execution of all K members: median (min..max)" %
+             (torch.cuda.get_device_name(0), args.rounds, args.target_ms),
+             "# member = permutedims!(dst, src, reverse) of a Float64 array; bytes = algorithmic bytes of one member",
+             "%-8s %9s %4s  %-26s %-26s %-26s %s" % ("shape", "bytes", "K", "(a) single", "(b) sequence", "(c) group", "group wins")]
+    wins = []
+    for shape, ks in SHAPES:
+        n = int(np.prod(shape))
+        perm = tuple(reversed(range(len(shape))))
+        for K in ks:
+            src = [dview(torch.randn(n, dtype=torch.float64, device="cuda"), shape) for _ in range(K)]
+            dst = [dview(torch.zeros(n, dtype=torch.float64, device="cuda"), shape) for _ in range(K)]
+            dst2 = [dview(torch.zeros(n, dtype=torch.float64, device="cuda"), shape) for _ in range(K)]
+            plans = [S.make_plan(lambda x: x, None, None, shape, (d, s.permutedims(perm))) for d, s in zip(dst, src)]
+            built = [S.build_problem(lambda x: x, None, None, shape, (d, s.permutedims(perm)), stream=stream) for d, s in zip(dst2, src)]
+            grp = L.Group([b[0] for b in built], keepalive=built)
+            seq = S.Sequence()
+            for p in plans:
+                seq.add(p)
+            sync()
+
+            def single(reps):
+                for _ in range(reps):
+                    for p in plans:
+                        p.execute(stream)
+
+            def sequence(reps):
+                seq.run(reps, stream)
+                seq.wait()
+
+            def group(reps):
+                for _ in range(reps):
+                    grp.execute(stream)
+
+            forms = (single, sequence, group)
+            for f in forms:  # warm: code objects, tables, packets
+                f(3)
+            sync()
+            for d, e in zip(dst, dst2):
+                assert torch.equal(d.parent, e.parent), "group result differs from the single calls"
+            reps = []
+            for f in forms:  # size every window from a short probe
+                t = timed(f, 5, sync)
+                reps.append(max(5, int(args.target_ms * 1e3 / max(t, 0.5))))
+            samples = [[], [], []]
+            for _ in range(args.rounds):
+                for i, f in enumerate(forms):
+                    samples[i].append(timed(f, reps[i], sync))
+            med = [statistics.median(x) for x in samples]
+            cell = ["%8.2f (%.2f..%.2f)" % (m, min(x), max(x)) for m, x in zip(med, samples)]
+            win = med[2] < med[0] and med[2] < med[1]
+            wins.append((shape, K, 2 * n * 8, win, med[2] < med[0]))
+            lines.append("%-8s %9d %4d  %-26s %-26s %-26s %s" % ("%d^%d" % (shape[0], len(shape)), 2 * n * 8, K, *cell, "yes" if win else "no"))
+            print(lines[-1], flush=True)
+            del plans, grp, seq
+    lines.append("")
+    won = [(s, k, b) for s, k, b, w, _ in wins if w]
+    if won:
+        lines.append("# crossover: (c) beats both (a) and (b) at " + ", ".join("%d^%d K=%d" % (s[0], len(s), k) for s, k, _ in won))
+        at8 = [b for s, k, b in won if k == 8]
+        lines.append("# largest member at which (c) beats both at K = 8: " + ("%d bytes" % max(at8) if at8 else "none"))
+    else:
+        lines.append("# (c) does not beat both (a) and (b) at any row of this table")
+    # the front replaces single calls, never a recorded sequence: the default of option group_max_bytes comes from this line
+    a8 = [b for s, k, b, _, wa in wins if wa and k == 8]
+    lines.append("# largest member at which (c) beats (a) at K = 8: " + ("%d bytes" % max(a8) if a8 else "none"))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
