@@ -277,8 +277,14 @@ int smr_overlap_fence(void* stream);
 int smr_stream_create(void** out);
 int smr_stream_destroy(void* stream);
 
-/* ---- recorded sequences: the library's own replay of a list of plan executions ---------------------
+/* ---- recorded sequences: the library's own replay of a list of plan and group executions ----------
  * smr_seq_add records executions of plans (with optional rebinding of base pointers, as smr_plan_execute);
+ * smr_seq_add_group records one execution of a group (smr_group_*, below: K small maps as one launch) -- a sequence may mix
+ * both kinds in any order, and a group is ONE step of the list: one packet per replay, no host call per execution.  Its footprint
+ * is the union of its members' operand ranges (reads: every input; writes: every destination; kept merged by smr_group_create,
+ * also under SMR_GROUP_INDEPENDENT, where they are the conservative bounding ranges).  A group's base pointers are fixed (no
+ * rebinding) and the group must outlive the sequence.  Its workgroups are independent, so a component that is one group launch
+ * can be cut into block ranges over several queues ("slices" below), runtime-compiled f included.
  * smr_seq_run(seq, reps, stream) performs the recorded list `reps` times with the results of in-order
  * execution on `stream`.  On MI355X the replay does not go through HIP's launch path: every launch
  * becomes a pre-built AQL dispatch packet (kernel object of the code object HIP loaded, kernarg block
@@ -314,6 +320,8 @@ int smr_stream_destroy(void* stream);
 typedef struct smr_seq smr_seq;
 int smr_seq_create(smr_seq** out);
 int smr_seq_add(smr_seq* seq, smr_plan* plan, void* const* bases);
+struct smr_group;
+int smr_seq_add_group(smr_seq* seq, struct smr_group* group);
 int smr_seq_run(smr_seq* seq, int reps, void* stream);
 int smr_seq_wait(smr_seq* seq);
 int smr_seq_info(smr_seq* seq, char* buf, size_t buflen);
@@ -446,7 +454,8 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * an execute into a hipGraph).  smr_group_execute is ONE kernel launch, asynchronous on `stream` (NULL = the stream of member 0);
  * its result is bit-identical to smr_mapreduce on each member in order.  The launch goes through HIP; on a library-owned stream
  * (smr_stream_create) it is ordered behind the library's direct launches and the stream's next direct launch waits for it.  The base
- * pointers are fixed at creation (no rebinding), and a group cannot be recorded into a sequence.
+ * pointers are fixed at creation (no rebinding).  A caller that executes the same group again and again records it into a sequence
+ * (smr_seq_add_group): the replay is then one pre-built packet instead of one launch through HIP.
  * smr_group_describe: one line, "family=group members=K grid=G linear=a transposing=b f=<functor> jit=0/1 bytes=...".
  * smr_group_layout: per member 4 values -- form (0 linear, 1 transposing), first workgroup, workgroups, canonical rank; returns
  * 4 * count and writes min(that, cap) values.  The members' workgroup ranges tile [0, grid) in member order.                     */

@@ -81,7 +81,7 @@ EXPORTS = [
     "smr_plan_describe", "smr_plan_algorithmic_bytes", "smr_plan_tile_order", "smr_plan_orbit_pairs", "smr_plan_flat_runs", "smr_plan_flat_side", "smr_plan_flat_batched", "smr_mapreduce_scalar", "smr_plan_jit_compile", "smr_plan_jit_source", "smr_plan_prepare", "smr_comm_unique_id", "smr_comm_init", "smr_comm_rank", "smr_comm_library",
     "smr_comm_destroy", "smr_mapreduce_sharded", "smr_mapreduce_sharded_ex", "smr_shard", "smr_shard_ex", "smr_init_reduction", "smr_set_option",
     "smr_get_option", "smr_overlap_begin", "smr_overlap_end", "smr_overlap_fence", "smr_stream_create", "smr_stream_destroy",
-    "smr_seq_create", "smr_seq_add", "smr_seq_run", "smr_seq_wait", "smr_seq_info", "smr_seq_components", "smr_seq_fences", "smr_seq_set", "smr_seq_destroy", "smr_debug_kernarg_layout", "smr_debug_canon_prog", "smr_debug_seq_schedule",
+    "smr_seq_create", "smr_seq_add", "smr_seq_add_group", "smr_seq_run", "smr_seq_wait", "smr_seq_info", "smr_seq_components", "smr_seq_fences", "smr_seq_set", "smr_seq_destroy", "smr_debug_kernarg_layout", "smr_debug_canon_prog", "smr_debug_seq_schedule",
     "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_destroy",
 ]
 
@@ -181,6 +181,7 @@ def load():
     lib.smr_stream_destroy.argtypes = [C.c_void_p]
     lib.smr_seq_create.argtypes = [C.POINTER(C.c_void_p)]
     lib.smr_seq_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.smr_seq_add_group.argtypes = [C.c_void_p, C.c_void_p]
     lib.smr_seq_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.smr_seq_wait.argtypes = [C.c_void_p]
     lib.smr_seq_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
@@ -274,8 +275,9 @@ class Stream:
 
 
 class Sequence:
-    """smr_seq: a recorded list of plan executions, replayed by the library itself (on MI355X as pre-built AQL packets on its
-    own HSA queue; independent launches overlap on the device) with the results of in-order execution on `stream`."""
+    """smr_seq: a recorded list of plan executions (`add`) and group executions (`add_group`), replayed by the library itself (on
+    MI355X as pre-built AQL packets on its own HSA queue; independent launches overlap on the device) with the results of in-order
+    execution on `stream`.  A group is one step of the list and one packet of a replay."""
 
     def __init__(self):
         self._lib = load()
@@ -289,6 +291,12 @@ class Sequence:
             arr = (C.c_void_p * len(bases))(*bases)
         check(self._lib.smr_seq_add(self._h, plan._h, arr))
         self._keep.append(plan)
+        return self
+
+    def add_group(self, group: "Group"):
+        """Records one execution of `group` (smr_seq_add_group); the sequence keeps the group alive."""
+        check(self._lib.smr_seq_add_group(self._h, group._h))
+        self._keep.append(group)
         return self
 
     def run(self, reps: int = 1, stream: int | None = None):
@@ -306,7 +314,7 @@ class Sequence:
         check(self._lib.smr_seq_set(self._h, name.encode(), int(value)))
 
     def components(self):
-        """Dependency component of every recorded execution (host-only analysis: works without a device)."""
+        """Dependency component of every recorded execution, plan or group (host-only analysis: works without a device)."""
         n = len(self._keep)
         buf = (C.c_int32 * max(1, n))()
         rc = self._lib.smr_seq_components(self._h, buf, n)

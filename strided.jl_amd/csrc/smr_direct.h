@@ -22,6 +22,9 @@ namespace smr {
 int seq_execute_plan(smr_plan* plan, void* const* bases, hipStream_t s, bool prepare_only);
 void seq_footprint(smr_plan* plan, void* const* bases, std::vector<std::pair<uintptr_t, uintptr_t>>& rd, std::vector<std::pair<uintptr_t, uintptr_t>>& wr);
 int seq_nops(smr_plan* plan);
+// smr_group.cpp: a recorded group execution (one launch; the footprint is the merged byte ranges of all members, kept by the planner)
+int seq_execute_group(smr_group* group, hipStream_t s, bool prepare_only);
+void seq_footprint_group(smr_group* group, Spans& rd, Spans& wr);
 bool seq_stream_is_owned(hipStream_t s);
 
 // ---- the HSA runtime HIP already loaded (never a second copy) ------------------------------------------------------------------

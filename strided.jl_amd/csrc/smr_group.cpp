@@ -2,12 +2,14 @@
 // A group is K independent small maps that share one functor f and one operand-type signature and differ in rank, dims, strides,
 // base pointers and offsets; smr_group_execute runs them as ONE launch of the kernel in smr_k_group.hip.  Planning is host
 // arithmetic: every member is canonicalised like a single call, checked against member 0, given one of the kernel's two bodies and
-// a contiguous range of workgroups.  The device tables are uploaded by smr_group_prepare or the first execution.
+// a contiguous range of workgroups.  The device tables are uploaded by smr_group_prepare or the first execution.  The planner also
+// keeps the byte ranges one execution reads and writes: the footprint of a group recorded in a sequence (smr_seq_add_group).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
+#include "smr_direct.h"
 #include "smr_dispatch.h"
 #include "smr_group.h"
 
@@ -137,6 +139,19 @@ int check_independent(std::vector<Range>& rs) {
     return SMR_OK;
 }
 
+// the union of `rs` as sorted ranges, overlapping and adjacent ones merged (a 128-member group hands a sequence's scheduler a
+// handful of ranges, not 256)
+Spans merged(Spans rs) {
+    std::sort(rs.begin(), rs.end());
+    Spans out;
+    for (const auto& r : rs) {
+        if (r.second <= r.first) continue;
+        if (!out.empty() && r.first <= out.back().second) out.back().second = std::max(out.back().second, r.second);
+        else out.push_back(r);
+    }
+    return out;
+}
+
 int launch_group(const GroupPlan& g, hipStream_t s) {
     switch (g.c.bitcopy ? SMR_F32 : g.c.ct) {
         case SMR_F32: return launch_group_ct<SMR_F32>(g, s);
@@ -176,6 +191,18 @@ struct smr_group {
     void* stream = nullptr;  // of member 0: drained before the tables are freed
 };
 
+// ---- hooks for smr_seq.cpp, declared in smr_direct.h (the smr_group struct is private to this file) -----------------------------------
+namespace smr {
+int seq_execute_group(smr_group* g, hipStream_t s, bool prepare_only) {
+    if (prepare_only) return smr_group_prepare(g);
+    return smr_group_execute(g, (void*)s);  // while a sequence records, the launch is appended to the recorder instead
+}
+void seq_footprint_group(smr_group* g, Spans& rd, Spans& wr) {
+    rd.insert(rd.end(), g->plan.rd.begin(), g->plan.rd.end());
+    wr.insert(wr.end(), g->plan.wr.begin(), g->plan.wr.end());
+}
+}  // namespace smr
+
 extern "C" {
 
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
@@ -189,6 +216,7 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
     g.first_wg.assign((size_t)count + 1, 0);
     g.rank.resize((size_t)count);
     std::vector<Range> ranges;
+    Spans rd, wr;
     i64 grid = 0;
     int rc = SMR_OK;
     for (int i = 0; i < count && rc == SMR_OK; ++i) {
@@ -225,14 +253,16 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
         }
         g.first_wg[(size_t)i + 1] = (uint32_t)grid;
         g.algbytes += c.algbytes;
-        if (!(flags & SMR_GROUP_INDEPENDENT))
-            for (int k = 0; k < c.M; ++k) {
-                Range r;
-                operand_span(c, k, c.base[k], r.lo, r.hi);
-                r.member = i;
-                r.write = k == 0;
-                ranges.push_back(r);
-            }
+        // the bounding byte range of every operand: compared for the independence check (skipped under SMR_GROUP_INDEPENDENT) and
+        // always kept as the group's footprint, which stays conservative for interleaved members
+        for (int k = 0; k < c.M; ++k) {
+            Range r;
+            operand_span(c, k, c.base[k], r.lo, r.hi);
+            r.member = i;
+            r.write = k == 0;
+            (r.write ? wr : rd).emplace_back(r.lo, r.hi);
+            if (!(flags & SMR_GROUP_INDEPENDENT)) ranges.push_back(r);
+        }
     }
     if (rc == SMR_OK && !(flags & SMR_GROUP_INDEPENDENT)) rc = check_independent(ranges);
     if (rc) {
@@ -240,6 +270,8 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
         return rc;
     }
     h->stream = members[0].stream;
+    g.rd = merged(std::move(rd));
+    g.wr = merged(std::move(wr));
     // what launch_group_ct() does: with_prog (runtime compilation first) for a mixed group and for an f without a native functor.
     // FK_PROG has a bit in GROUP_FMASK like every kind, so the mask alone does not tell
     g.jit = options().jit && !g.c.bitcopy && (g.c.mixed || g.c.fkind == FK_PROG || !(GROUP_FMASK & fbit(g.c.fkind)));

@@ -44,6 +44,9 @@ struct GroupPlan {
     bool jit = false;                 // f runs as a runtime-compiled functor
     i64 algbytes = 0;
     std::string desc;
+    // what one execution reads (every input of every member) and writes (every destination): operand_span() ranges, sorted, with
+    // overlapping and adjacent ones merged -- the footprint of a group recorded in a sequence (smr_seq_add_group)
+    std::vector<std::pair<uintptr_t, uintptr_t>> rd, wr;
     // device copies of `members` and `first_wg`, uploaded by prepare / the first execution
     mutable std::mutex build_mu;
     mutable void* d_members = nullptr;

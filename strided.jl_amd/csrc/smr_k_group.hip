@@ -1,7 +1,8 @@
 // smr_k_group.hip -- grouped launches: K small independent maps (one functor f, the same operand types; rank, dims, strides,
 // pointers and offsets of their own) in ONE launch of 256-lane workgroups.  The grid is the sum of the members' workgroup counts:
-// a workgroup finds its member by a binary search of the prefix sums first_wg[] with blockIdx.x and reads the member's descriptor
-// (smr_group.h: GroupMemberD).  Both steps use wave-uniform indices only, so they stay in scalar registers.  Two bodies, chosen
+// a workgroup finds its member by a binary search of the prefix sums first_wg[] with its index in the group (blockIdx.x + wg0: a
+// launch may be one contiguous block range of the group, which is how a recorded sequence spreads one group over several hardware
+// queues) and reads the member's descriptor (smr_group.h: GroupMemberD).  Both steps use wave-uniform indices only, so they stay in scalar registers.  Two bodies, chosen
 // per member by the group planner (smr_group.cpp):
 //   linear       destination-fastest enumeration, GROUP_CHUNK consecutive canonical indices per workgroup, GROUP_U per lane
 //                (256 apart: a wave's accesses are consecutive).  The index is decomposed once per lane and then stepped by the
@@ -32,14 +33,15 @@ struct GroupArgs {
     int32_t count, M;
     int32_t dtype[MAXM];
     int32_t conj[MAXM];
+    uint32_t wg0;              // first workgroup of this launch within the group (0: the launch is the whole group)
 };
 
 template <class T, class F, bool MIXED>
 SMR_DEV void group_body(const GroupArgs a, F f) {
     __shared__ T tile[GROUP_TILE * (GROUP_TILE + 1)];
     const int nin = (F::NIN >= 0) ? F::NIN : a.M - 1;
-    // the member of this workgroup: the last one whose first workgroup is <= blockIdx.x (every member has at least one)
-    const uint32_t b = blockIdx.x;
+    // the member of this workgroup: the last one whose first workgroup is <= its index in the group (every member has at least one)
+    const uint32_t b = blockIdx.x + a.wg0;
     GroupWordC* const first_wg = (GroupWordC*)a.first_wg;
     int lo = 0, hi = a.count;
     while (hi - lo > 1) {
@@ -193,7 +195,11 @@ static int go(const GroupPlan& g, hipStream_t s, F f) {
         a.dtype[k] = k < c.M ? c.dtype[k] : 0;
         a.conj[k] = k < c.M ? c.conj[k] : 0;
     }
+    a.wg0 = 0;
     const unsigned grid = g.first_wg.back();
+    // the members are independent and a workgroup serves one member: any contiguous block range can be launched on its own.  `a` is
+    // the first kernel parameter of k_group and of the runtime-compiled entry alike, so wg0 has one kernarg offset in both
+    mark_sliceable(1, (unsigned)offsetof(GroupArgs, wg0), 0);
     if constexpr (is_jit<F>::value)
         return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED);
     else

@@ -1,4 +1,4 @@
-// smr_seq.cpp -- recorded sequences of plan executions, replayed as hand-built AQL packets on the library's own HSA queue.
+// smr_seq.cpp -- recorded sequences of plan and group executions, replayed as hand-built AQL packets on the library's own HSA queue.
 //
 // Why.  The reference runs independent pieces of work as concurrent tasks and waits only where it must (src/mapreduce.jl:203-223).
 // On MI355X the unit is the LAUNCH, and a stream-ordered launch of 16 MiB is a span of 1.6-3.2 us plus a 1.6-1.9 us boundary (drain,
@@ -34,8 +34,9 @@
 using namespace smr;
 
 // ---- the sequence object ----------------------------------------------------------------------------------------------------------
-struct SeqItem {
+struct SeqItem {  // one recorded execution: of a plan (with optional rebinding of base pointers) or of a group (`plan` is null)
     smr_plan* plan;
+    smr_group* group;
     bool has_bases;
     void* bases[SMR_MAXM];
 };
@@ -114,17 +115,22 @@ struct Rec {
     size_t blocksize(size_t j) const { return (std::max<size_t>(refs[j].kernarg_size, launches[j].args.size()) + 255) & ~(size_t)255; }
 };
 void* const* bases_of(const SeqItem& it) { return it.has_bases ? it.bases : nullptr; }
+// an item executes (or, prepare_only: builds whatever its first execution would build) as what it is
+int seq_execute_item(const SeqItem& it, hipStream_t s, bool prepare_only) {
+    return it.group ? seq_execute_group(it.group, s, prepare_only) : seq_execute_plan(it.plan, bases_of(it), s, prepare_only);
+}
 
 // the footprints of the recorded executions, as the scheduler wants them (launch facts are added by seq_record)
 std::vector<SchedExec> seq_footprints(smr_seq* q) {
     std::vector<SchedExec> ex(q->items.size());
     for (size_t i = 0; i < ex.size(); ++i) {
         const SeqItem& it = q->items[i];
-        seq_footprint(it.plan, bases_of(it), ex[i].rd, ex[i].wr);
+        if (it.group) seq_footprint_group(it.group, ex[i].rd, ex[i].wr);
+        else seq_footprint(it.plan, bases_of(it), ex[i].rd, ex[i].wr);
         ex[i].same_as = (int)i;
         for (size_t j = 0; j < i && ex[i].same_as == (int)i; ++j) {
             const SeqItem& o = q->items[j];
-            if (o.plan == it.plan && o.has_bases == it.has_bases && !(it.has_bases && std::memcmp(it.bases, o.bases, sizeof it.bases) != 0)) ex[i].same_as = (int)j;
+            if (o.plan == it.plan && o.group == it.group && o.has_bases == it.has_bases && !(it.has_bases && std::memcmp(it.bases, o.bases, sizeof it.bases) != 0)) ex[i].same_as = (int)j;
         }
     }
     return ex;
@@ -143,15 +149,15 @@ SchedKnobs seq_knobs(const smr_seq* q) {
 // self-released only while everything the sequence touches stays in the caches (schedule(): cache_resident)
 int seq_record(smr_seq* q, std::vector<Rec>& recs, std::vector<SchedExec>& ex) {
     for (const SeqItem& it : q->items)
-        if (int rc = seq_execute_plan(it.plan, bases_of(it), nullptr, true)) return rc;
+        if (int rc = seq_execute_item(it, nullptr, true)) return rc;
     ex = seq_footprints(q);
     const bool allow_self = schedule(ex, seq_knobs(q)).cache_resident;
     for (size_t i = 0; i < q->items.size(); ++i) {
         set_recorder(&recs[i].launches, allow_self);
-        int rc = seq_execute_plan(q->items[i].plan, bases_of(q->items[i]), nullptr, false);
+        int rc = seq_execute_item(q->items[i], nullptr, false);
         set_recorder(nullptr);
         if (rc) return rc;
-        if (recs[i].launches.empty()) return set_error(SMR_EINVAL, "smr_seq: a plan recorded no launch");
+        if (recs[i].launches.empty()) return set_error(SMR_EINVAL, "smr_seq: an item recorded no launch");
         const RecLaunch& l0 = recs[i].launches[0];
         ex[i].nlaunch = (int)recs[i].launches.size();
         ex[i].grid = l0.grid;
@@ -411,6 +417,17 @@ int smr_seq_add(smr_seq* q, smr_plan* plan, void* const* bases) {
     return SMR_OK;
 }
 
+int smr_seq_add_group(smr_seq* q, smr_group* group) {
+    if (!q || !group) return set_error(SMR_EINVAL, "null argument");
+    if (q->inflight) return set_error(SMR_EINVAL, "smr_seq_add_group: a replay is in flight (smr_seq_wait first)");
+    SeqItem it;
+    std::memset(&it, 0, sizeof it);
+    it.group = group;
+    q->items.push_back(it);
+    q->built = false;
+    return SMR_OK;
+}
+
 int smr_seq_run(smr_seq* q, int reps, void* stream) {
     if (!q || reps < 1) return set_error(SMR_EINVAL, "smr_seq_run: null sequence or reps < 1");
     if (q->items.empty()) return set_error(SMR_EINVAL, "smr_seq_run: empty sequence");
@@ -427,7 +444,7 @@ int smr_seq_run(smr_seq* q, int reps, void* stream) {
     if (!q->aql) {  // HIP path: the same launches, in order on the caller's stream
         for (int r = 0; r < reps; ++r)
             for (SeqItem& it : q->items) {
-                int rc = seq_execute_plan(it.plan, it.has_bases ? it.bases : nullptr, s, false);
+                int rc = seq_execute_item(it, s, false);
                 if (rc) return rc;
             }
         ++q->runs;
@@ -525,18 +542,20 @@ int smr_seq_info(smr_seq* q, char* buf, size_t buflen) {
         int rc = seq_build(q);
         if (rc) return rc;
     }
+    int ngroups = 0;
+    for (const SeqItem& it : q->items) ngroups += it.group != nullptr;
     if (q->aql) {
         const Direct& d = direct_of(q->device);
         size_t np = 0;
         for (const auto& v : q->packets) np += v.size();
         const int first = q->acq_first >= 0 ? q->acq_first : q->acq_first_auto;
-        std::snprintf(buf, buflen, "backend=aql items=%zu packets=%zu components=%d sliced=%d queues=%d ordered=%d unordered=%d acquire=%s(%d of %zu packets) first_acquire=%s release=%d self_released=%d kernarg_layout=%s agent=%s stream_wait=%s last_replay_us=%.3f",
-                      q->items.size(), np, q->ncomp, q->nsliced, q->nq, q->n_barrier, q->n_any, q->acq_mid < 0 ? "by-need" : (q->acq_mid == 0 ? "none" : (q->acq_mid == 1 ? "agent" : "system")),
+        std::snprintf(buf, buflen, "backend=aql items=%zu groups=%d packets=%zu components=%d sliced=%d queues=%d ordered=%d unordered=%d acquire=%s(%d of %zu packets) first_acquire=%s release=%d self_released=%d kernarg_layout=%s agent=%s stream_wait=%s last_replay_us=%.3f",
+                      q->items.size(), ngroups, np, q->ncomp, q->nsliced, q->nq, q->n_barrier, q->n_any, q->acq_mid < 0 ? "by-need" : (q->acq_mid == 0 ? "none" : (q->acq_mid == 1 ? "agent" : "system")),
                       q->n_acquire, np, first == 2 ? "system" : (first == 1 ? "agent" : "none"), q->rel_mid, q->n_self_released, layout_source(d), d.agent_by_pci ? "pci-address" : "only-gpu",
                       q->async_mode == 0 ? "host(blocking)" : (d.wait_value_ok ? "hipStreamWaitValue64" : "holding-kernel|owned-stream"), d.last_us);
     }
     else
-        std::snprintf(buf, buflen, "backend=hip items=%zu (%s)", q->items.size(), q->why_not_aql.c_str());
+        std::snprintf(buf, buflen, "backend=hip items=%zu groups=%d (%s)", q->items.size(), ngroups, q->why_not_aql.c_str());
     return SMR_OK;
 }
 

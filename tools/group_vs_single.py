@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""K small permutedims! calls issued three ways, warm, on one MI355X:
+"""K small permutedims! calls issued four ways, warm, on one MI355X:
 
   (a) single   K plan executions one by one on a HIP stream (what a loop over blocks does today)
   (b) sequence the same K plans recorded into a Sequence and replayed by the library (default 4 queues)
-  (c) group    ONE launch of a group of the K members (smr_group_*, csrc/smr_k_group.hip)
+  (c) group    ONE launch of a group of the K members through HIP (smr_group_execute, csrc/smr_k_group.hip)
+  (d) recorded group  that group recorded into a Sequence (smr_seq_add_group): one kernel AND one pre-built packet per execution;
+               with the default "slices", with "slices" = 1 (never cut) and with "slices" = 4 (the one launch cut into four block
+               ranges on four hardware queues -- the scheduler cuts only launches of at least 64 workgroups per range)
 
 Every member is a Float64 array of its own, permuted with the reversal permutation into an array of its own.  A round times
 `reps` executions of each form between device synchronisations with the host clock (so launch cost on the host counts, as it does
-for a user); rounds alternate the three forms, the table gives the median over the rounds and the spread (min..max) in us per
-execution of all K members.  The results of (c) are compared bit for bit with those of (a) before anything is timed.
+for a user); rounds alternate the forms, the table gives the median over the rounds and the spread (min..max) in us per
+execution of all K members.  The results of (c) and of every (d) are compared bit for bit with those of (a) before anything is timed.
 
     python tools/group_vs_single.py [--rounds 7] [--target-ms 250] [--out profiles/group_launch.txt]
 """
@@ -57,8 +60,10 @@ def main():
     lines = ["# %s, %d rounds of >= %.0f ms per form, us per execution of all K members: median (min..max)" %
              (torch.cuda.get_device_name(0), args.rounds, args.target_ms),
              "# member = permutedims!(dst, src, reverse) of a Float64 array; bytes = algorithmic bytes of one member",
-             "%-8s %9s %4s  %-26s %-26s %-26s %s" % ("shape", "bytes", "K", "(a) single", "(b) sequence", "(c) group", "group wins")]
-    wins = []
+             "# (d) = the group recorded in a sequence: slices default / 1 / 4 (sliced=0/1: whether the scheduler cut the launch)",
+             "%-8s %9s %4s  %-26s %-26s %-26s %-26s %-26s %-28s %s" % ("shape", "bytes", "K", "(a) single", "(b) sequence", "(c) group", "(d) recorded group",
+                                                                  "(d) slices=1", "(d) slices=4", "(d) beats (b) and (c)")]
+    wins, dwins = [], []
     for shape, ks in SHAPES:
         n = int(np.prod(shape))
         perm = tuple(reversed(range(len(shape))))
@@ -87,27 +92,51 @@ def main():
                 for _ in range(reps):
                     grp.execute(stream)
 
-            forms = (single, sequence, group)
-            for f in forms:  # warm: code objects, tables, packets
+            def recorded(q):
+                def run(reps):
+                    q.run(reps, stream)
+                    q.wait()
+                return run
+
+            gseqs = []
+            for slices in (None, 1, 4):
+                q = S.Sequence().add_group(grp)
+                if slices is not None:
+                    q.set("slices", slices)
+                gseqs.append(q)
+            forms = (single, sequence, group) + tuple(recorded(q) for q in gseqs)
+            for f in forms:  # warm: code objects, tables, packets; every form that writes dst2 is checked on zeroed destinations
+                if f is not single and f is not sequence:
+                    for e in dst2:
+                        e.parent.zero_()
+                    sync()
                 f(3)
-            sync()
-            for d, e in zip(dst, dst2):
-                assert torch.equal(d.parent, e.parent), "group result differs from the single calls"
+                sync()
+                if f is not single and f is not sequence:
+                    for d, e in zip(dst, dst2):
+                        assert torch.equal(d.parent, e.parent), "group result differs from the single calls"
+            how = [q.info() for q in gseqs]
+            assert all("backend=aql" in h for h in how), how
+            cut = ["sliced=1" in h for h in how]
             reps = []
             for f in forms:  # size every window from a short probe
                 t = timed(f, 5, sync)
                 reps.append(max(5, int(args.target_ms * 1e3 / max(t, 0.5))))
-            samples = [[], [], []]
+            samples = [[] for _ in forms]
             for _ in range(args.rounds):
                 for i, f in enumerate(forms):
                     samples[i].append(timed(f, reps[i], sync))
             med = [statistics.median(x) for x in samples]
             cell = ["%8.2f (%.2f..%.2f)" % (m, min(x), max(x)) for m, x in zip(med, samples)]
+            cell[5] += " sliced=%d" % cut[2]
+            assert not cut[0] and not cut[1], how
             win = med[2] < med[0] and med[2] < med[1]
             wins.append((shape, K, 2 * n * 8, win, med[2] < med[0]))
-            lines.append("%-8s %9d %4d  %-26s %-26s %-26s %s" % ("%d^%d" % (shape[0], len(shape)), 2 * n * 8, K, *cell, "yes" if win else "no"))
+            dwin = med[3] < med[1] and med[3] < med[2]
+            dwins.append((shape, K, dwin, med[3] < med[1], med[3] < med[2], min(med[3:]) < med[1]))
+            lines.append("%-8s %9d %4d  %-26s %-26s %-26s %-26s %-26s %-28s %s" % ("%d^%d" % (shape[0], len(shape)), 2 * n * 8, K, *cell, "yes" if dwin else "no"))
             print(lines[-1], flush=True)
-            del plans, grp, seq
+            del plans, grp, seq, gseqs
     lines.append("")
     won = [(s, k, b) for s, k, b, w, _ in wins if w]
     if won:
@@ -119,6 +148,11 @@ def main():
     # the front replaces single calls, never a recorded sequence: the default of option group_max_bytes comes from this line
     a8 = [b for s, k, b, _, wa in wins if wa and k == 8]
     lines.append("# largest member at which (c) beats (a) at K = 8: " + ("%d bytes" % max(a8) if a8 else "none"))
+    name = lambda s, k: "%d^%d K=%d" % (s[0], len(s), k)  # noqa: E731
+    lines.append("# (d) beats both (b) and (c) at " + (", ".join(name(s, k) for s, k, w, _, _, _ in dwins if w) or "no row"))
+    lines.append("# (d) does not beat (b) at " + (", ".join(name(s, k) for s, k, _, wb, _, _ in dwins if not wb) or "no row"))
+    lines.append("# (d) does not beat (c) at " + (", ".join(name(s, k) for s, k, _, _, wc, _ in dwins if not wc) or "no row"))
+    lines.append("# no slice setting of (d) beats (b) at " + (", ".join(name(s, k) for s, k, _, _, _, wany in dwins if not wany) or "no row"))
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
