@@ -359,7 +359,7 @@ class _Deferred:
 class group:
     """`with S.group(independent=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
-    `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, stream) becomes ONE
+    `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
       * a call whose byte ranges conflict with a pending call (it writes what one reads or writes, or reads what one writes) first
         flushes everything pending.  With `independent=True` only exact same-view conflicts count -- the caller asserts that
@@ -424,7 +424,11 @@ class group:
         c.stream = _current_stream()
         dts = tuple(np.dtype(a.dtype) for a in arrays)
         code, consts = _serialized(f, len(arrays), dts)
-        c.bucket = (bytes(code), tuple(consts), tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), c.stream)
+        # inputs that are one operand to the library (csrc/smr_canon.cpp dedupes identical inputs): calls that differ in this pattern run
+        # another kernel signature, and one bucket of them would be refused as a group
+        ops = [(a._base, a.offset, a.op, tuple(st for d, st in zip(c.dims, a.strides) if d != 1)) for a in arrays[1:]]
+        same = tuple(ops.index(o) for o in ops)
+        c.bucket = (bytes(code), tuple(consts), tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream)
         c.wr = _byte_range(arrays[0])
         c.rd = [_byte_range(a) for a in arrays[1:]]
         c.key = _problem_key(f, None, None, c.dims, arrays)

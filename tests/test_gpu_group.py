@@ -4,69 +4,10 @@ import numpy as np
 import pytest
 
 import strided_jl_amd as S
-from strided_jl_amd import _lib as L
+from group_cases import CHUNK, ident, rand, run_group, same_bits, sync
 from util import host_flat, run_oracle, rtol, to_device
 
 pytestmark = pytest.mark.gpu
-
-CHUNK = 256 * 4  # canonical indices per workgroup of the linear body (csrc/smr_group.h: GROUP_CHUNK)
-
-
-def ident(x):
-    return x
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def cur_stream():
-    import torch
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
-def rand(rng, shape, dt):
-    dt = np.dtype(dt)
-    if np.issubdtype(dt, np.integer):
-        a = rng.integers(-100000, 100000, size=shape).astype(dt)
-    elif np.issubdtype(dt, np.complexfloating):
-        a = (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(dt)
-    else:
-        a = rng.standard_normal(shape).astype(dt)
-    return S.StridedView(np.asfortranarray(a).copy(order="F"))
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def run_group(calls, independent=False, ref=None):
-    """calls: (f, host arrays).  Returns (group, per call: oracle result, group result, result of the call issued alone).
-    `ref`: a NumPy function of the input arrays that stands in for the oracle, whose f-program evaluator has no math opcodes."""
-    cache, devs = {}, []
-    for f, arrays in calls:
-        devs.append(tuple(to_device(a, cache) for a in arrays))
-    alone = []
-    for (f, arrays), dev in zip(calls, devs):  # the same call alone, on private copies taken before anything ran
-        c2 = {}
-        d2 = tuple(to_device(a, c2) for a in arrays)
-        S._mapreduce_fuse_(f, None, None, arrays[0].size, d2)
-        sync()
-        alone.append(d2[0].toarray())
-    built = [S.build_problem(f, None, None, arrays[0].size, dev, stream=cur_stream()) for (f, arrays), dev in zip(calls, devs)]
-    g = L.Group([b[0] for b in built], independent, keepalive=built)
-    sync()
-    before = S.get_option("launches")
-    g.execute(cur_stream())
-    assert S.get_option("launches") == before + 1
-    sync()
-    got = [dev[0].toarray() for dev in devs]
-    if ref is None:
-        want = [run_oracle(f, None, None, arrays[0].size, arrays) for f, arrays in calls]
-    else:
-        want = [ref(*[a.toarray() for a in arrays[1:]]) for f, arrays in calls]
-    return g, want, got, alone
 
 
 SHAPES = [(1,), (5, 7), (31, 33), (32, 32), (33, 31), (64, 1, 3), (3, 65, 2), (2, 3, 4, 5, 2, 3), (4,) * 8, (CHUNK,), (CHUNK + 1,),
