@@ -29,6 +29,7 @@ constexpr int MAXIN = SMR_MAXM - 1;
 constexpr int STACK = 8;  // device evaluator stack depth (register-rotated)
 constexpr int MAXG = 4;   // FAM_ORBIT: largest permutation group handled (slots of LDS per workgroup)
 constexpr int FLATB_MAXP = 512;  // FAM_FLAT, batched form: largest contiguous block (elements)
+constexpr int TILED_NG = 4;      // FAM_TILED: grid dims the lean kernels decode branch-free
 
 #ifndef SMR_JIT
 int set_error(int code, const std::string& msg);  // returns code
@@ -147,6 +148,7 @@ struct TilePlan {
     int ord_groups = 0;
     bool no_persist = false;  // block-ordered lists run in the one-shot form
     int gorder[MAXN] = {0, 1, 2, 3, 4, 5, 6, 7};  // order of the grid dims (canonical dims, fastest first; dims with one tile are skipped): plan_tiles
+    bool origins32 = false;  // at most TILED_NG grid dims and every operand's tile origins below 4 GiB, no negative grid stride: the lean kernels apply
 };
 
 // Description for FAM_ORBIT (smr_k_orbit.hip).  Every input k is a view of one buffer whose strides are
@@ -375,6 +377,19 @@ struct RedLaunch {
     int ctx = 0, cty = 0, cy0 = 0, cy1 = 0;  // COL: lanes along kept dim 0 x rows (cy0 along the inner reduced dim x cy1 along q)
 };
 RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch);
+
+// TILED: the kernel variant one execution launches for the given operand bases (nullptr: the bases the plan was made with), elements
+// of `esize` bytes and MIXED operand types or not.  The launcher (smr_k_tiled.hip: go, go_tl, go3) dispatches on it and describe()
+// prints it; the rules live in tiled_variant() alone (smr_plan.cpp).
+struct TiledVariant {
+    int V = 1;          // elements per global access (V * esize <= 16 bytes)
+    bool ua = false;    // ... at element alignment: odd extents, odd row strides, views that begin inside a vector
+    int mode = 0;       // MODE of tiled_map_body: bit 0 bounds checks, bit 1 tile-order lookup, bit 2 general tile origins, 9 = 1 + partial vectors
+    bool wide = false;  // 64-bit within-tile byte offsets
+    int thrlog = 8;     // log2 threads per workgroup (4 elements per lane)
+    unsigned pgrid = 0; // workgroups of the persistent, software-pipelined form (0: the one-shot form runs)
+};
+TiledVariant tiled_variant(const Plan& plan, void* const* bases, int esize, bool mixed);
 
 // ---- runtime compilation of f-programs without a natively compiled functor (smr_jit.cpp) ------------
 // The kernel family's own source file is compiled by hiprtc with the f-program turned into a

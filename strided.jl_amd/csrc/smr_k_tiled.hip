@@ -62,7 +62,7 @@
 namespace smr {
 
 constexpr int MAXT = 5;
-constexpr int NG = 4;   // grid dims decoded branch-free; further ones in a (rare) loop
+constexpr int NG = TILED_NG;  // grid dims decoded branch-free; further ones in a (rare) loop
 constexpr int EPL = 4;  // elements per lane (tile elements / workgroup size)
 constexpr int NORD16 = 512;  // tile-order entries that fit into the kernel arguments
 
@@ -845,7 +845,6 @@ static Swizzle choose_swizzle(int tilelog, int w, const std::vector<LanePattern>
 template <bool WIDE>
 struct TiledLaunch {
     TiledArgs<WIDE> a;
-    bool lean_fails = false;  // the lean variants (MODE & 4 == 0) assume 32-bit tile origins over at most NG grid dims: variant 7
     unsigned grid = 0;        // workgroups of the one-shot form
     unsigned pgrid = 0;       // of the persistent, software-pipelined form (0: the one-shot form runs)
     size_t lds = 0;
@@ -855,9 +854,9 @@ struct TiledLaunch {
 // first execution of the variant (WIDE, V) with its lane and tile-order tables, and cached in the plan (Plan::tiled_cache).  The operand
 // addresses, the persistent grid and the store policy are set per call; wt_store: the kernel's vector type has write-through stores.
 template <bool WIDE>
-static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V, int MODE, int THRLOG, bool ua, bool wt_store,
-                            TiledLaunch<WIDE>& L) {
+static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, const TiledVariant& tv, bool wt_store, TiledLaunch<WIDE>& L) {
     typedef typename off_t_of<WIDE>::type O;
+    const int V = tv.V, MODE = tv.mode, THRLOG = tv.thrlog;
     const bool EDGE = (MODE & 1) != 0, LEAN = (MODE & 4) == 0;
     const int NREP = EPL / V, NT = 1 << THRLOG;
     const Canon& c = plan.c;
@@ -868,15 +867,7 @@ static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V
     TiledArgs<WIDE>& a = L.a;
     L.lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * esize;
     L.grid = t.ord.empty() ? (unsigned)t.grid : (unsigned)t.ord.size();
-    // persistent, software-pipelined form when the work list is longer than the machine holds at once
-    L.pgrid = 0;
-    if (!EDGE && o.tiled_persist && !t.no_persist && !ua) {  // (the persistent form keeps aligned vector accesses)
-        i64 wpc = std::min<i64>(2048 >> THRLOG, L.lds ? (i64)(160 * 1024 / L.lds) : 8);
-        wpc = std::max<i64>(1, std::min<i64>(wpc, 4));  // measured: 4 workgroups per CU beat 8 and 2
-        if (o.tiled_persist_wpc > 0) wpc = o.tiled_persist_wpc;
-        const i64 cap = (i64)cu_count() * wpc / 8 * 8;
-        if ((i64)L.grid >= cap * o.tiled_persist_min && cap >= 8) L.pgrid = (unsigned)cap;
-    }
+    L.pgrid = tv.pgrid;  // the persistent, software-pipelined form (tiled_variant)
     // non-temporal stores: measured faster or equal whenever a tile writes whole 128-byte lines (32^4 Float64
     // permutedims! 3.36 -> 2.76 us, 128^4 864 -> 818 us, never slower for a consumer kernel that follows);
     // partial lines must meet in L2 first, so short destination runs keep plain stores
@@ -892,7 +883,6 @@ static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V
     Plan::FormCache& cached = plan.tiled_cache[variant];
     if (cached.args.size() == sizeof a) {
         std::memcpy(&a, cached.args.data(), sizeof a);
-        L.lean_fails = LEAN && (!a.base32 || a.ng > NG);
         for (int k = 0; k < c.M; ++k) a.op[k].base = tab.base[k];
         a.nts = nts_now;
         return SMR_OK;
@@ -1079,22 +1069,9 @@ static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V
         }
     }
     a.ng = ng;
-    // 32-bit tile-origin arithmetic when every operand's tile origins stay below 4 GiB
-    bool base32 = ng <= NG;
-    for (int k = 0; k < c.M && base32; ++k) {
-        long double span = 0;
-        for (int d = 0; d < c.N; ++d) {
-            if (gof[d] < 0) continue;
-            if (c.strides[k][d] < 0) base32 = false;
-            span += (long double)c.strides[k][d] * c.esize[k] * (long double)(t.ntiles[d] - 1) * (long double)((i64)1 << tlogdim[d]);
-        }
-        if (span >= 4294967296.0L) base32 = false;
-    }
-    a.base32 = base32 ? 1 : 0;
-    if (LEAN && (!base32 || ng > NG)) {  // (variant 7 builds and caches the arguments)
-        L.lean_fails = true;
-        return SMR_OK;
-    }
+    // 32-bit tile-origin arithmetic when every operand's tile origins stay below 4 GiB (plan_tiles; tiled_variant picks variant 7 otherwise)
+    a.base32 = t.origins32 ? 1 : 0;
+    if (LEAN && (!t.origins32 || ng > NG)) return set_error(SMR_EINVAL, "tiled: a lean variant was picked for a plan without 32-bit tile origins");
 
     // per-lane table: built once per (plan, kernel variant), kept in device memory (not needed by the BITS form)
     const bool build_tab = !BITS && cached.tab == nullptr && !jit_dry_run();
@@ -1181,10 +1158,10 @@ static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, int V
 }
 
 template <class T, class F, bool MIXED, bool WIDE, int V, int MODE, int THRLOG>
-static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua = false) {
+static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const TiledVariant& tv) {
     TiledLaunch<WIDE> L;
     constexpr bool wt_store = V > 1 && !MIXED && has_wt_store<TVec<T, V>>::value;
-    if (int rc = build_tiled_args<WIDE>(plan, tab, (int)sizeof(T), V, MODE, THRLOG, ua, wt_store, L)) return rc;
+    if (int rc = build_tiled_args<WIDE>(plan, tab, (int)sizeof(T), tv, wt_store, L)) return rc;
     const TiledArgs<WIDE>& ka = L.a;
     const unsigned block = 1u << THRLOG;
     auto launch = [&]() -> int {
@@ -1208,89 +1185,32 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua 
             });
         }
     };
-    // (after the lambda: the kernels it names keep their place in the code object, ahead of variant 7's)
-    if constexpr ((MODE & 4) == 0) {
-        if (L.lean_fails) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, ua);
-    }
     return launch();
 }
 
+// The kernel of tiled_variant()'s choice (smr_plan.cpp): MODE here, 64-bit offsets, vector width and threads in go_tl and go.
 template <class T, class F, bool MIXED, bool WIDE, int V, int THRLOG>
-static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool ua = false) {
-    const Canon& c = plan.c;
-    const TilePlan& t = plan.tile;
-    bool ragged = false;
-    for (int j = 0; j < t.nt; ++j)
-        if (c.dims[t.tdim[j]] & (((i64)1 << t.tlog[j]) - 1)) ragged = true;
-    // ragged extents: the lean kernel plus bounds checks in the workgroups that sit on a last, partly filled tile (round 6; every
-    // ragged problem used to take variant 7 -- lane tables from memory, 64-bit origins, order lookups -- and paid ~2 us for it:
-    // transposes of 7200 x 100 Float64 5.4 us against 3.0 us for 7200 x 128, profiles/r06_ragged_tiles.txt)
-    bool pv = false;  // does some operand's vector axis end in a partial vector?
+static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const TiledVariant& tv) {
     if constexpr (V > 1) {
-        for (int k = 0; k < c.M; ++k) {
-            const int j0 = (k > 0 && t.staged[k] >= 0) ? t.order[k][0] : 0;
-            if (c.dims[t.tdim[j0]] % V) pv = true;
-        }
-        if (ragged && t.ord.empty() && pv) return go3e<T, F, MIXED, WIDE, V, 9, THRLOG>(plan, s, f, tab, ua);
+        if (tv.mode == 9) return go3e<T, F, MIXED, WIDE, V, 9, THRLOG>(plan, s, f, tab, tv);
     }
-    if (ragged && t.ord.empty()) return go3e<T, F, MIXED, WIDE, V, 1, THRLOG>(plan, s, f, tab, ua);
-    if (ragged) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, ua);
-    if (!t.ord.empty()) return go3e<T, F, MIXED, WIDE, V, 2, THRLOG>(plan, s, f, tab, ua);
-    return go3e<T, F, MIXED, WIDE, V, 0, THRLOG>(plan, s, f, tab, ua);
-}
-
-// The same at element alignment (round 6): odd extents, odd row strides, views that begin inside a vector.  Every operand still runs
-// along its unit axis; the one partial vector at the end of a row (extent not a multiple of V) is moved element by element by the
-// workgroups of the ragged last tile.  Elements of 4 or 8 bytes.
-static bool vector_ok_ua(const Plan& plan, const OpTab& tab, int V, int esize) {
-    const Canon& c = plan.c;
-    const TilePlan& t = plan.tile;
-    int vlog = 0;
-    while ((1 << vlog) < V) ++vlog;
-    if (esize < 4) return false;
-    for (int k = 0; k < c.M; ++k) {
-        const bool staged = k > 0 && t.staged[k] >= 0;
-        const int j0 = staged ? t.order[k][0] : 0;
-        const int d0 = t.tdim[j0];
-        if (t.tlog[j0] < vlog) return false;
-        if (c.strides[k][d0] != 1 || c.dims[d0] < V) return false;
-        if (((uintptr_t)tab.base[k]) % esize) return false;
-    }
-    return true;
-}
-
-// Can every operand be accessed V elements at a time (V * sizeof(T) <= 16 bytes)?
-static bool vector_ok(const Plan& plan, const OpTab& tab, int V, int esize) {
-    const Canon& c = plan.c;
-    const TilePlan& t = plan.tile;
-    int vlog = 0;
-    while ((1 << vlog) < V) ++vlog;
-    const size_t vb = (size_t)V * esize;
-    for (int k = 0; k < c.M; ++k) {
-        const bool staged = k > 0 && t.staged[k] >= 0;
-        const int j0 = staged ? t.order[k][0] : 0;  // first axis of this operand's enumeration
-        const int d0 = t.tdim[j0];
-        if (t.tlog[j0] < vlog) return false;
-        // a direct input that is not unit-stride along dim 0 (broadcast, odd stride) has no V-wide form
-        if (c.strides[k][d0] != 1) return false;
-        if (c.dims[d0] % V) return false;
-        if (((uintptr_t)tab.base[k]) % vb) return false;
-        for (int d = 0; d < c.N; ++d)
-            if (d != d0 && (c.strides[k][d] % V)) return false;
-    }
-    return true;
+    if (tv.mode == 1) return go3e<T, F, MIXED, WIDE, V, 1, THRLOG>(plan, s, f, tab, tv);
+    if (tv.mode == 7) return go3e<T, F, MIXED, WIDE, V, 7, THRLOG>(plan, s, f, tab, tv);
+    if (tv.mode == 2) return go3e<T, F, MIXED, WIDE, V, 2, THRLOG>(plan, s, f, tab, tv);
+    if (tv.mode == 0) return go3e<T, F, MIXED, WIDE, V, 0, THRLOG>(plan, s, f, tab, tv);
+    return set_error(SMR_EINVAL, "tiled: no kernel of this MODE");
 }
 
 template <class T, class F, bool MIXED, int THRLOG>
-static int go_tl(const Plan& plan, hipStream_t s, F f, const OpTab& tab, bool narrow) {
-    if (!narrow) return go3<T, F, MIXED, true, 1, THRLOG>(plan, s, f, tab);
+static int go_tl(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const TiledVariant& tv) {
+    if (tv.wide) return go3<T, F, MIXED, true, 1, THRLOG>(plan, s, f, tab, tv);
     if constexpr (!MIXED && sizeof(T) < 16) {
         // a lane's 4 elements as 16-byte vectors (8-byte for 1/2-byte element types)
         constexpr int VMAX = (16 / sizeof(T)) > 4 ? 4 : (int)(16 / sizeof(T));
-        if (options().tiled_vec && vector_ok(plan, tab, VMAX, (int)sizeof(T))) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab);
-        if (options().tiled_vec && options().tiled_uavec && vector_ok_ua(plan, tab, VMAX, (int)sizeof(T))) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab, true);
+        if (tv.V == VMAX) return go3<T, F, false, false, VMAX, THRLOG>(plan, s, f, tab, tv);
     }
-    return go3<T, F, MIXED, false, 1, THRLOG>(plan, s, f, tab);
+    if (tv.V != 1) return set_error(SMR_EINVAL, "tiled: no kernel of this vector width");
+    return go3<T, F, MIXED, false, 1, THRLOG>(plan, s, f, tab, tv);
 }
 
 // ---- XPOSE: the lean form of an HBM-sized transposing copy (round 5) -------------------------------------------------------------
@@ -1430,22 +1350,10 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
         const int rc = try_xpose_big<T, F>(plan, s, f, tab);
         if (rc != SMR_EUNSUPPORTED) return rc;
     }
-    // 32-bit within-tile byte offsets when every tiled stride is >= 0 and the tile spans < 4 GiB
-    bool narrow = true;
-    for (int k = 0; k < c.M && narrow; ++k) {
-        long double span = 0;
-        for (int j = 0; j < t.nt; ++j) {
-            const i64 st = c.strides[k][t.tdim[j]];
-            if (st < 0) narrow = false;
-            span += (long double)st * (((i64)1 << t.tlog[j]) - 1) * c.esize[k];
-        }
-        if (span >= 4294967296.0L) narrow = false;
-    }
-    // always 4 elements per lane: 1024-element tiles on 256 lanes, 4096-element tiles on 1024 lanes.
-    // Measured alternatives (32^4 f64): 2048/4096-element tiles on 256 lanes are 10-40 % slower.
-    if (t.tilelog == 10) return go_tl<T, F, MIXED, 8>(plan, s, f, tab, narrow);
-    if (t.tilelog == 12) return go_tl<T, F, MIXED, 10>(plan, s, f, tab, narrow);
-    return set_error(SMR_EINVAL, "tiled: the planner must pick 1024- or 4096-element tiles");
+    if (t.tilelog != 10 && t.tilelog != 12) return set_error(SMR_EINVAL, "tiled: the planner must pick 1024- or 4096-element tiles");
+    const TiledVariant tv = tiled_variant(plan, bases, (int)sizeof(T), MIXED);  // smr_plan.cpp: describe() prints the same choice
+    if (tv.thrlog == 8) return go_tl<T, F, MIXED, 8>(plan, s, f, tab, tv);
+    return go_tl<T, F, MIXED, 10>(plan, s, f, tab, tv);
 }
 
 template <>

@@ -925,6 +925,23 @@ static bool plan_tiles(const Canon& c, TilePlan& t) {
     }
     if (!t.ord.empty())  // work lists hold linear tile ids in canonical grid order
         for (int i = 0; i < MAXN; ++i) t.gorder[i] = i < c.N ? i : -1;
+    // 32-bit tile-origin arithmetic over at most TILED_NG grid dims (the lean kernels): grid dims are the dims with more than one tile
+    // plus one slot per tiled dim that is a single, partly empty tile; every operand's tile origins stay below 4 GiB
+    int ng = 0;
+    for (int d = 0; d < c.N; ++d)
+        if (t.ntiles[d] > 1) ++ng;
+    for (int j = 0; j < t.nt; ++j)
+        if (t.ntiles[t.tdim[j]] <= 1 && (c.dims[t.tdim[j]] & (((i64)1 << t.tlog[j]) - 1))) ++ng;
+    t.origins32 = ng <= TILED_NG;
+    for (int k = 0; k < c.M && t.origins32; ++k) {
+        long double span = 0;
+        for (int d = 0; d < c.N; ++d) {
+            if (t.ntiles[d] <= 1) continue;
+            if (c.strides[k][d] < 0) t.origins32 = false;
+            span += (long double)c.strides[k][d] * c.esize[k] * (long double)(t.ntiles[d] - 1) * (long double)((i64)1 << lg[d]);
+        }
+        if (span >= 4294967296.0L) t.origins32 = false;
+    }
     return true;
 }
 
@@ -1640,6 +1657,78 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
     return r;
 }
 
+TiledVariant tiled_variant(const Plan& plan, void* const* bases, int esize, bool mixed) {
+    const Canon& c = plan.c;
+    const TilePlan& t = plan.tile;
+    const Options& o = options();
+    TiledVariant v;
+    // always 4 elements per lane: 1024-element tiles on 256 lanes, 4096-element tiles on 1024 lanes.
+    // Measured alternatives (32^4 f64): 2048/4096-element tiles on 256 lanes are 10-40 % slower.
+    v.thrlog = t.tilelog - 2;
+    // 32-bit within-tile byte offsets when every tiled stride is >= 0 and the tile spans < 4 GiB
+    for (int k = 0; k < c.M && !v.wide; ++k) {
+        long double span = 0;
+        for (int j = 0; j < t.nt; ++j) {
+            const i64 st = c.strides[k][t.tdim[j]];
+            if (st < 0) v.wide = true;
+            span += (long double)st * (((i64)1 << t.tlog[j]) - 1) * c.esize[k];
+        }
+        if (span >= 4294967296.0L) v.wide = true;
+    }
+    // a lane's 4 elements as 16-byte vectors (8-byte for 1/2-byte element types): can every operand be accessed V elements at a time?
+    // `whole`: aligned vectors, every extent and stride a multiple of V.  Else at element alignment (round 6): odd extents, odd row
+    // strides, views that begin inside a vector.  Every operand still runs along its unit axis; the one partial vector at the end of a
+    // row (extent not a multiple of V) is moved element by element by the workgroups of the ragged last tile.  Elements of 4 or 8 bytes.
+    if (!v.wide && !mixed && esize < 16 && o.tiled_vec) {
+        const int V = 16 / esize > 4 ? 4 : 16 / esize;
+        int vlog = 0;
+        while ((1 << vlog) < V) ++vlog;
+        bool whole = V > 1, ua = V > 1 && o.tiled_uavec && esize >= 4;
+        for (int k = 0; k < c.M && (whole || ua); ++k) {
+            const bool staged = k > 0 && t.staged[k] >= 0;
+            const int j0 = staged ? t.order[k][0] : 0;  // first axis of this operand's enumeration
+            const int d0 = t.tdim[j0];
+            const uintptr_t base = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]);
+            // a direct input that is not unit-stride along dim 0 (broadcast, odd stride) has no V-wide form
+            if (t.tlog[j0] < vlog || c.strides[k][d0] != 1) whole = ua = false;
+            if (c.dims[d0] % V || base % ((size_t)V * esize)) whole = false;
+            for (int d = 0; d < c.N && whole; ++d)
+                if (d != d0 && (c.strides[k][d] % V)) whole = false;
+            if (c.dims[d0] < V || base % esize) ua = false;
+        }
+        if (whole || ua) {
+            v.V = V;
+            v.ua = !whole;
+        }
+    }
+    bool ragged = false;
+    for (int j = 0; j < t.nt; ++j)
+        if (c.dims[t.tdim[j]] & (((i64)1 << t.tlog[j]) - 1)) ragged = true;
+    // ragged extents: the lean kernel plus bounds checks in the workgroups that sit on a last, partly filled tile (round 6; every
+    // ragged problem used to take variant 7 -- lane tables from memory, 64-bit origins, order lookups -- and paid ~2 us for it:
+    // transposes of 7200 x 100 Float64 5.4 us against 3.0 us for 7200 x 128, profiles/r06_ragged_tiles.txt)
+    bool pv = false;  // does some operand's vector axis end in a partial vector?
+    if (v.V > 1)
+        for (int k = 0; k < c.M; ++k) {
+            const int j0 = (k > 0 && t.staged[k] >= 0) ? t.order[k][0] : 0;
+            if (c.dims[t.tdim[j0]] % v.V) pv = true;
+        }
+    if (ragged) v.mode = !t.ord.empty() ? 7 : (pv ? 9 : 1);
+    else v.mode = t.ord.empty() ? 0 : 2;
+    if (!t.origins32) v.mode = 7;  // the lean variants (MODE & 4 == 0) assume 32-bit tile origins over at most TILED_NG grid dims
+    // persistent, software-pipelined form when the work list is longer than the machine holds at once
+    if ((v.mode & 1) == 0 && o.tiled_persist && !t.no_persist && !v.ua) {  // (the persistent form keeps aligned vector accesses)
+        const size_t lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * esize;
+        const i64 grid = t.ord.empty() ? t.grid : (i64)t.ord.size();
+        i64 wpc = std::min<i64>(2048 >> v.thrlog, lds ? (i64)(160 * 1024 / lds) : 8);
+        wpc = std::max<i64>(1, std::min<i64>(wpc, 4));  // measured: 4 workgroups per CU beat 8 and 2
+        if (o.tiled_persist_wpc > 0) wpc = o.tiled_persist_wpc;
+        const i64 cap = (i64)cu_count() * wpc / 8 * 8;
+        if ((i64)(unsigned)grid >= cap * o.tiled_persist_min && cap >= 8) v.pgrid = (unsigned)cap;
+    }
+    return v;
+}
+
 void describe(Plan& plan) {
     const Canon& c = plan.c;
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat"};
@@ -1656,6 +1745,11 @@ void describe(Plan& plan) {
         n += std::snprintf(buf + n, sizeof buf - n, " staged=%d lds=%zu grid=%lld threads=%d", plan.tile.nstaged,
                            plan.tile.lds_bytes, (long long)plan.tile.grid, plan.tile.threads);
         if (!plan.tile.ord.empty()) n += std::snprintf(buf + n, sizeof buf - n, " order=orbits:%d", plan.tile.ord_groups);
+        if (plan.tile.tilelog == 10 || plan.tile.tilelog == 12) {  // as launched with the bases the plan was made with
+            const TiledVariant v = tiled_variant(plan, nullptr, elem_bytes(c), c.mixed && !c.bitcopy);
+            n += std::snprintf(buf + n, sizeof buf - n, " vec=%d%s mode=%d%s%s", v.V, v.ua ? "(element-aligned)" : "", v.mode, v.wide ? " wide" : "",
+                               v.pgrid ? " pipe" : "");
+        }
     } else if (plan.family == FAM_ORBIT) {
         const OrbitPlan& ob = plan.orbit;
         n += std::snprintf(buf + n, sizeof buf - n, " tile=");

@@ -4,7 +4,7 @@ recipe is built to select one family -- STREAM (flat and strided rows), TILED (1
 ragged tiles, reversed dims = wide offsets, persistent form, orbit-major order), ORBIT, GENERIC, REDUCE_ALL,
 REDUCE_PART (ROW / COL / general, split reductions) -- at sizes of 10^5..2*10^6 elements, four element types
 (Float32, Float64, ComplexF32, ComplexF64), NaN-carrying min / max.  HIP path vs the CPU oracle on identical
-inputs; + - * / maps bit for bit, the rest within the reference's tolerance.  The families actually hit are
+inputs; + - * / maps of reals and copies / sums of complex numbers bit for bit, the rest within the reference's tolerance.  The families actually hit are
 counted from smr_plan_describe and printed (>= 200 problems per family)."""
 import collections
 import os
@@ -15,7 +15,7 @@ import pytest
 
 import oraclelib
 import strided_jl_amd as S
-from test_gpu_fuzz import EXPRS, _random_view, dview
+from test_gpu_fuzz import EXPRS, _random_view, bitwise, cx_exact, dview
 from util import fview, rtol
 
 pytestmark = pytest.mark.gpu
@@ -100,16 +100,16 @@ def recipe(name, seed, T):
     elif name == "flat":
         # round 3: unary transposing maps whose flat side has short leading dims with extents that are not powers of two
         # (destination or input flat, ragged tiles along p and q, outer dims, a sub-box offset, conj views, scalar / jit f)
-        UN = [(lambda a: a, 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: a * a - a / 3, 1, True),
-              (lambda a: fn.conj(a) * 3, 1, True), (lambda a, b: a + b, 2, True), (lambda a, b: 2 * a + 3 * b, 2, True), (lambda a, b, c: a * b - c, 3, True)]
+        UN = [(cx_exact(lambda a: a), 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: a * a - a / 3, 1, True),
+              (lambda a: fn.conj(a) * 3, 1, True), (cx_exact(lambda a, b: a + b), 2, True), (lambda a, b: 2 * a + 3 * b, 2, True), (lambda a, b, c: a * b - c, 3, True)]
         f, nin, exact = UN[int(rng0.integers(0, len(UN)))]
         dims = pick([(3, 480, 640), (3, 100, 70, 5), (5, 33, 200), (10, 3, 100, 3, 10), (6, 50, 41, 9), (3, 64, 1000), (7, 7, 300), (12, 40, 130)])
         mkview = None
     elif name == "flat2":
         # round 3: both sides' unit-stride dims are short and not powers of two (two-sided FLAT form); the input's leading dim is drawn
         # among the box dims, so one-sided FLAT, TILED and STREAM plans are mixed in
-        UN = [(lambda a: a, 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: fn.conj(a) * 3, 1, True),
-              (lambda a, b: a + b, 2, True), (lambda a, b: a * 2.5 + b, 2, True), (lambda a, b: 3 * a - b * 0.5, 2, True),
+        UN = [(cx_exact(lambda a: a), 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: fn.conj(a) * 3, 1, True),
+              (cx_exact(lambda a, b: a + b), 2, True), (lambda a, b: a * 2.5 + b, 2, True), (lambda a, b: 3 * a - b * 0.5, 2, True),
               (lambda a, b, c: a + b * c, 3, True)]   # n-ary: ONE input has the other layout, the rest the destination's
         f, nin, exact = UN[int(rng0.integers(0, len(UN)))]
         dims = pick([(5, 60, 50, 7), (17, 9, 33, 31), (3, 100, 90, 3), (7, 30, 40, 9), (6, 16, 16, 16, 5), (12, 10, 14, 9, 11), (10, 50, 60, 10), (31, 65, 33, 17)])
@@ -118,12 +118,12 @@ def recipe(name, seed, T):
     elif name == "flat_batched":
         # round 4: blocks that are contiguous on both sides, in different element orders, one behind the other (batched FLAT form); one time
         # in three the batch grid is permuted as well (the input side then moves block by block)
-        f, nin, exact = pick([(lambda a: a, 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: fn.conj(a) * 3, 1, True)])
+        f, nin, exact = pick([(cx_exact(lambda a: a), 1, True), (lambda a: a * 2.5, 1, True), (lambda a: fn.abs2(a) + 1, 1, True), (lambda a: fn.conj(a) * 3, 1, True)])
         dims = pick([(9, 11, 800), (5, 9, 1600), (3, 4, 5, 1200), (7, 6, 333, 9), (17, 23, 200), (3, 10, 13, 200), (9, 11, 40, 30), (6, 10, 50, 40)])
         mkview = None
     elif name == "flat2_long":
         # round 4: long unit-stride dims with odd extents (two-sided FLAT form with evenly cut leads; forced for these small boxes)
-        UN = [(lambda a: a, 1, True), (lambda a: a * 2.5, 1, True), (lambda a, b: a + b, 2, True), (lambda a, b: 3 * a - b * 0.5, 2, True)]
+        UN = [(cx_exact(lambda a: a), 1, True), (lambda a: a * 2.5, 1, True), (cx_exact(lambda a, b: a + b), 2, True), (lambda a, b: 3 * a - b * 0.5, 2, True)]
         f, nin, exact = UN[int(rng0.integers(0, len(UN)))]
         dims = pick([(257, 129, 9), (301, 75, 11), (513, 65), (129, 257, 5), (131, 67, 3, 5)])
         opts = {"flat2_long": 100}
@@ -242,7 +242,7 @@ def recipe(name, seed, T):
             S._mapreducedim_(f, op, initop, tuple(dims), (out, *ins))
         return out.toarray()
 
-    return run, exact, opts, dict(recipe=name, dims=dims, nin=nin, reduce=reduce_dims, op=op, initop=initop, nan=nan)
+    return run, bitwise(f, exact, T), opts, dict(recipe=name, dims=dims, nin=nin, reduce=reduce_dims, op=op, initop=initop, nan=nan)
 
 
 def _initop_fn(i):
@@ -298,7 +298,7 @@ def test_family_targeted_random_problems_match_the_oracle(name, monkeypatch):
             fam[key] += 1
             msg = f"seed {seed} {np.dtype(T).name} {info} | {d}"
             assert got.shape == want.shape, msg
-            if exact and not np.issubdtype(np.dtype(T), np.complexfloating):
+            if exact:   # (test_gpu_fuzz.bitwise: for complex types the copies and sums)
                 assert np.array_equal(got, want), msg
             else:
                 g, w = got.astype(np.complex128).ravel(), want.astype(np.complex128).ravel()
