@@ -442,6 +442,14 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  *     are converted, have the same number M of distinct operands, the same dtype and conj flag per operand position and the same
  *     f-program including its constants: the kernel is instantiated once, f is ONE functor for the whole launch.  Members may
  *     differ in rank, dims, strides, base pointers and offsets;
+ *   - with SMR_GROUP_MEMBER_SCALARS the VALUES of f's constants may differ as well (C_blk .= a_blk .* permutedims(A_blk, p) .+
+ *     b_blk .* C_blk with a coefficient per block): the members still agree in everything above, in the program's length, every
+ *     (opcode, immediate) pair, the number of constants and the functor f is recognised as.  A member whose constants put it into
+ *     another compute class (a complex scalar among real ones, a non-integer scalar among integer arrays) is refused like any
+ *     member of another class.  Every member keeps the constants of its own canonicalisation in a third device table (one row of
+ *     doubles per member) that its workgroups read next to the descriptor; the kernel is still instantiated once, and a
+ *     runtime-compiled f is compiled once for every set of scalars.  When all members' constants are bit-equal (-0.0 differs from
+ *     0.0) the group is the one planned without the flag.  The scalars are fixed at creation, like the base pointers;
  *   - every member has at most 2^31 - 1 box elements;
  *   - independence: without SMR_GROUP_INDEPENDENT the bounding byte range [lo, hi) of a member's destination must not intersect
  *     the range of ANOTHER member's destination or inputs (the same ranges a recorded sequence compares); a member's destination
@@ -449,18 +457,20 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  *     the CALLER asserts that no member writes an element another member reads or writes.  The flag is the only way to group
  *     interleaved blocks of one parent array, whose byte ranges overlap although their elements do not.
  * smr_group_create and smr_group_layout are host arithmetic only and need no device (like smr_plan_create).  smr_group_prepare
- * uploads the two device tables and compiles + loads the kernel of a runtime-compiled f without launching; the first
+ * uploads the device tables and compiles + loads the kernel of a runtime-compiled f without launching; the first
  * smr_group_execute does the same when prepare was not called (the uploads are synchronous copies: prepare before capturing
  * an execute into a hipGraph).  smr_group_execute is ONE kernel launch, asynchronous on `stream` (NULL = the stream of member 0);
  * its result is bit-identical to smr_mapreduce on each member in order.  The launch goes through HIP; on a library-owned stream
  * (smr_stream_create) it is ordered behind the library's direct launches and the stream's next direct launch waits for it.  The base
  * pointers are fixed at creation (no rebinding).  A caller that executes the same group again and again records it into a sequence
  * (smr_seq_add_group): the replay is then one pre-built packet instead of one launch through HIP.
- * smr_group_describe: one line, "family=group members=K grid=G linear=a transposing=b f=<functor> jit=0/1 bytes=...".
+ * smr_group_describe: one line, "family=group members=K grid=G linear=a transposing=b f=<functor> jit=0/1 bytes=...", under
+ * SMR_GROUP_MEMBER_SCALARS followed by " scalars=member" (a row of constants per member) or " scalars=shared" (they were equal).
  * smr_group_layout: per member 4 values -- form (0 linear, 1 transposing), first workgroup, workgroups, canonical rank; returns
  * 4 * count and writes min(that, cap) values.  The members' workgroup ranges tile [0, grid) in member order.                     */
 typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
+#define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out);
 int smr_group_prepare(smr_group* g);
 int smr_group_execute(smr_group* g, void* stream);

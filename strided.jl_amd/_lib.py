@@ -464,15 +464,18 @@ class Plan:
 
 
 SMR_GROUP_INDEPENDENT = 1
+SMR_GROUP_MEMBER_SCALARS = 2
 
 
 class Group:
     """smr_group handle: K small independent maps (one f, one operand-type signature; rank, dims, strides, pointers and offsets
     of their own) that execute as ONE kernel launch.  `problems` is a sequence of smr_problem; creating a group is host arithmetic
     (no device).  `independent=True` passes SMR_GROUP_INDEPENDENT: the caller asserts that no member writes an element another
-    member reads or writes, and the byte-range check is skipped (interleaved blocks of one parent)."""
+    member reads or writes, and the byte-range check is skipped (interleaved blocks of one parent).  `member_scalars=True` passes
+    SMR_GROUP_MEMBER_SCALARS: the values of f's constants may differ from member to member (a coefficient per block); the program,
+    the number of constants and the compute class they lead to must still be those of member 0."""
 
-    def __init__(self, problems, independent: bool = False, keepalive=()):
+    def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False):
         self._lib = load()
         self._h = C.c_void_p()
         self.count = len(problems)
@@ -480,7 +483,8 @@ class Group:
         for i, p in enumerate(problems):
             C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(smr_problem))
         self._keep = (arr, problems, keepalive)
-        check(self._lib.smr_group_create(arr, self.count, SMR_GROUP_INDEPENDENT if independent else 0, C.byref(self._h)))
+        flags = (SMR_GROUP_INDEPENDENT if independent else 0) | (SMR_GROUP_MEMBER_SCALARS if member_scalars else 0)
+        check(self._lib.smr_group_create(arr, self.count, flags, C.byref(self._h)))
 
     def execute(self, stream: int | None = None):
         check(self._lib.smr_group_execute(self._h, C.c_void_p(stream or 0)))

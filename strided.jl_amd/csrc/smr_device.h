@@ -610,6 +610,13 @@ SMR_DEV void store_op(const OpTab& t, i64 idx, T v) {
 
 // ---- functors: f(a[0..NIN-1]) ---------------------------------------------------------------
 // NIN < 0 means "runtime" (interpreter).  Constants come from Canon::fc.
+// A functor with constants also takes them on the device: set_consts(k) rebuilds them from a row of doubles laid out like
+// Canon::fc (a program: like ProgD::consts), converted as hostmk<T> converts on the host.  A grouped launch whose members have
+// scalars of their own (smr_k_group.hip) calls it with the member's row; P is a pointer to double in any address space.
+template <class T, class P> SMR_DEV T mk_const(P k, int i) {
+    typedef typename tr<T>::real R;
+    return mk<T>(rcast<R>(k[2 * i]), rcast<R>(k[2 * i + 1]));
+}
 template <class T> struct FIdent {
     static constexpr int NIN = 1;
     SMR_DEV T operator()(const T* a) const { return a[0]; }
@@ -629,21 +636,25 @@ template <class T> struct FAdd4 {
 template <class T> struct FScale {
     static constexpr int NIN = 1;
     T c;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
     SMR_DEV T operator()(const T* a) const { return a[0] * c; }
 };
 template <class T> struct FSym {
     static constexpr int NIN = 2;
     T c;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
     SMR_DEV T operator()(const T* a) const { return mathx<T>::bin(SMR_OP_DIV, a[0] + a[1], c); }
 };
 template <class T> struct FAxpy {
     static constexpr int NIN = 2;
     T c;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
     SMR_DEV T operator()(const T* a) const { return c * a[0] + a[1]; }
 };
 template <class T> struct FAxpby {
     static constexpr int NIN = 2;
     T c, d;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); d = mk_const<T>(k, 1); }
     SMR_DEV T operator()(const T* a) const { return c * a[0] + d * a[1]; }
 };
 template <class T> struct FAbs2 {
@@ -657,6 +668,7 @@ template <class T> struct FMul2 {
 template <class T> struct FExpr5 {  // a*exp(c*a) + sin(a*a), real types only
     static constexpr int NIN = 1;
     T c;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
     SMR_DEV T operator()(const T* a) const {
         T x = a[0];
         if constexpr (is_int_class<T>::value) return x;  // never selected for the integer class
@@ -670,6 +682,11 @@ template <class T> struct FExpr5 {  // a*exp(c*a) + sin(a*a), real types only
 template <class T> struct FProg {
     static constexpr int NIN = -1;
     ProgD p;
+    template <class P> SMR_DEV void set_consts(P k) {  // the row holds 2 * nconst doubles, no more
+#pragma unroll
+        for (int i = 0; i < 2 * SMR_MAXCONST; ++i)
+            if (i < 2 * p.nconst) p.consts[i] = k[i];
+    }
     SMR_DEV T operator()(const T* a) const {
         typedef typename tr<T>::real R;
         T s0 = mk<T>(R(0), R(0)), s1 = s0, s2 = s0, s3 = s0, s4 = s0, s5 = s0, s6 = s0, s7 = s0;

@@ -2,7 +2,8 @@
 // A group is K independent small maps that share one functor f and one operand-type signature and differ in rank, dims, strides,
 // base pointers and offsets; smr_group_execute runs them as ONE launch of the kernel in smr_k_group.hip.  Planning is host
 // arithmetic: every member is canonicalised like a single call, checked against member 0, given one of the kernel's two bodies and
-// a contiguous range of workgroups.  The device tables are uploaded by smr_group_prepare or the first execution.  The planner also
+// a contiguous range of workgroups.  Under SMR_GROUP_MEMBER_SCALARS the values of f's constants may differ: every member keeps the
+// constants of its own canonicalisation as a row of a third table.  The device tables are uploaded by smr_group_prepare or the first execution.  The planner also
 // keeps the byte ranges one execution reads and writes: the footprint of a group recorded in a sequence (smr_seq_add_group).
 #include <algorithm>
 #include <cstdio>
@@ -28,7 +29,8 @@ namespace {
 std::string member_tag(int i) { return "smr_group_create: member " + std::to_string(i); }
 
 // does member `c` run the same kernel instantiation with the same functor as member 0 (`r`)?  Empty = yes, else what differs.
-std::string mismatch(const Canon& r, const Canon& c) {
+// `own_scalars` (SMR_GROUP_MEMBER_SCALARS): the values of f's constants may differ, nothing else.
+std::string mismatch(const Canon& r, const Canon& c, bool own_scalars) {
     if (c.bitcopy != r.bitcopy || (!c.bitcopy && c.ct != r.ct)) return "computes in another class than member 0";
     if (c.mixed != r.mixed) return "differs from member 0 in whether operand types are converted";
     if (c.M != r.M) return "has another number of distinct operands than member 0 (" + std::to_string(c.M) + " != " + std::to_string(r.M) + ")";
@@ -38,9 +40,23 @@ std::string mismatch(const Canon& r, const Canon& c) {
     }
     const ProgD &p = c.prog, &q = r.prog;
     if (p.len != q.len || p.nconst != q.nconst || std::memcmp(p.code, q.code, (size_t)(2 * p.len)) != 0 ||
-        std::memcmp(p.consts, q.consts, sizeof(double) * (size_t)(2 * p.nconst)) != 0)
-        return "has another f (program or constants) than member 0";
+        (!own_scalars && std::memcmp(p.consts, q.consts, sizeof(double) * (size_t)(2 * p.nconst)) != 0))
+        return own_scalars ? "has another f-program than member 0 (only the values of its constants may differ)" : "has another f (program or constants) than member 0";
+    // recognition (smr_canon.cpp) looks at the program's structure, FK_EXPR5 also at a constant's value: one launch runs ONE functor
+    if (own_scalars && c.fkind != r.fkind) return "is recognised as another functor than member 0";
     return std::string();
+}
+
+// does the launch run a natively compiled functor that keeps constants in fields (with_functor, smr_dispatch.h)?  Its per-member
+// row is Canon::fc; every other f with constants is a program (runtime-compiled or interpreted) and its row is ProgD::consts.
+bool native_with_consts(const Canon& c) {
+    if (c.bitcopy || c.mixed || !(GROUP_FMASK & fbit(c.fkind))) return false;
+    switch (c.fkind) {
+        case FK_SCALE: case FK_AXPY: case FK_AXPBY: return true;
+        case FK_SYM: return c.ct != SMR_I64;
+        case FK_EXPR5: return c.ct == SMR_F32 || c.ct == SMR_F64;
+        default: return false;
+    }
 }
 
 // picks the body of one member and fills its descriptor; returns its number of workgroups
@@ -171,6 +187,9 @@ int ensure_tables(const GroupPlan& g) {
     if (!g.d_first) {
         if (int rc = upload_table(&g.d_first, g.first_wg.data(), g.first_wg.size() * sizeof(uint32_t), "group workgroup ranges")) return rc;
     }
+    if (g.varc && !g.d_consts) {
+        if (int rc = upload_table(&g.d_consts, g.consts.data(), g.consts.size() * sizeof(double), "group member scalars")) return rc;
+    }
     return SMR_OK;
 }
 
@@ -208,7 +227,7 @@ extern "C" {
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
     if (!members || !out) return set_error(SMR_EINVAL, "smr_group_create: null argument");
     if (count < 1 || count > 65535) return set_error(SMR_EINVAL, "smr_group_create: count must be 1..65535");
-    if (flags & ~SMR_GROUP_INDEPENDENT) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
+    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
     smr_group* h = new (std::nothrow) smr_group();
     if (!h) return set_error(SMR_ENOMEM, "out of host memory");
     GroupPlan& g = h->plan;
@@ -219,6 +238,8 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
     Spans rd, wr;
     i64 grid = 0;
     int rc = SMR_OK;
+    const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0;
+    bool native_row = false;
     for (int i = 0; i < count && rc == SMR_OK; ++i) {
         const smr_problem& p = members[i];
         if (p.redop != SMR_RED_NONE) {
@@ -233,7 +254,7 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
             break;
         }
         if (i > 0) {
-            const std::string why = mismatch(g.c, c);
+            const std::string why = mismatch(g.c, c, own_scalars);
             if (!why.empty()) {
                 rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
                 break;
@@ -242,6 +263,14 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
         if (c.total > 0x7fffffffLL) {
             rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " has more than 2^31 - 1 box elements");
             break;
+        }
+        if (own_scalars) {  // the member's row of the constant table: what its own canonicalisation handed the functor
+            if (i == 0) {
+                native_row = native_with_consts(c);
+                g.W = native_row ? 4 : (c.bitcopy ? 0 : 2 * c.prog.nconst);
+            }
+            const double* row = native_row ? c.fc : c.prog.consts;
+            g.consts.insert(g.consts.end(), row, row + g.W);
         }
         const i64 wgs = plan_member(c, g.members[(size_t)i]);
         g.rank[(size_t)i] = c.N;
@@ -270,14 +299,24 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
         return rc;
     }
     h->stream = members[0].stream;
+    if (own_scalars) {
+        // bit-equal rows (-0.0 differs from 0.0): the group is the one the call without the flag plans, no third table
+        const size_t row = sizeof(double) * (size_t)g.W;
+        for (int i = 1; i < count && !g.varc; ++i) g.varc = row && std::memcmp(g.consts.data(), g.consts.data() + (size_t)i * g.W, row) != 0;
+        if (!g.varc) {
+            std::vector<double>().swap(g.consts);
+            g.W = 0;
+        }
+    }
     g.rd = merged(std::move(rd));
     g.wr = merged(std::move(wr));
     // what launch_group_ct() does: with_prog (runtime compilation first) for a mixed group and for an f without a native functor.
     // FK_PROG has a bit in GROUP_FMASK like every kind, so the mask alone does not tell
     g.jit = options().jit && !g.c.bitcopy && (g.c.mixed || g.c.fkind == FK_PROG || !(GROUP_FMASK & fbit(g.c.fkind)));
     char buf[256];
-    std::snprintf(buf, sizeof buf, "family=group members=%d grid=%lld linear=%d transposing=%d f=%s jit=%d bytes=%lld%s", count, (long long)grid,
-                  g.nlinear, g.ntrans, functor_name(g.c), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "");
+    std::snprintf(buf, sizeof buf, "family=group members=%d grid=%lld linear=%d transposing=%d f=%s jit=%d bytes=%lld%s%s", count, (long long)grid,
+                  g.nlinear, g.ntrans, functor_name(g.c), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "",
+                  own_scalars ? (g.varc ? " scalars=member" : " scalars=shared") : "");
     g.desc = buf;
     *out = h;
     return SMR_OK;
@@ -332,11 +371,12 @@ int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap) {
 
 int smr_group_destroy(smr_group* g) {
     if (!g) return SMR_OK;
-    if (g->plan.d_members || g->plan.d_first) {
+    if (g->plan.d_members || g->plan.d_first || g->plan.d_consts) {
         (void)eager_fence_if_active();
         (void)hipDeviceSynchronize();  // a queued launch may still read the tables
         if (g->plan.d_members) (void)hipFree(g->plan.d_members);
         if (g->plan.d_first) (void)hipFree(g->plan.d_first);
+        if (g->plan.d_consts) (void)hipFree(g->plan.d_consts);
         (void)hipGetLastError();
     }
     delete g;

@@ -34,7 +34,8 @@ struct GroupMemberD {
 // runtime-compiled, or interpreted, as in GENERIC
 constexpr unsigned GROUP_FMASK = 0xffffffffu;
 
-// A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member.
+// A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
+// (the values of the program's constants too, unless `varc`).
 struct GroupPlan {
     Canon c;
     std::vector<GroupMemberD> members;
@@ -47,10 +48,16 @@ struct GroupPlan {
     // what one execution reads (every input of every member) and writes (every destination): operand_span() ranges, sorted, with
     // overlapping and adjacent ones merged -- the footprint of a group recorded in a sequence (smr_seq_add_group)
     std::vector<std::pair<uintptr_t, uintptr_t>> rd, wr;
-    // device copies of `members` and `first_wg`, uploaded by prepare / the first execution
+    // per-member scalars (SMR_GROUP_MEMBER_SCALARS and constants that do differ): row i holds member i's W doubles, Canon::fc
+    // (W = 4) for a recognised functor, ProgD::consts (W = 2 * nconst) for a program
+    bool varc = false;
+    int W = 0;
+    std::vector<double> consts;
+    // device copies of `members`, `first_wg` and `consts`, uploaded by prepare / the first execution
     mutable std::mutex build_mu;
     mutable void* d_members = nullptr;
     mutable void* d_first = nullptr;
+    mutable void* d_consts = nullptr;
 };
 
 template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);

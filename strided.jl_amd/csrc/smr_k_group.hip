@@ -12,7 +12,15 @@
 //                pass through LDS (rows padded to 33 elements: the column reads of 4-, 8- and 16-byte elements are free of bank
 //                conflicts), ragged edges guarded, outer dims decomposed from the tile index, other inputs read directly.
 // Loads and stores go through load_op / store_op: conj, mixed dtypes and bit copies behave as in GENERIC.
+// Per-member scalars (VARC, SMR_GROUP_MEMBER_SCALARS): f's constants differ from member to member.  A third table holds one row
+// of W doubles per member (Canon::fc for a recognised functor, ProgD::consts for a program); the workgroup reads its member's row
+// by scalar loads like the descriptor and rebuilds the functor's constants from it (set_consts, smr_device.h) before any data
+// load.  Without VARC the functor is the kernel argument as it came: one f for the whole launch.
 // Compiled once per compute type (-DSMR_CT=n).
+#ifndef SMR_JIT
+#include <utility>
+#endif
+
 #include "smr_dispatch.h"
 #include "smr_group.h"
 
@@ -22,10 +30,11 @@
 
 namespace smr {
 
-// The two tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
+// The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
 // space they are fetched by scalar loads into scalar registers, not once per lane.
 typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
 typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
+typedef const double __attribute__((address_space(4))) GroupConstC;
 
 struct GroupArgs {
     const GroupMemberD* members;
@@ -34,9 +43,11 @@ struct GroupArgs {
     int32_t dtype[MAXM];
     int32_t conj[MAXM];
     uint32_t wg0;              // first workgroup of this launch within the group (0: the launch is the whole group)
+    int32_t W;                 // VARC: doubles per row of `consts` (behind wg0, which keeps its place in the kernarg segment)
+    const double* consts;      // VARC: count rows of f's constants, one per member (null otherwise)
 };
 
-template <class T, class F, bool MIXED>
+template <class T, class F, bool MIXED, bool VARC = false>
 SMR_DEV void group_body(const GroupArgs a, F f) {
     __shared__ T tile[GROUP_TILE * (GROUP_TILE + 1)];
     const int nin = (F::NIN >= 0) ? F::NIN : a.M - 1;
@@ -51,6 +62,7 @@ SMR_DEV void group_body(const GroupArgs a, F f) {
     }
     GroupMemberC& m = ((GroupMemberC*)a.members)[lo];
     const uint32_t w = b - first_wg[lo];
+    if constexpr (VARC) f.set_consts((GroupConstC*)a.consts + (i64)lo * a.W);
     OpTab t;
 #pragma unroll
     for (int k = 0; k < MAXM; ++k) {
@@ -184,6 +196,15 @@ __global__ void __launch_bounds__(256) k_group(GroupArgs a, F f) {
 }
 
 template <class T, class F, bool MIXED>
+__global__ void __launch_bounds__(256) k_group_varc(GroupArgs a, F f) {
+    group_body<T, F, MIXED, true>(a, f);
+}
+
+// does F take constants on the device (set_consts)?  Only such a functor has a VARC instantiation
+template <class F, class = void> struct takes_consts { static constexpr bool value = false; };
+template <class F> struct takes_consts<F, decltype(std::declval<F&>().set_consts((const double*)nullptr))> { static constexpr bool value = true; };
+
+template <class T, class F, bool MIXED>
 static int go(const GroupPlan& g, hipStream_t s, F f) {
     const Canon& c = g.c;
     GroupArgs a;
@@ -196,14 +217,25 @@ static int go(const GroupPlan& g, hipStream_t s, F f) {
         a.conj[k] = k < c.M ? c.conj[k] : 0;
     }
     a.wg0 = 0;
+    a.W = g.varc ? g.W : 0;
+    a.consts = g.varc ? (const double*)g.d_consts : nullptr;
     const unsigned grid = g.first_wg.back();
     // the members are independent and a workgroup serves one member: any contiguous block range can be launched on its own.  `a` is
     // the first kernel parameter of k_group and of the runtime-compiled entry alike, so wg0 has one kernarg offset in both
     mark_sliceable(1, (unsigned)offsetof(GroupArgs, wg0), 0);
-    if constexpr (is_jit<F>::value)
+    if constexpr (is_jit<F>::value) {
+        // the kernel argument kc holds member 0's constants and goes unused under VARC; the text depends on f's structure only
+        if (g.varc) return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED, true);
         return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED);
-    else
+    } else {
+        if constexpr (takes_consts<F>::value) {
+            if (g.varc)
+                return launch_native(nullptr, 0, "k_group_varc", [&] { SMR_LAUNCH((k_group_varc<T, F, MIXED>), dim3(grid), dim3(256), 0, s, a, f); });
+        } else if (g.varc) {
+            return set_error(SMR_EINVAL, "group: per-member scalars planned for an f without constants");
+        }
         return launch_native(nullptr, 0, "k_group", [&] { SMR_LAUNCH((k_group<T, F, MIXED>), dim3(grid), dim3(256), 0, s, a, f); });
+    }
 }
 
 template <>

@@ -12,6 +12,7 @@ from __future__ import annotations
 import builtins
 import collections
 import ctypes as C
+import math
 import operator
 import threading
 
@@ -320,7 +321,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, stream); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream); least recently used first
 
 
 def _byte_range(a):
@@ -352,12 +353,21 @@ def _member_bytes(arrays):
     return builtins.sum(foot.values())  # (this module defines its own `sum`)
 
 
+def _integer_valued(v) -> bool:
+    """Does the integer class take this constant (csrc/smr_canon.cpp: integer-valued within Int64, or an infinite seed)?"""
+    v = complex(v)
+    if v.imag != 0:
+        return False
+    r = v.real
+    return math.isinf(r) or (r == math.floor(r) and abs(r) <= 9223372036854775808.0) if not math.isnan(r) else False
+
+
 class _Deferred:
     __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key")
 
 
 class group:
-    """`with S.group(independent=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    """`with S.group(independent=False, member_scalars=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
     `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
@@ -368,12 +378,19 @@ class group:
         then run as usual;
       * a bucket the library refuses as a group (smr_group_create: SMR_EUNSUPPORTED) runs call by call through the normal path;
         an error a single call would have raised at once is raised at the flush instead.
+    `member_scalars=True` (SMR_GROUP_MEMBER_SCALARS): the VALUES of f's captured scalars leave the bucket key, so that
+    `axpby_(a_i, X_i, b_i, Y_i)` with a coefficient per block is one launch; every member still computes with its own scalars.
+    What the values decide in the library stays in the key: how many constants there are, whether any has an imaginary part and
+    whether all are integer-valued (the compute class).  Equal captured values are ONE constant of the f-program (expr.py merges
+    them): `a*X + a*Y` is another program than `a*X + b*Y`, and the `linalg` fronts choose another f for alpha = 1 and for
+    beta = 0 or 1 -- such calls land in buckets of their own, correctly.
     `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
 
     MAX_PENDING = 4096
 
-    def __init__(self, independent: bool = False):
+    def __init__(self, independent: bool = False, member_scalars: bool = False):
         self.independent = bool(independent)
+        self.member_scalars = bool(member_scalars)
         self.pending = []
         self.groups = []
         self.singles = 0
@@ -428,7 +445,11 @@ class group:
         # another kernel signature, and one bucket of them would be refused as a group
         ops = [(a._base, a.offset, a.op, tuple(st for d, st in zip(c.dims, a.strides) if d != 1)) for a in arrays[1:]]
         same = tuple(ops.index(o) for o in ops)
-        c.bucket = (bytes(code), tuple(consts), tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream)
+        if self.member_scalars:  # not the values, only what they decide in canonicalise(): count, complex or not, integer class or not
+            ck = (len(consts), any(v.imag != 0 for v in consts), all(_integer_valued(v) for v in consts))
+        else:
+            ck = tuple(consts)
+        c.bucket = (bytes(code), ck, tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream)
         c.wr = _byte_range(arrays[0])
         c.rd = [_byte_range(a) for a in arrays[1:]]
         c.key = _problem_key(f, None, None, c.dims, arrays)
@@ -450,7 +471,7 @@ class group:
     def _launch(self, calls, stream):
         key = None
         if all(c.key is not None for c in calls):
-            key = (tuple(c.key for c in calls), self.independent, stream)
+            key = (tuple(c.key for c in calls), self.independent, self.member_scalars, stream)
         grp = None
         if key is not None:
             try:
@@ -461,7 +482,7 @@ class group:
             built = [build_problem(c.f, None, None, c.dims, c.arrays, stream=stream) for c in calls]
             try:
                 # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
-                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built])
+                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=self.member_scalars)
             except L.UnsupportedOnDevice:
                 for c in calls:
                     self._single(c)
