@@ -239,6 +239,7 @@ struct ReducePlan {
     int col_tx = 0, col_v = 1; // COL, exact lane map (round 6): lanes along kept dim 0 (0 = the power of two above), valid for this vector width
     int col_y0 = 1, col_y1 = 1; //   rows of a workgroup along the inner reduced dim x along the outer index (TY = 256 / tx = y0 * y1)
     int xsplit = 1, qsplit = 1;  // split of the inner / outer reduced range over workgroups
+    int narrowed = 0;            // COL: the row segment was narrowed to put more workgroups along the kept dims (describe() says so)
 };
 
 struct Plan {

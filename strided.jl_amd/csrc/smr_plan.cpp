@@ -1356,6 +1356,7 @@ static void plan_part_col(const Canon& c, const PartShape& s, ReducePlan& rp) {
     // rows to each -- when that makes the split unnecessary it saves the partials and the second launch
     // (sum(A; dims=2) of 512x384x64 f32: 16.0 -> 12.4 us, 256^3: 18.4 -> 14.7 us, tools/reduce_sweep.py)
     auto kb_at = [&](int t) { return ((K0 + (((i64)vmax) << t) - 1) / (((i64)vmax) << t)) * (c.nout / K0); };
+    const int narrowed_from = txlog;
     if (o.reduce_col_narrow && kb_at(txlog) < o.reduce_part_wgs) {
         int fill = -1;  // the widest segment that still puts a workgroup on every CU (round 6)
         const int t0 = txlog;
@@ -1373,6 +1374,7 @@ static void plan_part_col(const Canon& c, const PartShape& s, ReducePlan& rp) {
         if (txlog == t0 && fill >= 0 && o.reduce_col_narrow >= 1 && kb_at(t0) < 256) txlog = fill;
     }
     rp.txlog = txlog;
+    rp.narrowed = narrowed_from > txlog ? 1 : 0;
     const int tylog = 8 - txlog;
     rp.g0log = std::min(tylog, ceil_log2(L0));
     rp.g1log = tylog - rp.g0log;
@@ -1786,6 +1788,13 @@ void describe(Plan& plan) {
         static const char* folds[] = {"epilogue", "in-launch", "second-launch"};
         const RedLaunch r = reduce_launch(plan, nullptr, true);
         n += std::snprintf(buf + n, sizeof buf - n, " vec=%d fold=%s", r.vec, folds[r.fold]);
+        // ROW / COL: how a split reduction is cut (xsplit along the inner reduced dim x qsplit along the outer reduced index; the tokens must not
+        // contain "split=", which tests match); COL: lanes along kept dim 0 as launched
+        if (plan.family == FAM_REDUCE_PART && plan.red.kind != 0) {
+            n += std::snprintf(buf + n, sizeof buf - n, " xcut=%d qcut=%d", r.nparts > 1 ? plan.red.xsplit : 1, r.nparts > 1 ? plan.red.qsplit : 1);
+            // (narrowed): the launched lanes along kept dim 0 are the segment plan_part_col narrowed -- not said when an exact lane map replaces it
+            if (plan.red.kind == 2) n += std::snprintf(buf + n, sizeof buf - n, " tx=%d%s", r.ctx, (plan.red.narrowed && r.ctx == (1 << plan.red.txlog)) ? "(narrowed)" : "");
+        }
     }
     if (c.int_wraps) n += std::snprintf(buf + n, sizeof buf - n, " int_wraps=%d", c.int_wraps);
     std::snprintf(buf + n, sizeof buf - n, " algbytes=%lld", (long long)c.algbytes);

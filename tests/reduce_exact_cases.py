@@ -81,6 +81,7 @@ class Case:
     options: dict = field(default_factory=dict)
     expect: tuple = ()
     note: str = ""
+    wants: dict = None                      # reduce_fuzz_cases.py: times -> destination elements after that many applications of the call
 
     @property
     def oshape(self):
@@ -90,10 +91,11 @@ class Case:
     def nelem(self):
         return int(np.prod(self.dims))
 
-    def expected_parent(self):
-        """The destination parent as it must be after the call."""
+    def expected_parent(self, times=1):
+        """The destination parent as it must be after `times` applications of the call onto the same destination (more than one:
+        cases that carry `wants`, computed like `want` in exact arithmetic)."""
         out = self.dest.parent.copy()
-        w = self.want
+        w = self.want if times == 1 else self.wants[times]
         if self.dest.conj:
             w = np.conj(w)
         out[_index(self.dest.offset, self.oshape, self._ostrides())] = w
@@ -102,9 +104,9 @@ class Case:
     def _ostrides(self):
         return tuple(0 if d in self.rdims else s for d, s in enumerate(self.dest.strides))
 
-    def mismatch(self, got_parent):
-        """None when `got_parent` (the destination's whole parent after the call) is right, else a message."""
-        want = self.expected_parent()
+    def mismatch(self, got_parent, times=1):
+        """None when `got_parent` (the destination's whole parent after `times` applications of the call) is right, else a message."""
+        want = self.expected_parent(times)
         idx = _index(self.dest.offset, self.oshape, self._ostrides()).ravel()
         nanpos = idx[np.isnan(want[idx].astype(np.complex128))] if np.dtype(self.dest.dtype) != np.bool_ else idx[:0]
         gb = got_parent.copy()
@@ -120,8 +122,9 @@ class Case:
             return None
         es = np.dtype(self.dest.dtype).itemsize
         bad = np.unique(np.nonzero(g8 != w8)[0] // es)
-        inside = [int(i) for i in bad if i in set(idx.tolist())]
-        outside = [int(i) for i in bad if i not in set(idx.tolist())]
+        mine = set(idx.tolist())
+        inside = [int(i) for i in bad if i in mine]
+        outside = [int(i) for i in bad if i not in mine]
         msg = f"{self.name}:"
         if inside:
             msg += f" elements at parent index {inside[:4]}: got {gb[inside[:4]].tolist()} want {wb[inside[:4]].tolist()};"
