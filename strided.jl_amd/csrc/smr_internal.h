@@ -377,11 +377,11 @@ struct RedLaunch {
     i64 groups = 0;       // REDUCE_PART: workgroups along the outputs
     int ctx = 0, cty = 0, cy0 = 0, cy1 = 0;  // COL: lanes along kept dim 0 x rows (cy0 along the inner reduced dim x cy1 along q)
 };
-RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch);
+RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch);  // smr_plan_reduce.cpp
 
 // TILED: the kernel variant one execution launches for the given operand bases (nullptr: the bases the plan was made with), elements
 // of `esize` bytes and MIXED operand types or not.  The launcher (smr_k_tiled.hip: go, go_tl, go3) dispatches on it and describe()
-// prints it; the rules live in tiled_variant() alone (smr_plan.cpp).
+// prints it; the rules live in tiled_variant() alone (smr_plan_tiled.cpp).
 struct TiledVariant {
     int V = 1;          // elements per global access (V * esize <= 16 bytes)
     bool ua = false;    // ... at element alignment: odd extents, odd row strides, views that begin inside a vector

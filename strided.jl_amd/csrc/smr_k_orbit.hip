@@ -14,7 +14,7 @@
 //   * outputs leave in the same natural order (the destination has the identity view's strides).
 // Every element of the buffer crosses L1 once instead of once per view, and an in-place update
 // (destination = the buffer) is safe: an orbit is read completely before it is written, and orbits are
-// disjoint.  Orbits are executed super-cell by super-cell in XCD-contiguous runs (smr_plan.cpp:
+// disjoint.  Orbits are executed super-cell by super-cell in XCD-contiguous runs (smr_plan_orbit.cpp:
 // plan_orbit), so the partner halves of 64-B runs meet in one XCD's L2.
 // All index arithmetic is bit slicing of the lane id with kernel-argument shifts (no lane tables, no
 // dependent memory round trip before the first global load).
@@ -222,7 +222,7 @@ SMR_DEV void orbit_map_body(const OrbitArgs a, const OrbitHead h, F f) {
     uint32_t tilelog = (uint32_t)a.tilelog;
     asm volatile("" : "+s"(tilelog));
     // the LDS slot every (output slot, view) pair reads from: fields of this workgroup's row (orbits that share a workgroup have
-    // their own little maps: smr_plan.cpp, plan_orbit)
+    // their own little maps: smr_plan_orbit.cpp, plan_orbit)
     auto slot_bases = [&](uint64_t mp) {
 #pragma unroll
         for (int k = 0; k < NK; ++k)
@@ -959,7 +959,7 @@ static int go2(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
             // travels to the memory side on its own and 64-byte pieces pay: replay of the 4-way sum at 32^4 4.72 -> 4.31 us on one queue,
             // 3.66 -> 3.04 cut in two, bench step 5.65 -> 5.2 us -- plain-store launches through HIP 4.40 -> 4.27 us.  (With the first
             // work list -- an orbit's smallest tile paired with whatever sat next to it -- the form LOST through HIP, 4.72 us: the list
-            // matters as much as the kernel, smr_plan.cpp.)  orbit_pair = 0 switches the form off (tests, tools/cold_orbit_sweep.py).
+            // matters as much as the kernel, smr_plan_orbit.cpp.)  orbit_pair = 0 switches the form off (tests, tools/cold_orbit_sweep.py).
             if (o.pair_ok && own0 && o.ng == 4 && plan.c.M - 1 == F::NIN && options().orbit_pair >= 1)
                 return go_pair<T, F>(plan, s, f, tab);
         }

@@ -869,7 +869,7 @@ static int go_all(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     RedArgs a;
     fill_args(plan, bases, a);
     a.linear = (c.N == 1) ? 1 : 0;
-    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width and fold form (smr_plan.cpp)
+    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width and fold form (smr_plan_reduce.cpp)
     const int blocks = r.nparts;
     a.nparts = blocks;
     a.single = r.fold == RED_FOLD_IN_LAUNCH ? 1 : 0;
@@ -906,7 +906,7 @@ static int launch_part(const Canon& c, const RedArgs& a, i64 blocks, hipStream_t
     }
 }
 
-// Fills the arguments of a partial reduction as reduce_launch() (smr_plan.cpp) says this execution runs: chunks per output, fold form,
+// Fills the arguments of a partial reduction as reduce_launch() (smr_plan_reduce.cpp) says this execution runs: chunks per output, fold form,
 // vector width and -- COL -- the lane map.
 // (tests/reduce_fuzz_cases.py: empty_chunks() restates chunk, xchunk and qchunk from describe()'s tokens to count the cases whose trailing
 // chunks are empty: a change of the rounding here must be made there too.)
@@ -955,7 +955,7 @@ static int build_part_args(const Plan& plan, void* const* bases, const RedLaunch
 template <class T, class F, bool MIXED>
 static int go_part(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     const Canon& c = plan.c;
-    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width, fold form, groups (smr_plan.cpp)
+    const RedLaunch r = reduce_launch(plan, bases, plan.scratch != nullptr);  // vector width, fold form, groups (smr_plan_reduce.cpp)
     RedArgs a;
     if (int rc = build_part_args(plan, bases, r, a)) return rc;
     const i64 blocks = r.groups * r.nparts;

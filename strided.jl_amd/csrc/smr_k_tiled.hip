@@ -17,7 +17,7 @@
 // Variants: the classic form runs one tile per workgroup (tiled_map_body; MODE selects at compile
 // time which rarely needed features it carries); long work lists use the persistent,
 // software-pipelined form (tiled_map_pipe_body).  Tiles are visited in the planner's order
-// (smr_plan.cpp: plan_tile_order -- orbit-major when several inputs are permuted views of one
+// (smr_plan_tiled.cpp: plan_tile_order -- orbit-major when several inputs are permuted views of one
 // buffer, so that they meet in one XCD's L2).
 //
 // Index arithmetic.  Tile extents are powers of two, so the position e of an element inside a
@@ -207,7 +207,7 @@ SMR_DEV void tiled_map_body(const TiledArgs<WIDE> a, F f) {
     // ---- which tile ---------------------------------------------------------------------------------
     uint32_t b = blockIdx.x + a.blk0;
     if constexpr (ORD) {
-        // locality-aware tile order (smr_plan.cpp: plan_tile_order).  The in-kernarg lookup is
+        // locality-aware tile order (smr_plan_tiled.cpp: plan_tile_order).  The in-kernarg lookup is
         // issued unconditionally so that it travels with the first batch of scalar loads.
         const uint32_t pair = a.ord16[(b & (NORD16 - 1)) >> 1];
         if (a.ordmode == 1) {
@@ -1188,7 +1188,7 @@ static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const Ti
     return launch();
 }
 
-// The kernel of tiled_variant()'s choice (smr_plan.cpp): MODE here, 64-bit offsets, vector width and threads in go_tl and go.
+// The kernel of tiled_variant()'s choice (smr_plan_tiled.cpp): MODE here, 64-bit offsets, vector width and threads in go_tl and go.
 template <class T, class F, bool MIXED, bool WIDE, int V, int THRLOG>
 static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const TiledVariant& tv) {
     if constexpr (V > 1) {
@@ -1351,7 +1351,7 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
         if (rc != SMR_EUNSUPPORTED) return rc;
     }
     if (t.tilelog != 10 && t.tilelog != 12) return set_error(SMR_EINVAL, "tiled: the planner must pick 1024- or 4096-element tiles");
-    const TiledVariant tv = tiled_variant(plan, bases, (int)sizeof(T), MIXED);  // smr_plan.cpp: describe() prints the same choice
+    const TiledVariant tv = tiled_variant(plan, bases, (int)sizeof(T), MIXED);  // smr_plan_tiled.cpp: describe() prints the same choice
     if (tv.thrlog == 8) return go_tl<T, F, MIXED, 8>(plan, s, f, tab, tv);
     return go_tl<T, F, MIXED, 10>(plan, s, f, tab, tv);
 }

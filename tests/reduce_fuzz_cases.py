@@ -923,7 +923,7 @@ CT_VMAX = {"f32": 4, "f64": 2, "c32": 2, "c64": 1, "i64": 2}   # elements per 16
 
 def empty_chunks(desc):
     """does the cut of a split partial reduction leave trailing chunks without elements?  This restates the chunk sizes of build_part_args
-    (smr_k_reduce.hip) and g0log of plan_part_row (smr_plan.cpp) from describe()'s tokens; a note there points back here."""
+    (smr_k_reduce.hip) and g0log of plan_part_row (smr_plan_reduce.cpp) from describe()'s tokens; a note there points back here."""
     split = int(token(desc, "split") or 1)
     if token(desc, "family") != "reduce_part" or split == 1 or token(desc, "fold") == "epilogue":
         return False

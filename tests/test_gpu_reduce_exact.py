@@ -4,7 +4,7 @@ The cases come from reduce_exact_cases.py (checked on the CPU oracle by test_red
 bounded so that any reduction order gives the same bits, products of powers of two, min / max with planted extremes, NaN,
 signed zeros and Inf.  Every case must match the table bit for bit, leave every byte of the destination's parent outside
 its elements unchanged, and run on the kernel path the table names -- checked through describe(), which reports the
-vector width and the fold form the launch takes (smr_plan.cpp: reduce_launch).  Then determinism (order-sensitive random
+vector width and the fold form the launch takes (smr_plan_reduce.cpp: reduce_launch).  Then determinism (order-sensitive random
 data: two executions and a fresh plan agree bitwise) and accumulation precision (the error bound of the launch geometry,
 far below the serial chain's), and a final check that every cell of the coverage table was reached.
 """

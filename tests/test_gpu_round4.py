@@ -1,6 +1,6 @@
 """GPU: the kernel-side changes of round 4, each against NumPy (bit-exact where the reference compares with `==`):
   * stepped ranges behind a permutation (an input whose smallest stride is 2..4 elements) take the TILED family with that dim as the
-    input's near-unit axis (csrc/smr_plan.cpp: near_axis) -- /root/reference/test/othertests.jl:130-190 uses exactly such views;
+    input's near-unit axis (csrc/smr_plan_tiled.cpp: near_axis) -- /root/reference/test/othertests.jl:130-190 uses exactly such views;
   * STREAM rows of 129 .. 1024 elements share a workgroup (packed form of csrc/smr_k_stream.hip);
   * split partial reductions with up to 1024 chunks fold inside the launch through two levels of arrival counters
     (csrc/smr_k_reduce.hip: fold_in_launch) -- /root/reference/test/othertests.jl:68-107."""
