@@ -389,7 +389,13 @@ int smr_plan_destroy(smr_plan* plan);
  * runtime-compiled f compiled and loaded, reduction scratch allocated -- without launching.
  * Call it before capturing smr_plan_execute into a hipGraph (uploads are synchronous copies).  */
 int smr_plan_prepare(smr_plan* plan);
-/* Writes a one-line description ("family=tiled tile=32x32 grid=1024 ...") into buf.      */
+/* Writes a one-line description ("family=tiled tile=32x32 grid=1024 ...") into buf.
+ * family=contract (outer-product reductions, the box of the generic mul!: two inputs that vary along different kept
+ * dims) reads "tile=d<i>:<TI>xd<j>:<TJ> k=<TK> grid=<G> lds=<bytes> vec=<V>": input tiles are staged in LDS once per
+ * chunk of TK reduced elements and every lane keeps a block of outputs in registers (tiles of 64, 32 or 16 squared).
+ * Its accumulation order is defined: one lane per output, from the operator's neutral element, over the outer reduced
+ * index and then the inner reduced dim, ascending, the (init-ed) old destination combined last -- for real floats
+ * bit-identical to the sequential loop.                                                                              */
 int smr_plan_describe(const smr_plan* plan, char* buf, size_t buflen);
 /* Algorithmic bytes of one execution: every distinct operand footprint counted once
  * (SURVEY.md section 8d).                                                                 */
@@ -561,6 +567,10 @@ int smr_mapreduce_sharded_ex(const smr_problem* problem, uint32_t local_ops);
  *     "flat2_lead_bytes" (512), "flat2_long" (80: two-sided form for long unit-stride dims whose 32 x 32
  *     tiles would be less full than this per cent; 0 off), "flatb" (1: batched form for small contiguous
  *     blocks).
+ *   CONTRACT: "contract" (1: the LDS- and register-tiled family for reductions of two inputs that vary along
+ *     different kept dims -- the generic mul! box -- when the problem is large enough: op = +, tile extents >= 32, at
+ *     least 256 output tiles, an inner reduced dim of >= 16, and no f that "jit" = 0 would leave to the interpreter;
+ *     0 never; 2 wherever the shape qualifies: tests and experiments).
  *   STREAM: "stream_ua" (1: element-aligned 16-byte vectors + a partial vector per row),
  *     "stream_pack_rows" (1: short rows share a workgroup), "nt_store" (-1: non-temporal stores; 0 never;
  *     1 always; 2 write-through), "nt_stream_min" (0).

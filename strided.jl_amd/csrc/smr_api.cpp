@@ -68,6 +68,7 @@ int launch_reduce_all(const Plan& plan, void* const* bases, hipStream_t s) { SMR
 int launch_reduce_part(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_reduce_part) }
 int launch_orbit_map(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_orbit_map) }
 int launch_flat_map(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_flat_map) }
+int launch_contract(const Plan& plan, void* const* bases, hipStream_t s) { SMR_DISPATCH_CT(launch_contract) }
 
 // ---- overlap windows and library-owned streams --------------------------------------------------------------------------
 // smr_overlap_begin / _end nest per stream.  HIP ignores the any-order dispatch flag on gfx9 (profiles/r04_overlap.txt), so a window
@@ -180,6 +181,7 @@ static int execute_family(const Plan& plan, void* const* bases, hipStream_t s) {
         case FAM_FLAT: return launch_flat_map(plan, bases, s);
         case FAM_REDUCE_ALL: return launch_reduce_all(plan, bases, s);
         case FAM_REDUCE_PART: return launch_reduce_part(plan, bases, s);
+        case FAM_CONTRACT: return launch_contract(plan, bases, s);
     }
     return set_error(SMR_EINVAL, "plan has no kernel family");
 }
@@ -449,6 +451,7 @@ const OptionField OPTION_FIELDS[] = {
     {"flat", &Options::flat},
     {"flat_wide", &Options::flat_wide},
     {"flat2", &Options::flat2},
+    {"contract", &Options::contract},
     {"flat2_pair", &Options::flat2_pair},
     {"flat2_bytes", &Options::flat2_bytes},
     {"flat2_lead_bytes", &Options::flat2_lead_bytes},

@@ -91,8 +91,28 @@ enum Family : int {
     FAM_REDUCE_ALL = 4,
     FAM_REDUCE_PART = 5,
     FAM_ORBIT = 6,    // LDS-staged: every input is a differently permuted view of ONE buffer
-    FAM_FLAT = 7      // unary transposing map whose short leading dims (extents not powers of two) are addressed as one flat run
+    FAM_FLAT = 7,     // unary transposing map whose short leading dims (extents not powers of two) are addressed as one flat run
+    FAM_CONTRACT = 8  // outer-product reduction of two inputs (the generic __mul! box): LDS-staged input tiles, a register block of outputs per lane
 };
+
+// FAM_CONTRACT tile geometry, shared by the planner and the kernel (smr_k_contract.hip).  256 lanes = 16 x 16; a lane owns an
+// RB x RB block of outputs (RB = 4: 64 x 64 tiles, RB = 2: 32 x 32, RB = 1: 16 x 16), the reduced dim is walked in chunks of TK.
+// The two small tiles take four times the chunk of the large one: a launch with one wave per SIMD pays a fixed ~0.5 us per chunk
+// (measured: 256^3 Float32 with 32 x 32 tiles 16.8 -> 10.8 us, 512^3 30.6 -> 19.2 us).
+// Which tile a problem gets is decided by the workgroups it gives (smr_plan_contract.cpp): 64 x 64 from 512 tiles on.  That threshold
+// is NOT measured: no option forces a tile, so the 64 x 64 kernel was timed against REDUCE_PART only (profiles/contract_cases.txt),
+// never against 32 x 32 tiles on the same problem.
+constexpr int CONTRACT_LANES = 16;  // lanes along either tiled dim
+constexpr int contract_tk(int es, int rb) { return rb >= 4 ? (es >= 16 ? 8 : 16) : (es >= 16 ? 16 : (es >= 8 ? 32 : 64)); }
+constexpr int contract_pad(int es) { return es >= 16 ? 1 : 16 / es; }  // LDS rows end in 16 bytes of padding: rows stay 16-byte aligned
+// tiled index of a lane's r-th value, t the lane's position along that dim: pieces of CE elements (a 16-byte LDS read, or RB elements),
+// contiguous over the 16 lanes.  Shared by the kernel (CGeom::idx) and the CPU walk of the decomposition (tools/contract_walk.cpp).
+constexpr int contract_ce(int es, int rb) { return (es >= 16 ? 1 : 16 / es) < rb ? (es >= 16 ? 1 : 16 / es) : rb; }
+constexpr int contract_idx(int es, int rb, int t, int r) {
+    return (r / contract_ce(es, rb)) * (CONTRACT_LANES * contract_ce(es, rb)) + t * contract_ce(es, rb) + (r % contract_ce(es, rb));
+}
+// static LDS of the kernel: two inputs x two buffers x TK rows of (tile + pad) elements
+constexpr size_t contract_lds(int es, int rb) { return (size_t)2 * 2 * contract_tk(es, rb) * (CONTRACT_LANES * rb + contract_pad(es)) * es; }
 
 #ifndef SMR_JIT
 // Does the program hold a math opcode (strided_hip.h: FMA, 96..127, 128..159)?  Those run in runtime-compiled kernels only.
@@ -242,6 +262,23 @@ struct ReducePlan {
     int narrowed = 0;            // COL: the row segment was narrowed to put more workgroups along the kept dims (describe() says so)
 };
 
+// Description for FAM_CONTRACT (smr_k_contract.hip): dest[i, j, rest] = op over (q, k) of f(in1[i, k, ..], in2[j, k, ..]).
+// Accumulation order (defined): every output is accumulated by ONE lane, starting from the neutral element of `op`, over the outer
+// reduced index q ascending (dims NK+1.., dim NK+1 fastest) and inside it over k ascending along dim NK; the (init-ed) old
+// destination is combined last.  No partials, no scratch, one launch.
+struct ContractPlan {
+    int di = -1, dj = -1;  // tiled kept dims: input 1 varies along di only, input 2 along dj only
+    int rb = 4;            // register block edge per lane: 4, 2 or 1 (tile edge = 16 * rb)
+    int ti = 64, tj = 64, tk = 16;
+    i64 nti = 1, ntj = 1, nrest = 1;  // tiles along di, along dj, product of the other kept extents
+    i64 grid = 1;
+    size_t lds_bytes = 0;
+};
+// the vector width (elements per 16-byte global load of whole tiles) one execution uses for the given operand bases (nullptr: the
+// bases the plan was made with): smr_plan_contract.cpp, read by the launcher and by describe()
+struct Plan;
+int contract_vec(const Plan& plan, void* const* bases);
+
 struct Plan {
     Canon c;
     int family = FAM_GENERIC;
@@ -252,6 +289,7 @@ struct Plan {
     Flat2Plan flat2;
     StreamPlan stream;
     ReducePlan red;
+    ContractPlan contract;
     mutable bool eager_seen = false;  // the plan's device tables (uploaded by hipMemcpy on its first execution) have been made visible to the direct queues
     void* scratch = nullptr;  // reductions: partials (owned, ReducePlan::scratch_bytes), followed by RED_COUNTERS arrival counters (zero between launches)
     size_t counter_off = 0;   // byte offset of the counters inside `scratch` (set when it is allocated)
@@ -355,6 +393,8 @@ struct Options {
     i64 nt_stream_min = 0;
     i64 nt_load = -1;        // non-temporal loads in REDUCE_ALL: 0 never, 1 always, -1 = inputs below 2 GiB
     i64 max_lds_bytes = 65536;
+    i64 contract = 1;        // FAM_CONTRACT for outer-product reductions (the generic __mul! shape): 0 never, 1 when the shape qualifies and the problem is
+                             // large enough (smr_plan_contract.cpp: contract_gate), 2 wherever the shape qualifies (tests, experiments)
     i64 tile_lg[MAXN] = {-1, -1, -1, -1, -1, -1, -1, -1};  // per canonical dim log2 tile extent override
 };
 Options& options();
@@ -488,6 +528,7 @@ int launch_reduce_all(const Plan& plan, void* const* bases, hipStream_t s);
 int launch_reduce_part(const Plan& plan, void* const* bases, hipStream_t s);
 int launch_orbit_map(const Plan& plan, void* const* bases, hipStream_t s);
 int launch_flat_map(const Plan& plan, void* const* bases, hipStream_t s);
+int launch_contract(const Plan& plan, void* const* bases, hipStream_t s);
 
 #endif  // !SMR_JIT
 

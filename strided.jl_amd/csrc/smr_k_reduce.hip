@@ -47,31 +47,6 @@ struct RedArgs {
     int32_t single;      // 1: the last workgroup to arrive folds the partials; 0: a second launch does
 };
 
-template <class T>
-SMR_DEV T neutral(int op) {
-    typedef typename tr<T>::real R;
-    switch (op) {
-        case SMR_RED_MUL: return mk<T>(R(1), R(0));
-        case SMR_RED_AND: return mk<T>(R(1), R(0));
-        case SMR_RED_MIN: return mk<T>(rcast<R>(__builtin_huge_val()), R(0));   // integer class: typemax / typemin
-        case SMR_RED_MAX: return mk<T>(rcast<R>(-__builtin_huge_val()), R(0));
-        case SMR_RED_ADD:
-            // the identity of IEEE addition is -0.0: x + (-0.0) == x bit for bit for every x, +0.0 included, while (-0.0) + (+0.0) is
-            // +0.0 -- accumulators and the partials of empty chunks seeded with +0.0 turned a sum of -0.0 into +0.0
-            // The zero is made opaque in a vector register and negated there.  Written as the constant (-0.0, -0.0), the seed of the folds
-            // that take `op` at run time (k_reduce_final, k_reduce_part_final) sits in scalar registers, and for ComplexF64 the compiler's
-            // assembly sets the imaginary part by `s_mov_b64 s[2:3], 0x8000000000000000`.  gfx950 has no 64-bit scalar literal: the
-            // object holds the instruction with the low 32 bits only (disassembled: `s_mov_b64 s[2:3], 0`), +0.0.
-            if constexpr (!is_int_class<T>::value) {
-                R z = R(0);
-                asm volatile("" : "+v"(z));
-                return mk<T>(-z, -z);
-            }
-            break;
-    }
-    return mk<T>(R(0), R(0));
-}
-
 // reduce `v` over the `width` (power of two <= 64) consecutive lanes of a wave
 template <class T>
 SMR_DEV T wave_reduce(T v, int op, int width) {

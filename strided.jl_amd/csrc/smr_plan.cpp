@@ -104,7 +104,7 @@ static void plan_stream(const Canon& c, StreamPlan& sp) {
 
 // ---- family selection -------------------------------------------------------------------------------
 // make_plan only selects: canonicalise, decide the family, call that family's planner (plan_flatb / plan_flat / plan_flat2,
-// plan_tiles, plan_orbit, plan_stream, plan_reduce_all / plan_reduce_part; GENERIC has nothing to plan), describe.
+// plan_tiles, plan_orbit, plan_stream, plan_reduce_all / plan_reduce_part, plan_contract; GENERIC has nothing to plan), describe.
 int make_plan(const smr_problem* p, Plan& plan) {
     int rc = canonicalise(p, plan.c);
     if (rc) return rc;
@@ -161,6 +161,8 @@ int make_plan(const smr_problem* p, Plan& plan) {
         // the ROW form with a single destination element walks it without a per-element index
         // decomposition (measured on a 1000x1000x256 box of a 1024x1024x256 array: 0.59 -> 5 TB/s)
         if (fam == FAM_REDUCE_ALL && c.N > 1 && inputs_run_along(c, 0)) fam = FAM_REDUCE_PART;
+        // two inputs that vary along different kept dims (the generic __mul! box): LDS- and register-tiled (option "contract")
+        if (fam == FAM_REDUCE_PART && o.force_family == 0 && plan_contract(c, plan.contract)) fam = FAM_CONTRACT;
     }
     if (o.force_family == FAM_GENERIC && c.redop == SMR_RED_NONE) fam = FAM_GENERIC;
     if (o.force_family == FAM_TILED && c.redop == SMR_RED_NONE && fam != FAM_TILED && plan_tiles(c, plan.tile)) fam = FAM_TILED;
@@ -187,7 +189,7 @@ static void appendf(std::string& s, const char* fmt, ...) {
 
 void describe(Plan& plan) {
     const Canon& c = plan.c;
-    static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat"};
+    static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     static const char* fk[] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
     static const char* ct[] = {"f32", "f64", "c32", "c64"};
     std::string s;
@@ -234,6 +236,10 @@ void describe(Plan& plan) {
         static const char* kinds[] = {"general", "row", "col"};
         appendf(s, " nout=%lld form=%s lanes_per_out=%d split=%d", (long long)c.nout, kinds[plan.red.kind], plan.red.tr, plan.red.nparts);
         if (plan.red.kind == 2 && plan.red.col_tx) appendf(s, " lanes=%dx%d", plan.red.col_tx, 256 / plan.red.col_tx);
+    }
+    if (plan.family == FAM_CONTRACT) {  // vec: as launched with the bases the plan was made with
+        const ContractPlan& cp = plan.contract;
+        appendf(s, " tile=d%d:%dxd%d:%d k=%d grid=%lld lds=%zu vec=%d", cp.di, cp.ti, cp.dj, cp.tj, cp.tk, (long long)cp.grid, cp.lds_bytes, contract_vec(plan, nullptr));
     }
     if (plan.family == FAM_REDUCE_ALL || plan.family == FAM_REDUCE_PART) {
         // as launched with the bases the plan was made with (the partials buffer is allocated on the first execution)

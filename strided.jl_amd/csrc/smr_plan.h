@@ -20,6 +20,7 @@ bool plan_flatb(const Canon& c, FlatBPlan& f);
 bool plan_flat2(const Canon& c, Flat2Plan& f);
 void plan_reduce_all(const Canon& c, ReducePlan& rp);              // smr_plan_reduce.cpp
 void plan_reduce_part(const Canon& c, ReducePlan& rp);
+bool plan_contract(const Canon& c, ContractPlan& cp);             // smr_plan_contract.cpp (shape rules + the "contract" option's gate)
 // predicates shared by the family planners (smr_plan.cpp)
 int elem_bytes(const Canon& c);                      // bytes per element as the kernels move them
 int ceil_log2(i64 v);                                // 0 for v <= 1

@@ -1,0 +1,115 @@
+// smr_plan_contract.cpp -- planner of FAM_CONTRACT (smr_k_contract.hip): the shape rules, the "contract" option's gate, the tile
+// geometry, and the vector width one execution uses (contract_vec).
+//
+// The shape: a reduction of f(in1, in2) whose two inputs vary along DIFFERENT kept dims -- the box of the reference's generic
+// __mul! (src/linalg.jl:130-162): C2 = (m, n, 1), A2 = (m, 1, k), B2 = (1, n, k).  Every element of in1 is used n times and every
+// element of in2 m times, so REDUCE_PART (one use per load) runs it at a few per cent of the vector ALUs; this family stages a
+// TI x TK tile of in1 and a TJ x TK tile of in2 in LDS once per chunk and keeps an RB x RB block of outputs per lane in registers
+// (RB = 4, 2 or 1: 64 x 64, 32 x 32 or 16 x 16 tiles, by the number of workgroups they give).
+#include "smr_plan.h"
+
+namespace smr {
+
+// The tiled kept dim of input `k` (the other input `o` does not vary along it): the largest extent, unit stride breaking ties.
+static int pick_tile_dim(const Canon& c, int k, int o) {
+    int best = -1;
+    for (int d = 0; d < c.NK; ++d) {
+        if (c.strides[k][d] == 0 || c.strides[o][d] != 0) continue;
+        if (best < 0 || c.dims[d] > c.dims[best] || (c.dims[d] == c.dims[best] && std::llabs(c.strides[k][d]) == 1 && std::llabs(c.strides[k][best]) != 1))
+            best = d;
+    }
+    return best;
+}
+
+// contract = 1: is the problem large enough for the family to win?  Measured with tools/contract_cases.py, CONTRACT against
+// REDUCE_PART (profiles/contract_cases.txt; the thresholds are quoted there).  The family has no split along the reduced range: a
+// launch with fewer workgroups than keep the device busy loses to REDUCE_PART's split forms, so the gate asks for enough output
+// tiles, for tiles that are mostly full, and for a reduced length that amortises staging.
+static bool contract_gate(const Canon& c, const ContractPlan& cp) {
+    // Thresholds (profiles/contract_cases.txt, MI355X, 256 CUs):
+    //   tile extents >= 32 along both tiled dims;
+    //   output tiles >= 256 (of the tile plan_contract chose): a workgroup per CU.  Every measured row with 256 and more wins, from
+    //     1.16x ((1000, 1000, 16) Float32) and 1.4x (256^3) to 3.6 - 5.3x (1024^3); rows with 42 - 144 tiles win 1.01 - 1.4x or tie,
+    //     (64, 64, 4096) with 16 tiles loses 4x: left to REDUCE_PART, whose split forms cut the reduced range;
+    //   extent of the inner reduced dim (the one walked in chunks) >= 16: (1000, 1000, 16) still wins; below, every chunk is a few
+    //     rows between two barriers and staging is not amortised, however long the outer reduced index (not measured: left alone);
+    //   op = +: min-plus (f = a + b, op = min, runtime-compiled) loses at every size measured (256^3 0.56x, 512^3 0.45x, 1024^3
+    //     0.71x): Julia's NaN-aware min is ten instructions per pair and the family's gain is in the loads -- left to REDUCE_PART;
+    //   no interpreted f: with jit = 0 every f but the natively compiled product of same-typed operands runs in the interpreter,
+    //     whose kernels of this family need scratch memory (they leave direct dispatch) and were never timed against REDUCE_PART.
+    //     (A runtime compiler that turns out to be missing at launch is not known here: that launch interprets.)
+    if (c.redop != SMR_RED_ADD) return false;
+    if (!options().jit && (c.mixed || c.fkind != FK_MUL2)) return false;
+    if (c.dims[cp.di] < 32 || c.dims[cp.dj] < 32) return false;
+    if (c.dims[c.NK] < 16) return false;
+    if (cp.grid < 256) return false;
+    return true;
+}
+
+bool plan_contract(const Canon& c, ContractPlan& cp) {
+    const Options& o = options();
+    if (o.contract == 0 || c.redop == SMR_RED_NONE || c.M != 3 || c.bitcopy) return false;
+    if (c.NK < 2 || c.N - c.NK < 1) return false;
+    // no repeated operand: identical inputs were deduplicated (M would be 2); an input that is the destination's own buffer would be
+    // read by one workgroup while another stores into it
+    for (int k = 1; k < 3; ++k)
+        if (c.base[k] == c.base[0]) return false;
+    if (c.strides[1][c.NK] == 0 || c.strides[2][c.NK] == 0) return false;
+    cp.di = pick_tile_dim(c, 1, 2);
+    cp.dj = pick_tile_dim(c, 2, 1);
+    if (cp.di < 0 || cp.dj < 0) return false;
+    const int es = dtype_size(c.ct);
+    // 64 x 64 tiles (4 x 4 outputs per lane) when they fill the device twice over, else 32 x 32 (2 x 2) when those give a workgroup per
+    // CU, else 16 x 16 (one output per lane: no reuse in registers, but 256^3 is 256 workgroups instead of 64 on a quarter of the CUs)
+    // (the 256 is measured, profiles/contract_cases.txt; the 512 is not: the 64 x 64 kernel was timed against REDUCE_PART only, never
+    // against 32 x 32 tiles on the same problem -- two workgroups per CU is where its two waves per SIMD are all resident)
+    i64 rest = 1;
+    for (int d = 0; d < c.NK; ++d)
+        if (d != cp.di && d != cp.dj) rest *= c.dims[d];
+    auto tiles = [&](int rb) {
+        const i64 t = CONTRACT_LANES * rb;
+        return ((c.dims[cp.di] + t - 1) / t) * ((c.dims[cp.dj] + t - 1) / t) * rest;
+    };
+    const int want = tiles(4) >= 512 ? 4 : (tiles(2) >= 256 ? 2 : 1);
+    // the LDS is static: a budget below the tile's takes the next smaller tile that fits, or refuses the family
+    const i64 cap = std::min<i64>(o.max_lds_bytes, 65536);
+    cp.rb = 0;
+    for (int rb = want; rb >= 1 && !cp.rb; rb >>= 1)
+        if ((i64)contract_lds(es, rb) <= cap) cp.rb = rb;
+    if (!cp.rb) return false;
+    cp.ti = cp.tj = CONTRACT_LANES * cp.rb;
+    cp.tk = contract_tk(es, cp.rb);
+    cp.nti = (c.dims[cp.di] + cp.ti - 1) / cp.ti;
+    cp.ntj = (c.dims[cp.dj] + cp.tj - 1) / cp.tj;
+    cp.nrest = rest;
+    cp.grid = tiles(cp.rb);
+    cp.lds_bytes = contract_lds(es, cp.rb);
+    if (cp.grid > 0x7fffffffLL) return false;
+    return o.contract >= 2 || contract_gate(c, cp);
+}
+
+// Whole tiles load 16-byte vectors when BOTH inputs allow it: along its unit-stride axis (the tiled dim or the inner reduced dim NK)
+// every other stride is a multiple of the vector, the base is 16-byte aligned, and -- vectors along NK -- the reduced extent is a
+// whole number of vectors.  Ragged tiles always load element by element (clamped, never guarded).
+int contract_vec(const Plan& plan, void* const* bases) {
+    const Canon& c = plan.c;
+    const ContractPlan& cp = plan.contract;
+    const int es = dtype_size(c.ct);
+    const int v = (c.mixed || es >= 16) ? 1 : 16 / es;
+    if (v == 1) return 1;
+    for (int k = 1; k < 3; ++k) {
+        const int dt = k == 1 ? cp.di : cp.dj;
+        int ax = -1;
+        if (c.strides[k][dt] == 1) ax = dt;
+        else if (c.strides[k][c.NK] == 1) ax = c.NK;
+        if (ax < 0) return 1;
+        if (ax == c.NK && c.dims[c.NK] % v) return 1;
+        const uintptr_t b = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]);
+        if (b % 16) return 1;
+        for (int d = 0; d < c.N; ++d)
+            if (d != ax && c.strides[k][d] % v) return 1;
+    }
+    return v;
+}
+
+}  // namespace smr

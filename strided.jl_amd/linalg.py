@@ -4,7 +4,11 @@ The scalar / BLAS-1 fronts (src/linalg.jl:2-42) are broadcast callers and land o
 compiled functors (scale, axpy, axpby).  Matrix multiplication: the reference routes BLAS
 floats to `gemm!` -- a dense contraction, out of scope for this path -- and
 everything else to the generic `__mul!` (src/linalg.jl:130-162), which is a 3-operand
-map-reduce with `initop`; that form is implemented here for every device element type.
+map-reduce with `initop`; that form is implemented here for every device element type and runs
+as the LDS- and register-tiled CONTRACT kernel family (csrc/smr_k_contract.hip) when the problem is
+large enough -- `S.set_option("contract", 0 | 1 | 2)`: never / by size (default) / wherever the
+shape qualifies.  Each output is accumulated by one lane over k ascending: for real floats the
+result is bit-identical to the sequential loop.
 """
 from __future__ import annotations
 

@@ -70,6 +70,10 @@ static uint64_t digest(const Plan& plan) {
         f.v(r.col_y0); f.v(r.col_y1); f.v(r.xsplit); f.v(r.qsplit); f.v(r.narrowed);
         const RedLaunch l = reduce_launch(plan, nullptr, true);
         f.v(l.vec); f.v(l.fold); f.v(l.nparts); f.v(l.groups); f.v(l.ctx); f.v(l.cty); f.v(l.cy0); f.v(l.cy1);
+    } else if (plan.family == FAM_CONTRACT) {
+        const ContractPlan& k = plan.contract;
+        f.v(k.di); f.v(k.dj); f.v(k.rb); f.v(k.ti); f.v(k.tj); f.v(k.tk); f.v(k.nti); f.v(k.ntj); f.v(k.nrest); f.v(k.grid); f.v(k.lds_bytes);
+        f.v(contract_vec(plan, nullptr));
     }
     return f.h;
 }
@@ -148,7 +152,7 @@ static const OptSet optsets[] = {{"default", nullptr, 0},           {"orbit=0", 
 // how many (problem, option set) lines reached each work-list builder and each input variant, and the least the corpus must give each
 enum { C_PAIR, C_PACKED, C_TILED_ORBIT, C_BLOCK_XCD, C_BLOCK_RR, C_COUNT };
 static const char* cname[] = {"orbit_pair", "orbit_packed", "tiled_orbit_order", "tiled_block_per_xcd", "tiled_block_round_robin"};
-static long counts[C_COUNT], var_lines[6], fam_lines[8], lines;
+static long counts[C_COUNT], var_lines[6], fam_lines[9], lines;
 constexpr long need = 40;
 
 // the TILED work list of the problem when one more option is set (empty: no list, or another family)
@@ -271,9 +275,27 @@ int main() {
                 }
             plan_all(ident(dims, dt, {all[1]}, "one"), problem(dims, dt, {all[1]}, ONE, ~0u, false));
         }
-    static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat"};
+    // reductions of the contraction shape (the generic __mul! box: C (m, n), A (m, k), B (k, n), column-major): the only lines the
+    // CONTRACT family may move
+    for (const auto& mnk : std::vector<std::vector<i64>>{{256, 256, 256}, {512, 512, 512}, {1024, 1024, 1024}, {4096, 64, 64}, {64, 64, 4096}, {100, 90, 80},
+                                                           {1000, 1000, 16}, {2048, 32, 256}, {2048, 2048, 64}, {33, 34, 9}, {1000, 1000, 8}, {512, 512, 15}})
+        for (int dt : dtypes) {
+            smr_problem p = problem(mnk, dt, {rotation(3, 0), rotation(3, 0)}, DISTINCT, 3u, true);
+            const i64 m = mnk[0], n = mnk[1], k = mnk[2];
+            const i64 sa[3] = {1, 0, m}, sb[3] = {0, k, 1};
+            for (int d = 0; d < 3; ++d) {
+                p.ops[1].strides[d] = sa[d];
+                p.ops[2].strides[d] = sb[d];
+            }
+            static const uint8_t mul[] = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0};
+            p.fprog = mul;
+            p.fprog_len = 3;
+            (void)n;
+            plan_all(ident(mnk, dt, {}, "contraction"), p, DISTINCT);
+        }
+    static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     std::fprintf(stderr, "%ld lines:", lines);
-    for (int f = 1; f < 8; ++f) std::fprintf(stderr, " %s=%ld", fam[f], fam_lines[f]);
+    for (int f = 1; f < 9; ++f) std::fprintf(stderr, " %s=%ld", fam[f], fam_lines[f]);
     std::fprintf(stderr, "\n");
     int rc = 0;
     auto report = [&](const char* what, long n) {
