@@ -436,14 +436,15 @@ int64_t smr_plan_flat_side(const smr_plan* plan, int64_t* out, size_t cap);
  *   then N dims, N destination strides, N input strides, P offsets srcoff[r] (input offset inside the block of destination position r) */
 int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
 
-/* ---- grouped launches: many small independent maps as ONE kernel launch --------------------------------
+/* ---- grouped launches: many small independent maps -- or contractions -- as ONE kernel launch -----------
  * A launch cannot finish in under about 2 us on MI355X, so K small maps issued one by one cost K launches however little each
  * moves (the blocks of a block-sparse tensor contraction: permutedims!, axpby!, copy! on dozens to hundreds of sub-views of a few
  * parents).  A GROUP is K maps ("members") that run as one launch of one kernel (csrc/smr_k_group.hip): every workgroup finds its
  * member in a device table and runs it.  No reference counterpart (the reference spawns one task tree per call).
  * smr_group_create accepts the members when all of this holds; anything else that is valid returns SMR_EUNSUPPORTED with a message
  * naming the first offending member, malformed input SMR_EINVAL:
- *   - 1 <= count <= 65535, and every member is a valid map (redop == SMR_RED_NONE);
+ *   - 1 <= count <= 65535, and every member is a valid map (redop == SMR_RED_NONE) -- or every member a contraction: the KIND of
+ *     a group is member 0's, see "contraction groups" below; a map group refuses every reduction, a contraction group every map;
  *   - once canonicalised, all members compute in the same class, agree on whether they are bit copies and whether operand types
  *     are converted, have the same number M of distinct operands, the same dtype and conj flag per operand position and the same
  *     f-program including its constants: the kernel is instantiated once, f is ONE functor for the whole launch.  Members may
@@ -473,7 +474,32 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * smr_group_describe: one line, "family=group members=K grid=G linear=a transposing=b f=<functor> jit=0/1 bytes=...", under
  * SMR_GROUP_MEMBER_SCALARS followed by " scalars=member" (a row of constants per member) or " scalars=shared" (they were equal).
  * smr_group_layout: per member 4 values -- form (0 linear, 1 transposing), first workgroup, workgroups, canonical rank; returns
- * 4 * count and writes min(that, cap) values.  The members' workgroup ranges tile [0, grid) in member order.                     */
+ * 4 * count and writes min(that, cap) values.  The members' workgroup ranges tile [0, grid) in member order.
+ *
+ * CONTRACTION GROUPS.  When member 0 is a reduction the group is K outer-product reductions -- the generic mul! box
+ * dest[i, j, rest] = op(initop(dest), op over k, q of f(in1[i, k, ..], in2[j, k, ..])) -- run as ONE launch of the grouped form of the
+ * CONTRACT kernel (csrc/smr_k_gcontract.hip: LDS- and register-tiled, no partials, no scratch, no second launch).  Every member must
+ * then be a reduction of that shape, whatever option "contract" says and whatever its size: once canonicalised it has exactly two
+ * distinct inputs and no bit copy, at least two kept dims and one reduced dim, both inputs vary along the inner reduced dim, input 1
+ * varies along a kept dim along which input 2 does not and the other way round, and neither input lies on the destination's buffer.
+ * (Size-1 dims are dropped first: a member with m == 1 is not of the shape.)  A member that is not gets SMR_EUNSUPPORTED with
+ * "contraction" in the message.  Every member must agree with member 0 in compute class, in whether operand types are converted,
+ * in dtype and conj flag per operand position, in the f-program including its constants, in redop and in the initop CODE; initarg
+ * (beta) is the member's own, and so are rank, extents, strides, pointers, offsets and batch / outer reduced dims.
+ * SMR_GROUP_MEMBER_SCALARS with a contraction group is SMR_EUNSUPPORTED (per-member constants of f: not supported there).  The
+ * independence check (the destination's range is a write range, which covers the read of the old destination), the footprints, the
+ * 2^31 - 1 workgroup limit and the count limits are those of map groups.
+ * One tile size per group: 32 x 32 outputs per workgroup when the group then still has >= 256 workgroups and those tiles are at
+ * least half full over the group, else 16 x 16; option "group_contract_tile" (16 / 32) forces it.  A tile that does not fit option
+ * "max_lds_bytes" falls back to 16 x 16, and creation returns SMR_EUNSUPPORTED if that does not fit either.  A member's workgroups
+ * are its tiles along the two tiled dims times its other kept extents, exactly what a single call's plan counts for that tile.
+ * Accumulation order is the single call's: one lane per output, from the neutral element, over the outer reduced index ascending
+ * and inside it over k ascending, the init-ed old destination combined last.  Each member's result is bit-identical to
+ * smr_mapreduce on that member alone under option "contract" = 2, whatever tile either side picked.
+ * smr_group_describe reads "family=group kind=contract members=K grid=G tile=<16|32> k=<chunk of the reduced dim> lds=<bytes>
+ * f=<mul2|prog> op=<+|*|min|max|&||> jit=<0|1> bytes=<algorithmic bytes>[ independent=asserted]"; smr_group_layout reports form 2
+ * for every member.  prepare, execute, destroy and smr_seq_add_group work as for map groups (a recorded contraction group is one
+ * packet per replay and can be cut into block ranges).                                                                           */
 typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
 #define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
@@ -589,7 +615,8 @@ int smr_mapreduce_sharded_ex(const smr_problem* problem, uint32_t local_ops);
  *     destinations).
  *   Sharding: "allreduce_f64" (0; 1: Float32 / ComplexF32 sums cross the ranks as Float64).
  *   Groups: "group_max_bytes" (16 MiB: largest member, in algorithmic bytes, that a front end still defers into a group; read by the
- *     front ends only: setting it keeps the plan cache).
+ *     front ends only: setting it keeps the plan cache); "group_contract_tile" (0: the rule; 16 / 32 force the tile of contraction
+ *     groups created afterwards: tests and measurements).
  *   Debug builds with device-side wall-clock stamps (csrc/smr_device.h): "stamp_base" / "stamp_cap" /
  *     "stamp_used"; read-only "stamp_build".
  *   Read-only counters: "launches" (kernel launches the library issued, through HIP or directly),

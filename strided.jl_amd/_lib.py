@@ -473,7 +473,11 @@ class Group:
     (no device).  `independent=True` passes SMR_GROUP_INDEPENDENT: the caller asserts that no member writes an element another
     member reads or writes, and the byte-range check is skipped (interleaved blocks of one parent).  `member_scalars=True` passes
     SMR_GROUP_MEMBER_SCALARS: the values of f's constants may differ from member to member (a coefficient per block); the program,
-    the number of constants and the compute class they lead to must still be those of member 0."""
+    the number of constants and the compute class they lead to must still be those of member 0.
+    A group whose member 0 is a reduction is a CONTRACTION group: every member is an outer-product reduction (the generic mul_
+    box) with the f, op and initop kind of member 0 and a beta of its own; one launch of the grouped CONTRACT kernel, each member
+    bit-identical to the single call under option "contract" = 2.  `member_scalars` is refused for it.  Option
+    "group_contract_tile" (0 = the rule, 16, 32) forces its tile.  See include/strided_hip.h."""
 
     def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False):
         self._lib = load()
@@ -499,7 +503,8 @@ class Group:
         return buf.value.decode()
 
     def layout(self):
-        """Per member (form, first workgroup, workgroups, canonical rank); form 0 = linear, 1 = transposing."""
+        """Per member (form, first workgroup, workgroups, canonical rank); form 0 = linear, 1 = transposing, 2 = a member of a
+        contraction group."""
         n = int(self._lib.smr_group_layout(self._h, None, 0))
         buf = (C.c_int64 * max(1, n))()
         self._lib.smr_group_layout(self._h, buf, n)

@@ -914,6 +914,11 @@ int smr_set_option(const char* name, int64_t value) {
         group_max_bytes() = value;
         return SMR_OK;
     }
+    if (n == "group_contract_tile") {  // read by smr_group_create only: no plan depends on it
+        if (value != 0 && value != 16 && value != 32) return set_error(SMR_EINVAL, "group_contract_tile must be 0 (the rule), 16 or 32");
+        group_contract_tile() = value;
+        return SMR_OK;
+    }
     if (i64 Options::*f = option_field(n)) o.*f = value;
     else if (const int d = tile_lg_dim(n); d >= 0) o.tile_lg[d] = value;
     else return set_error(SMR_EINVAL, "unknown option " + n);
@@ -938,6 +943,7 @@ int64_t smr_get_option(const char* name) {
     if (n == "stamp_used") return o.stamp_used;
     if (n == "stamp_build") return SMR_STAMP;
     if (n == "group_max_bytes") return group_max_bytes();
+    if (n == "group_contract_tile") return group_contract_tile();
     // read-only counters
     if (n == "launches") return g_launches.load();
     if (n == "jit_compiles") return jit_stats().compiles;

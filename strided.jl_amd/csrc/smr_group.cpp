@@ -5,11 +5,14 @@
 // a contiguous range of workgroups.  Under SMR_GROUP_MEMBER_SCALARS the values of f's constants may differ: every member keeps the
 // constants of its own canonicalisation as a row of a third table.  The device tables are uploaded by smr_group_prepare or the first execution.  The planner also
 // keeps the byte ranges one execution reads and writes: the footprint of a group recorded in a sequence (smr_seq_add_group).
+// A group whose member 0 is a reduction is a CONTRACTION group: every member is an outer-product reduction of FAM_CONTRACT's shape
+// (smr_plan_contract.cpp: contract_shape) with one f, one op and one initop code; the launch is the kernel in smr_k_gcontract.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <new>
 
+#include "smr_contract.h"
 #include "smr_direct.h"
 #include "smr_dispatch.h"
 #include "smr_group.h"
@@ -21,6 +24,11 @@ i64& group_max_bytes() {
     // profiles/group_launch.txt: the largest measured member at which one group of 8 beats the 8 single calls it replaces in the
     // front (it beats a recorded sequence only from K = 32 small members on)
     static i64 v = (i64)16 << 20;
+    return v;
+}
+
+i64& group_contract_tile() {
+    static i64 v = 0;
     return v;
 }
 
@@ -169,6 +177,14 @@ Spans merged(Spans rs) {
 }
 
 int launch_group(const GroupPlan& g, hipStream_t s) {
+    if (g.kind == 1) switch (g.c.ct) {
+        case SMR_F32: return launch_group_contract_ct<SMR_F32>(g, s);
+        case SMR_F64: return launch_group_contract_ct<SMR_F64>(g, s);
+        case SMR_C32: return launch_group_contract_ct<SMR_C32>(g, s);
+        case SMR_C64: return launch_group_contract_ct<SMR_C64>(g, s);
+        case SMR_I64: return launch_group_contract_ct<SMR_I64>(g, s);
+        default: return set_error(SMR_EINVAL, "bad compute class");
+    }
     switch (g.c.bitcopy ? SMR_F32 : g.c.ct) {
         case SMR_F32: return launch_group_ct<SMR_F32>(g, s);
         case SMR_F64: return launch_group_ct<SMR_F64>(g, s);
@@ -182,7 +198,9 @@ int launch_group(const GroupPlan& g, hipStream_t s) {
 int ensure_tables(const GroupPlan& g) {
     std::lock_guard<std::mutex> lk(g.build_mu);
     if (!g.d_members) {
-        if (int rc = upload_table(&g.d_members, g.members.data(), g.members.size() * sizeof(GroupMemberD), "group members")) return rc;
+        const void* src = g.kind == 1 ? (const void*)g.cmembers.data() : (const void*)g.members.data();
+        const size_t bytes = g.kind == 1 ? g.cmembers.size() * sizeof(GroupContractMemberD) : g.members.size() * sizeof(GroupMemberD);
+        if (int rc = upload_table(&g.d_members, src, bytes, "group members")) return rc;
     }
     if (!g.d_first) {
         if (int rc = upload_table(&g.d_first, g.first_wg.data(), g.first_wg.size() * sizeof(uint32_t), "group workgroup ranges")) return rc;
@@ -198,6 +216,86 @@ const char* functor_name(const Canon& c) {
     static const char* names[FK_COUNT] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
     const int k = (!c.mixed && (GROUP_FMASK & fbit(c.fkind))) ? c.fkind : FK_PROG;
     return names[k];
+}
+
+// ---- contraction groups ------------------------------------------------------------------------------------------------------
+// does reduction member `c` run the kernel instantiation, f, op and initop code of member 0 (`r`)?  Empty = yes.  beta (initarg)
+// is the member's own.
+std::string contract_mismatch(const Canon& r, const Canon& c) {
+    const std::string why = mismatch(r, c, false);
+    if (!why.empty()) return why;
+    if (c.redop != r.redop) return "reduces with another op than member 0";
+    if (c.initop != r.initop) return "has another kind of initop than member 0 (only its argument, beta, may differ)";
+    return std::string();
+}
+
+const char* redop_name(int op) {
+    static const char* names[] = {"none", "+", "*", "min", "max", "&", "|"};
+    return op >= 0 && op < 7 ? names[op] : "?";
+}
+
+// Plans members[0..count) as one contraction group into `g` (g.c, cmembers, first_wg, rank, rb, algbytes) and collects the operand
+// ranges.  Member 0 is known to be a reduction.
+int plan_contract_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g, std::vector<Range>& ranges, Spans& rd, Spans& wr, i64& grid_out) {
+    g.kind = 1;
+    g.cmembers.resize((size_t)count);
+    i64 wgs32 = 0, outputs = 0;
+    for (int i = 0; i < count; ++i) {
+        const smr_problem& p = members[i];
+        if (p.redop == SMR_RED_NONE) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a map; a contraction group (member 0 is a reduction) holds contractions only");
+        Canon ci;
+        Canon& c = i == 0 ? g.c : ci;
+        if (int rc = canonicalise(&p, c)) return set_error(rc, member_tag(i) + ": " + smr_last_error());
+        int di = -1, dj = -1;
+        if (!contract_shape(c, di, dj))
+            return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction, but not of the contraction shape: two inputs that vary along different kept dims of "
+                                                                "extent > 1 and both along a reduced dim, neither on the destination's buffer; a group holds maps only, or such contractions only");
+        if (i > 0) {
+            const std::string why = contract_mismatch(g.c, c);
+            if (!why.empty()) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
+        }
+        if (c.total > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " has more than 2^31 - 1 box elements");
+        GroupContractMemberD& m = g.cmembers[(size_t)i];
+        std::memset(&m, 0, sizeof m);
+        for (int k = 0; k < 3; ++k) m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+        contract_fill(m, c, di, dj, contract_vec_of(c, di, dj, nullptr), 1);  // (the tile-dependent fields are set again below)
+        i64 rest = 1;
+        for (int n = 0; n < m.nrd; ++n) rest *= m.dims[m.rdim[n]];
+        wgs32 += ((m.dims[di] + 31) / 32) * ((m.dims[dj] + 31) / 32) * rest;
+        outputs += c.nout;
+        g.rank[(size_t)i] = c.N;
+        g.algbytes += c.algbytes;
+        for (int k = 0; k < c.M; ++k) {
+            Range r;
+            operand_span(c, k, c.base[k], r.lo, r.hi);
+            r.member = i;
+            r.write = k == 0;
+            (r.write ? wr : rd).emplace_back(r.lo, r.hi);
+            if (!(flags & SMR_GROUP_INDEPENDENT)) ranges.push_back(r);
+        }
+    }
+    // One tile size per group.  The single call's rule, read over the whole group: 32 x 32 (2 x 2 outputs per lane) when the group
+    // then still has a workgroup per CU -- 256, the threshold measured for single calls (smr_plan_contract.cpp) -- AND those tiles are
+    // at least half full over the group (outputs >= 1/2 * 1024 * tiles): members of 16 or 24 along a dim would otherwise stage and
+    // compute mostly padding.  Measured (tools/group_contract_vs_single.py, profiles/group_contract.txt): 64 blocks of 64^3 Float64,
+    // every tile of either size full, 32 x 32 7.82 us against 16 x 16 8.15 us -- what this rule picks there.  The half-full condition
+    // is NOT measured: that is the only row timed under both tiles, and none has partly filled 32 x 32 tiles.
+    const int es = dtype_size(g.c.ct);
+    const i64 force = group_contract_tile();
+    int rb = force == 32 ? 2 : (force == 16 ? 1 : ((wgs32 >= 256 && 2 * outputs >= 1024 * wgs32) ? 2 : 1));
+    // the LDS is static: a budget below the tile's takes 16 x 16, or refuses
+    const i64 cap = std::min<i64>(options().max_lds_bytes, 65536);
+    while (rb >= 1 && (i64)contract_lds(es, rb) > cap) rb >>= 1;
+    if (rb < 1) return set_error(SMR_EUNSUPPORTED, "smr_group_create: the 16 x 16 tile of a contraction group does not fit max_lds_bytes");
+    g.rb = rb;
+    i64 grid = 0;
+    for (int i = 0; i < count; ++i) {
+        grid += contract_set_tile(g.cmembers[(size_t)i], es, rb);
+        if (grid > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, member_tag(i) + ": the group needs more than 2^31 - 1 workgroups");
+        g.first_wg[(size_t)i + 1] = (uint32_t)grid;
+    }
+    grid_out = grid;
+    return SMR_OK;
 }
 
 }  // namespace
@@ -231,7 +329,6 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
     smr_group* h = new (std::nothrow) smr_group();
     if (!h) return set_error(SMR_ENOMEM, "out of host memory");
     GroupPlan& g = h->plan;
-    g.members.resize((size_t)count);
     g.first_wg.assign((size_t)count + 1, 0);
     g.rank.resize((size_t)count);
     std::vector<Range> ranges;
@@ -240,7 +337,15 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
     int rc = SMR_OK;
     const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0;
     bool native_row = false;
-    for (int i = 0; i < count && rc == SMR_OK; ++i) {
+    // the kind is member 0's: a reduction opens a contraction group, a map a map group (which refuses every reduction below)
+    const bool contraction = members[0].redop != SMR_RED_NONE;
+    if (contraction) {
+        if (own_scalars) rc = set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a contraction group (member 0 is a reduction): per-member constants of f are not supported there");
+        else rc = plan_contract_group(members, count, flags, g, ranges, rd, wr, grid);
+    } else {
+        g.members.resize((size_t)count);
+    }
+    for (int i = 0; i < count && rc == SMR_OK && !contraction; ++i) {
         const smr_problem& p = members[i];
         if (p.redop != SMR_RED_NONE) {
             rc = set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction; a group holds maps only");
@@ -314,9 +419,17 @@ int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_
     // FK_PROG has a bit in GROUP_FMASK like every kind, so the mask alone does not tell
     g.jit = options().jit && !g.c.bitcopy && (g.c.mixed || g.c.fkind == FK_PROG || !(GROUP_FMASK & fbit(g.c.fkind)));
     char buf[256];
-    std::snprintf(buf, sizeof buf, "family=group members=%d grid=%lld linear=%d transposing=%d f=%s jit=%d bytes=%lld%s%s", count, (long long)grid,
-                  g.nlinear, g.ntrans, functor_name(g.c), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "",
-                  own_scalars ? (g.varc ? " scalars=member" : " scalars=shared") : "");
+    if (contraction) {  // launch_group_contract_ct(): the product of same-typed operands is native, every other f a program
+        const bool native = !g.c.mixed && g.c.fkind == FK_MUL2;
+        g.jit = options().jit && !native;
+        std::snprintf(buf, sizeof buf, "family=group kind=contract members=%d grid=%lld tile=%d k=%d lds=%zu f=%s op=%s jit=%d bytes=%lld%s", count, (long long)grid,
+                      CONTRACT_LANES * g.rb, contract_tk(dtype_size(g.c.ct), g.rb), contract_lds(dtype_size(g.c.ct), g.rb), native ? "mul2" : "prog",
+                      redop_name(g.c.redop), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "");
+    } else {
+        std::snprintf(buf, sizeof buf, "family=group members=%d grid=%lld linear=%d transposing=%d f=%s jit=%d bytes=%lld%s%s", count, (long long)grid,
+                      g.nlinear, g.ntrans, functor_name(g.c), g.jit ? 1 : 0, (long long)g.algbytes, (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : "",
+                      own_scalars ? (g.varc ? " scalars=member" : " scalars=shared") : "");
+    }
     g.desc = buf;
     *out = h;
     return SMR_OK;
@@ -359,10 +472,10 @@ int64_t smr_group_algorithmic_bytes(const smr_group* g) { return g ? g->plan.alg
 int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap) {
     if (!g) return 0;
     const GroupPlan& p = g->plan;
-    const size_t n = p.members.size();
+    const size_t n = p.rank.size();
     if (out)
         for (size_t i = 0; i < n; ++i) {
-            const int64_t v[4] = {p.members[i].form, p.first_wg[i], (int64_t)p.first_wg[i + 1] - (int64_t)p.first_wg[i], p.rank[i]};
+            const int64_t v[4] = {p.kind == 1 ? 2 : p.members[i].form, p.first_wg[i], (int64_t)p.first_wg[i + 1] - (int64_t)p.first_wg[i], p.rank[i]};
             for (size_t j = 0; j < 4; ++j)
                 if (4 * i + j < cap) out[4 * i + j] = v[j];
         }

@@ -1,6 +1,6 @@
 // smr_group.h -- grouped launches (smr_group_*): K independent small maps, each with its own rank, dims, strides, pointers and
-// offsets, run as ONE kernel launch (smr_k_group.hip).  Shared by the group planner / C ABI (smr_group.cpp) and the kernel's
-// translation units; the top part is also compiled by hiprtc (SMR_JIT).
+// offsets, run as ONE kernel launch (smr_k_group.hip) -- or K independent small contractions (smr_k_gcontract.hip).  Shared by the
+// group planner / C ABI (smr_group.cpp) and the kernels' translation units; the top part is also compiled by hiprtc (SMR_JIT).
 #pragma once
 
 #include "smr_internal.h"
@@ -29,6 +29,20 @@ struct GroupMemberD {
     uint32_t ntp, ntq;           // ... tiles along dim 0 and along dim q
 };
 
+// One member of a CONTRACTION group (smr_k_gcontract.hip): the geometry a single call of FAM_CONTRACT carries in ContractArgs
+// (smr_contract.h: the field names are those the shared tile body reads), and the member's operand addresses.  Everything in it
+// is wave-uniform.  beta (the initop's argument) is the member's own; redop and the initop code are those of member 0.
+struct GroupContractMemberD {
+    void* base[3];               // destination, input 1, input 2: element offsets folded in
+    int32_t N, NK, redop, initop, di, dj, vec, nrd;
+    int32_t rdim[MAXN];
+    int32_t mode[3];
+    i64 dims[MAXN];
+    i64 strides[3][MAXN];
+    double beta[2];
+    i64 nti, ntj, K, Q, nkc;
+};
+
 #ifndef SMR_JIT
 // every recognised functor of f has a natively compiled group kernel (the same functor code a single call runs); any other f is
 // runtime-compiled, or interpreted, as in GENERIC
@@ -39,6 +53,11 @@ constexpr unsigned GROUP_FMASK = 0xffffffffu;
 struct GroupPlan {
     Canon c;
     std::vector<GroupMemberD> members;
+    // kind 1, a contraction group: every member is an outer-product reduction (contract_shape) and runs FAM_CONTRACT's tile body;
+    // `cmembers` replaces `members`, one tile size (16 * rb) for the whole launch
+    int kind = 0;
+    int rb = 1;
+    std::vector<GroupContractMemberD> cmembers;
     std::vector<uint32_t> first_wg;   // count + 1 prefix sums of the members' workgroups
     std::vector<int> rank;            // canonical rank per member (smr_group_layout)
     int nlinear = 0, ntrans = 0;
@@ -61,9 +80,11 @@ struct GroupPlan {
 };
 
 template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);
+template <int CT> int launch_group_contract_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip
 
 int ensure_device();     // smr_api.cpp
 i64& group_max_bytes();  // option "group_max_bytes" (smr_group.cpp)
+i64& group_contract_tile();  // option "group_contract_tile": 0 = the planner's rule, 16 / 32 force the tile of contraction groups
 
 // Bounding byte range [lo, hi) of operand k of a canonical problem: what footprint() (smr_api.cpp) and the group planner compare.
 inline void operand_span(const Canon& c, int k, const void* base, uintptr_t& lo_out, uintptr_t& hi_out) {

@@ -278,6 +278,10 @@ struct ContractPlan {
 // bases the plan was made with): smr_plan_contract.cpp, read by the launcher and by describe()
 struct Plan;
 int contract_vec(const Plan& plan, void* const* bases);
+// the same for a canonical problem tiled along di / dj, and the family's shape rules without the "contract" option and its gate
+// (true: di / dj are the tiled kept dims): what the group planner asks of every member of a contraction group (smr_group.cpp)
+int contract_vec_of(const Canon& c, int di, int dj, void* const* bases);
+bool contract_shape(const Canon& c, int& di, int& dj);
 
 struct Plan {
     Canon c;

@@ -46,18 +46,25 @@ static bool contract_gate(const Canon& c, const ContractPlan& cp) {
     return true;
 }
 
-bool plan_contract(const Canon& c, ContractPlan& cp) {
-    const Options& o = options();
-    if (o.contract == 0 || c.redop == SMR_RED_NONE || c.M != 3 || c.bitcopy) return false;
+// The shape rules alone, without the "contract" option and its gate: is `c` an outer-product reduction this family's tile body can
+// run, and along which kept dims is it tiled?  plan_contract asks it for a single call, the group planner (smr_group.cpp) for every
+// member of a contraction group.
+bool contract_shape(const Canon& c, int& di, int& dj) {
+    if (c.redop == SMR_RED_NONE || c.M != 3 || c.bitcopy) return false;
     if (c.NK < 2 || c.N - c.NK < 1) return false;
     // no repeated operand: identical inputs were deduplicated (M would be 2); an input that is the destination's own buffer would be
     // read by one workgroup while another stores into it
     for (int k = 1; k < 3; ++k)
         if (c.base[k] == c.base[0]) return false;
     if (c.strides[1][c.NK] == 0 || c.strides[2][c.NK] == 0) return false;
-    cp.di = pick_tile_dim(c, 1, 2);
-    cp.dj = pick_tile_dim(c, 2, 1);
-    if (cp.di < 0 || cp.dj < 0) return false;
+    di = pick_tile_dim(c, 1, 2);
+    dj = pick_tile_dim(c, 2, 1);
+    return di >= 0 && dj >= 0;
+}
+
+bool plan_contract(const Canon& c, ContractPlan& cp) {
+    const Options& o = options();
+    if (o.contract == 0 || !contract_shape(c, cp.di, cp.dj)) return false;
     const int es = dtype_size(c.ct);
     // 64 x 64 tiles (4 x 4 outputs per lane) when they fill the device twice over, else 32 x 32 (2 x 2) when those give a workgroup per
     // CU, else 16 x 16 (one output per lane: no reuse in registers, but 256^3 is 256 workgroups instead of 64 on a quarter of the CUs)
@@ -91,14 +98,14 @@ bool plan_contract(const Canon& c, ContractPlan& cp) {
 // Whole tiles load 16-byte vectors when BOTH inputs allow it: along its unit-stride axis (the tiled dim or the inner reduced dim NK)
 // every other stride is a multiple of the vector, the base is 16-byte aligned, and -- vectors along NK -- the reduced extent is a
 // whole number of vectors.  Ragged tiles always load element by element (clamped, never guarded).
-int contract_vec(const Plan& plan, void* const* bases) {
-    const Canon& c = plan.c;
-    const ContractPlan& cp = plan.contract;
+int contract_vec(const Plan& plan, void* const* bases) { return contract_vec_of(plan.c, plan.contract.di, plan.contract.dj, bases); }
+
+int contract_vec_of(const Canon& c, int di, int dj, void* const* bases) {
     const int es = dtype_size(c.ct);
     const int v = (c.mixed || es >= 16) ? 1 : 16 / es;
     if (v == 1) return 1;
     for (int k = 1; k < 3; ++k) {
-        const int dt = k == 1 ? cp.di : cp.dj;
+        const int dt = k == 1 ? di : dj;
         int ax = -1;
         if (c.strides[k][dt] == 1) ax = dt;
         else if (c.strides[k][c.NK] == 1) ax = c.NK;

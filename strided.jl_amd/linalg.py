@@ -9,6 +9,10 @@ as the LDS- and register-tiled CONTRACT kernel family (csrc/smr_k_contract.hip) 
 large enough -- `S.set_option("contract", 0 | 1 | 2)`: never / by size (default) / wherever the
 shape qualifies.  Each output is accumulated by one lane over k ascending: for real floats the
 result is bit-identical to the sequential loop.
+Many small products (the blocks of a block-sparse contraction) share ONE launch inside
+`with S.group(contract=True):` -- calls of `mul_` on matrices with the same alpha and the same kind of
+beta (0, 1, or anything else; the value is per call) are deferred and run as a contraction group
+(csrc/smr_k_gcontract.hip), each result bit-identical to the single call under "contract" = 2.
 """
 from __future__ import annotations
 

@@ -276,6 +276,8 @@ def _mapreduce_fuse_(f, op, initop, dims, arrays):
     if g is not None:  # inside `with S.group():` -- maps are deferred, anything else runs after what is pending
         if op is None and g.defer(f, dims, arrays):
             return arrays[0]
+        if op is not None and g.contract and g.defer(f, dims, arrays, op, initop):  # a contraction: S.group(contract=True)
+            return arrays[0]
         g.flush()
     if _SMR_MAPREDUCE is None:
         _SMR_MAPREDUCE = L.load().smr_mapreduce
@@ -321,7 +323,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, forced contraction tile); least recently used first
 
 
 def _byte_range(a):
@@ -362,19 +364,51 @@ def _integer_valued(v) -> bool:
     return math.isinf(r) or (r == math.floor(r) and abs(r) <= 9223372036854775808.0) if not math.isnan(r) else False
 
 
+def _contract_shaped(dims, arrays) -> bool:
+    """Host-side mirror of the library's shape rule for a member of a contraction group (csrc/smr_plan_contract.cpp:
+    contract_shape, on the canonical problem): exactly three arrays (destination, input 1, input 2); a kept dim (the destination
+    varies along it) of extent > 1 along which only input 1 varies and another along which only input 2 varies; both inputs vary
+    along the inner reduced dim -- of the dims of extent > 1 the destination does not vary along, the one with the smallest input
+    stride, which is the one the kernel walks in chunks; no input on the destination's base; and algorithmic bytes within option
+    "group_max_bytes"."""
+    if len(arrays) != 3 or len(dims) > L.SMR_MAXN:
+        return False
+    c, a, b = arrays
+    if a._base == c._base or b._base == c._base:
+        return False
+    only_a = only_b = False
+    inner, inner_key = None, None
+    for d, n in enumerate(dims):
+        if n <= 1:
+            continue
+        sc, sa, sb = c.strides[d], a.strides[d], b.strides[d]
+        if sc != 0:
+            only_a = only_a or (sa != 0 and sb == 0)
+            only_b = only_b or (sb != 0 and sa == 0)
+        else:
+            key = min([abs(x) for x in (sa, sb) if x != 0] or [1 << 63])
+            if inner is None or key < inner_key:  # (a stable sort: the first of equal strides)
+                inner, inner_key = d, key
+    if not (only_a and only_b) or inner is None:
+        return False
+    if a.strides[inner] == 0 or b.strides[inner] == 0:
+        return False
+    return _member_bytes(arrays) <= L.get_option("group_max_bytes")
+
+
 class _Deferred:
-    __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key")
+    __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key", "op", "initop")
 
 
 class group:
-    """`with S.group(independent=False, member_scalars=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    """`with S.group(independent=False, member_scalars=False, contract=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
     `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
       * a call whose byte ranges conflict with a pending call (it writes what one reads or writes, or reads what one writes) first
         flushes everything pending.  With `independent=True` only exact same-view conflicts count -- the caller asserts that
         different views share no element, which is what lets interleaved blocks of one parent array share a launch;
-      * reductions, members above option "group_max_bytes" and host reads (`toarray`, `item`, `Array`) flush what is pending and
+      * reductions (but see `contract`), members above option "group_max_bytes" and host reads (`toarray`, `item`, `Array`) flush what is pending and
         then run as usual;
       * a bucket the library refuses as a group (smr_group_create: SMR_EUNSUPPORTED) runs call by call through the normal path;
         an error a single call would have raised at once is raised at the flush instead.
@@ -384,13 +418,20 @@ class group:
     whether all are integer-valued (the compute class).  Equal captured values are ONE constant of the f-program (expr.py merges
     them): `a*X + a*Y` is another program than `a*X + b*Y`, and the `linalg` fronts choose another f for alpha = 1 and for
     beta = 0 or 1 -- such calls land in buckets of their own, correctly.
+    `contract=True` (contraction groups): reductions of the outer-product shape -- `mul_(C, A, B, alpha, beta)` on matrices, and
+    every `_mapreducedim_` shaped like it (`_contract_shaped`) -- are deferred as well and every bucket of them becomes ONE launch
+    of the grouped CONTRACT kernel (csrc/smr_k_gcontract.hip).  Their bucket key also holds the reduction's op, the kind of initop
+    (zero / none / scale / const / ...: beta = 0, 1 and any other beta are three kinds) and the values of f's captured scalars (alpha)
+    -- those always, whatever `member_scalars` says: a contraction group has one f.  beta itself is per member.  Each result is
+    bit-identical to the single call's under option "contract" = 2.  Without `contract=True` a reduction flushes and runs as usual.
     `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
 
     MAX_PENDING = 4096
 
-    def __init__(self, independent: bool = False, member_scalars: bool = False):
+    def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False):
         self.independent = bool(independent)
         self.member_scalars = bool(member_scalars)
+        self.contract = bool(contract)
         self.pending = []
         self.groups = []
         self.singles = 0
@@ -428,16 +469,21 @@ class group:
                     return True
         return False
 
-    def defer(self, f, dims, arrays) -> bool:
-        """Takes one map call (destination first).  False: the call is not eligible (too large, too many operands) -- the caller
-        flushes and runs it through the normal path."""
+    def defer(self, f, dims, arrays, op=None, initop=None) -> bool:
+        """Takes one map call (destination first), or with `op` one reduction of the contraction shape.  False: the call is not
+        eligible (too large, too many operands, a reduction of another shape) -- the caller flushes and runs it through the normal
+        path."""
         arrays = tuple(arrays)
         if len(arrays) < 2 or len(arrays) > L.SMR_MAXM or len(dims) > L.SMR_MAXN:
             return False
-        if _member_bytes(arrays) > L.get_option("group_max_bytes"):
+        if op is not None:
+            if not _contract_shaped(dims, arrays):
+                return False
+        elif _member_bytes(arrays) > L.get_option("group_max_bytes"):
             return False
         c = _Deferred()
         c.f, c.dims, c.arrays = f, tuple(int(d) for d in dims), arrays
+        c.op, c.initop = op, initop
         c.stream = _current_stream()
         dts = tuple(np.dtype(a.dtype) for a in arrays)
         code, consts = _serialized(f, len(arrays), dts)
@@ -450,9 +496,11 @@ class group:
         else:
             ck = tuple(consts)
         c.bucket = (bytes(code), ck, tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream)
-        c.wr = _byte_range(arrays[0])
+        if op is not None:  # one f (the constants' values whatever member_scalars says), one op, one kind of initop; beta is the member's
+            c.bucket = c.bucket[:1] + (tuple(consts),) + c.bucket[2:] + ("contract", _redop_code(op), _initop_code(initop)[0])
+        c.wr = _byte_range(arrays[0])  # (a reduction also reads its destination: a write range conflicts with everything a read does)
         c.rd = [_byte_range(a) for a in arrays[1:]]
-        c.key = _problem_key(f, None, None, c.dims, arrays)
+        c.key = _problem_key(f, op, initop, c.dims, arrays)
         if self.pending and (len(self.pending) >= self.MAX_PENDING or self._conflicts(c)):
             self.flush()
         self.pending.append(c)
@@ -470,8 +518,10 @@ class group:
 
     def _launch(self, calls, stream):
         key = None
+        reducing = calls[0].op is not None  # a bucket of contractions: the library is not passed member_scalars
+        scalars = self.member_scalars and not reducing
         if all(c.key is not None for c in calls):
-            key = (tuple(c.key for c in calls), self.independent, self.member_scalars, stream)
+            key = (tuple(c.key for c in calls), self.independent, scalars, stream, L.get_option("group_contract_tile") if reducing else 0)
         grp = None
         if key is not None:
             try:
@@ -479,10 +529,10 @@ class group:
             except TypeError:
                 key = None
         if grp is None:
-            built = [build_problem(c.f, None, None, c.dims, c.arrays, stream=stream) for c in calls]
+            built = [build_problem(c.f, c.op, c.initop, c.dims, c.arrays, stream=stream) for c in calls]
             try:
                 # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
-                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=self.member_scalars)
+                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=scalars)
             except L.UnsupportedOnDevice:
                 for c in calls:
                     self._single(c)
@@ -507,10 +557,10 @@ class group:
         try:
             self.singles += 1
             if c.stream != _current_stream():
-                p, keep = build_problem(c.f, None, None, c.dims, c.arrays, stream=c.stream)
+                p, keep = build_problem(c.f, c.op, c.initop, c.dims, c.arrays, stream=c.stream)
                 L.check(L.load().smr_mapreduce(C.byref(p)))
             else:
-                _mapreduce_fuse_(c.f, None, None, c.dims, c.arrays)
+                _mapreduce_fuse_(c.f, c.op, c.initop, c.dims, c.arrays)
         finally:
             _GROUP.cur = cur
 
