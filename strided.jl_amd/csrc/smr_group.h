@@ -1,9 +1,10 @@
 // smr_group.h -- grouped launches (smr_group_*): K independent small maps, each with its own rank, dims, strides, pointers and
 // offsets, run as ONE kernel launch (smr_k_group.hip) -- or K independent small contractions (smr_k_gcontract.hip).  Shared by the
-// group planner / C ABI (smr_group.cpp) and the kernels' translation units; the top part is also compiled by hiprtc (SMR_JIT).
+// group planner (smr_plan_group.cpp), the C ABI and launch path (smr_group.cpp) and the kernels' translation units.  The top part
+// -- the device tables and the member search both kernels run -- is also compiled by hiprtc (SMR_JIT).
 #pragma once
 
-#include "smr_internal.h"
+#include "smr_device.h"
 
 namespace smr {
 
@@ -43,47 +44,83 @@ struct GroupContractMemberD {
     i64 nti, ntj, K, Q, nkc;
 };
 
+// The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
+// space they are fetched by scalar loads into scalar registers, not once per lane.
+typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
+typedef const GroupContractMemberD __attribute__((address_space(4))) GroupContractMemberC;
+typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
+typedef const double __attribute__((address_space(4))) GroupConstC;
+
+// The member of workgroup `b` of the group: the last one whose first workgroup is <= b (first_wg[]: count + 1 prefix sums of the
+// members' workgroups; every member has at least one).
+SMR_DEV int group_member_of(GroupWordC* first_wg, int count, uint32_t b) {
+    int lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first_wg[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 #ifndef SMR_JIT
-// every recognised functor of f has a natively compiled group kernel (the same functor code a single call runs); any other f is
-// runtime-compiled, or interpreted, as in GENERIC
+// every recognised functor has a natively compiled group kernel (a single call's functor code); any other f is a program, as in GENERIC
 constexpr unsigned GROUP_FMASK = 0xffffffffu;
 
+// the kind is member 0's: a reduction opens a contraction group (every member an outer-product reduction on FAM_CONTRACT's tile body)
+enum GroupKind { GROUP_MAP, GROUP_CONTRACT };
+// what smr_group_layout reports per member: the body a map member runs (GroupMemberD::form), or that it is a contraction
+enum GroupForm { GROUP_FORM_LINEAR = 0, GROUP_FORM_TRANSPOSING = 1, GROUP_FORM_CONTRACT = 2 };
+
+struct GroupMapPlan {  // GROUP_MAP only
+    std::vector<GroupMemberD> members;
+    int nlinear = 0, ntrans = 0;
+    // per-member scalars (SMR_GROUP_MEMBER_SCALARS and constants that do differ): row i holds member i's W doubles, Canon::fc
+    // (W = 4) for a recognised functor, ProgD::consts (W = 2 * nconst) for a program
+    bool varc = false;
+    int W = 0;
+    std::vector<double> consts;
+    mutable void* d_consts = nullptr;  // device copy of `consts`
+};
+struct GroupContractPlan {  // GROUP_CONTRACT only
+    std::vector<GroupContractMemberD> members;
+    int rb = 1;  // one tile size (16 * rb) for the whole launch
+};
+
 // A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
-// (the values of the program's constants too, unless `varc`).
+// (the values of the program's constants too, unless `map.varc`).
 struct GroupPlan {
     Canon c;
-    std::vector<GroupMemberD> members;
-    // kind 1, a contraction group: every member is an outer-product reduction (contract_shape) and runs FAM_CONTRACT's tile body;
-    // `cmembers` replaces `members`, one tile size (16 * rb) for the whole launch
-    int kind = 0;
-    int rb = 1;
-    std::vector<GroupContractMemberD> cmembers;
+    GroupKind kind = GROUP_MAP;
+    GroupMapPlan map;
+    GroupContractPlan contract;
     std::vector<uint32_t> first_wg;   // count + 1 prefix sums of the members' workgroups
     std::vector<int> rank;            // canonical rank per member (smr_group_layout)
-    int nlinear = 0, ntrans = 0;
     bool jit = false;                 // f runs as a runtime-compiled functor
     i64 algbytes = 0;
     std::string desc;
     // what one execution reads (every input of every member) and writes (every destination): operand_span() ranges, sorted, with
     // overlapping and adjacent ones merged -- the footprint of a group recorded in a sequence (smr_seq_add_group)
     std::vector<std::pair<uintptr_t, uintptr_t>> rd, wr;
-    // per-member scalars (SMR_GROUP_MEMBER_SCALARS and constants that do differ): row i holds member i's W doubles, Canon::fc
-    // (W = 4) for a recognised functor, ProgD::consts (W = 2 * nconst) for a program
-    bool varc = false;
-    int W = 0;
-    std::vector<double> consts;
-    // device copies of `members`, `first_wg` and `consts`, uploaded by prepare / the first execution
+    // device copies of the member table and `first_wg` (and map.d_consts), uploaded by prepare / the first execution
     mutable std::mutex build_mu;
     mutable void* d_members = nullptr;
     mutable void* d_first = nullptr;
-    mutable void* d_consts = nullptr;
+
+    // a host table as bytes; the member table of the group's kind
+    template <class E> static std::pair<const void*, size_t> bytes_of(const std::vector<E>& v) { return {v.data(), v.size() * sizeof(E)}; }
+    std::pair<const void*, size_t> member_table() const { return kind == GROUP_CONTRACT ? bytes_of(contract.members) : bytes_of(map.members); }
+    int form(size_t i) const { return kind == GROUP_CONTRACT ? GROUP_FORM_CONTRACT : map.members[i].form; }
 };
 
-template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);
+// smr_plan_group.cpp: plans members[0..count) (count >= 1, known flags) into a fresh `g`.  Host arithmetic only, no HIP runtime call
+int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g);
+
+template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);           // smr_k_group.hip
 template <int CT> int launch_group_contract_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip
 
-int ensure_device();     // smr_api.cpp
-i64& group_max_bytes();  // option "group_max_bytes" (smr_group.cpp)
+int ensure_device();         // smr_api.cpp
+i64& group_max_bytes();      // option "group_max_bytes" (smr_group.cpp)
 i64& group_contract_tile();  // option "group_contract_tile": 0 = the planner's rule, 16 / 32 force the tile of contraction groups
 
 // Bounding byte range [lo, hi) of operand k of a canonical problem: what footprint() (smr_api.cpp) and the group planner compare.

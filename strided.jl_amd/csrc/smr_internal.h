@@ -279,7 +279,7 @@ struct ContractPlan {
 struct Plan;
 int contract_vec(const Plan& plan, void* const* bases);
 // the same for a canonical problem tiled along di / dj, and the family's shape rules without the "contract" option and its gate
-// (true: di / dj are the tiled kept dims): what the group planner asks of every member of a contraction group (smr_group.cpp)
+// (true: di / dj are the tiled kept dims): what the group planner asks of every member of a contraction group (smr_plan_group.cpp)
 int contract_vec_of(const Canon& c, int di, int dj, void* const* bases);
 bool contract_shape(const Canon& c, int& di, int& dj);
 

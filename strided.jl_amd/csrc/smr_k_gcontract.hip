@@ -2,9 +2,9 @@
 // the same operand types; rank, extents, strides, pointers and beta of their own) in ONE launch of 256-lane workgroups.
 //
 // Every member is tiled like a single call of FAM_CONTRACT (smr_k_contract.hip) with ONE tile size for the whole launch, 16 x 16
-// or 32 x 32 (RB = 1 or 2; the group planner, smr_group.cpp, picks it); a member's workgroups are its nti * ntj * rest tiles and the
-// grid is their sum.  A workgroup finds its member by the binary search of the map groups (smr_k_group.hip) over the prefix sums
-// first_wg[] with its index in the group, blockIdx.x + wg0 -- a launch may be one contiguous block range of the group, which is
+// or 32 x 32 (RB = 1 or 2; the group planner, smr_plan_group.cpp, picks it); a member's workgroups are its nti * ntj * rest tiles and
+// the grid is their sum.  A workgroup finds its member by the binary search it shares with the map groups (smr_group.h:
+// group_member_of) over the prefix sums first_wg[] with its index in the group, blockIdx.x + wg0 -- a launch may be one contiguous block range of the group, which is
 // how a recorded sequence cuts it -- decodes its index inside the member into (tile along di, tile along dj, rest) and runs the
 // family's tile body (smr_contract.h: contract_impl) in one of its three copies: bounds-free for whole tiles, with 16-byte global
 // loads where the member's own `vec` allows, clamped for ragged tiles.  The sum has the copy with the operator fixed.
@@ -26,9 +26,6 @@
 
 namespace smr {
 
-typedef const GroupContractMemberD __attribute__((address_space(4))) GroupContractMemberC;
-typedef const uint32_t __attribute__((address_space(4))) GroupContractWordC;
-
 struct GroupContractArgs {
     const GroupContractMemberD* members;
     const uint32_t* first_wg;  // count + 1 prefix sums
@@ -44,15 +41,10 @@ SMR_DEV void group_contract_body(const GroupContractArgs a, F f) {
     typedef CGeom<T, RB> G;
     __shared__ __attribute__((aligned(16))) T lds[2 * 2 * G::TK * G::LD];
     static_assert(sizeof(T) * 2 * 2 * G::TK * G::LD == contract_lds(G::ES, RB), "the planner's LDS figure is the kernel's");
-    // the member of this workgroup: the last one whose first workgroup is <= its index in the group (every member has at least one)
+    // the member of this workgroup, by its index in the group (smr_group.h: group_member_of)
     const uint32_t b = blockIdx.x + a.wg0;
-    GroupContractWordC* const first_wg = (GroupContractWordC*)a.first_wg;
-    int lo = 0, hi = a.count;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first_wg[mid] <= b) lo = mid;
-        else hi = mid;
-    }
+    GroupWordC* const first_wg = (GroupWordC*)a.first_wg;
+    const int lo = group_member_of(first_wg, a.count, b);
     GroupContractMemberC& m = ((GroupContractMemberC*)a.members)[lo];
     OpTab t;
 #pragma unroll
@@ -94,7 +86,7 @@ static int go_gc(const GroupPlan& g, hipStream_t s, F f) {
     std::memset(&a, 0, sizeof a);
     a.members = (const GroupContractMemberD*)g.d_members;
     a.first_wg = (const uint32_t*)g.d_first;
-    a.count = (int32_t)g.cmembers.size();
+    a.count = (int32_t)g.contract.members.size();
     a.wg0 = 0;
     a.redop = c.redop;
     for (int k = 0; k < 3; ++k) {
@@ -102,8 +94,8 @@ static int go_gc(const GroupPlan& g, hipStream_t s, F f) {
         a.conj[k] = c.conj[k];
     }
     const unsigned grid = g.first_wg.back();
-    if (g.rb == 2) return launch_gc<T, F, MIXED, 2>(c, a, grid, s, f);
-    if (g.rb == 1) return launch_gc<T, F, MIXED, 1>(c, a, grid, s, f);
+    if (g.contract.rb == 2) return launch_gc<T, F, MIXED, 2>(c, a, grid, s, f);
+    if (g.contract.rb == 1) return launch_gc<T, F, MIXED, 1>(c, a, grid, s, f);
     return set_error(SMR_EINVAL, "contraction group: no kernel for this tile");
 }
 

@@ -1,9 +1,10 @@
 // smr_k_group.hip -- grouped launches: K small independent maps (one functor f, the same operand types; rank, dims, strides,
 // pointers and offsets of their own) in ONE launch of 256-lane workgroups.  The grid is the sum of the members' workgroup counts:
-// a workgroup finds its member by a binary search of the prefix sums first_wg[] with its index in the group (blockIdx.x + wg0: a
-// launch may be one contiguous block range of the group, which is how a recorded sequence spreads one group over several hardware
-// queues) and reads the member's descriptor (smr_group.h: GroupMemberD).  Both steps use wave-uniform indices only, so they stay in scalar registers.  Two bodies, chosen
-// per member by the group planner (smr_group.cpp):
+// a workgroup finds its member by a binary search of the prefix sums first_wg[] (smr_group.h: group_member_of, shared with the
+// contraction groups' kernel) with its index in the group (blockIdx.x + wg0: a launch may be one contiguous block range of the group,
+// which is how a recorded sequence spreads one group over several hardware queues) and reads the member's descriptor (smr_group.h:
+// GroupMemberD).  Both steps use wave-uniform indices only, so they stay in scalar registers.  Two bodies, chosen per member by the
+// group planner (smr_plan_group.cpp):
 //   linear       destination-fastest enumeration, GROUP_CHUNK consecutive canonical indices per workgroup, GROUP_U per lane
 //                (256 apart: a wave's accesses are consecutive).  The index is decomposed once per lane and then stepped by the
 //                mixed-radix digits of 256.  Correct for any strides; coalesced when the inputs are unit-stride or broadcast
@@ -30,12 +31,6 @@
 
 namespace smr {
 
-// The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
-// space they are fetched by scalar loads into scalar registers, not once per lane.
-typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
-typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
-typedef const double __attribute__((address_space(4))) GroupConstC;
-
 struct GroupArgs {
     const GroupMemberD* members;
     const uint32_t* first_wg;  // count + 1 prefix sums
@@ -51,15 +46,10 @@ template <class T, class F, bool MIXED, bool VARC = false>
 SMR_DEV void group_body(const GroupArgs a, F f) {
     __shared__ T tile[GROUP_TILE * (GROUP_TILE + 1)];
     const int nin = (F::NIN >= 0) ? F::NIN : a.M - 1;
-    // the member of this workgroup: the last one whose first workgroup is <= its index in the group (every member has at least one)
+    // the member of this workgroup, by its index in the group (smr_group.h: group_member_of)
     const uint32_t b = blockIdx.x + a.wg0;
     GroupWordC* const first_wg = (GroupWordC*)a.first_wg;
-    int lo = 0, hi = a.count;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (first_wg[mid] <= b) lo = mid;
-        else hi = mid;
-    }
+    const int lo = group_member_of(first_wg, a.count, b);
     GroupMemberC& m = ((GroupMemberC*)a.members)[lo];
     const uint32_t w = b - first_wg[lo];
     if constexpr (VARC) f.set_consts((GroupConstC*)a.consts + (i64)lo * a.W);
@@ -210,28 +200,29 @@ static int go(const GroupPlan& g, hipStream_t s, F f) {
     GroupArgs a;
     a.members = (const GroupMemberD*)g.d_members;
     a.first_wg = (const uint32_t*)g.d_first;
-    a.count = (int32_t)g.members.size();
+    a.count = (int32_t)g.map.members.size();
     a.M = c.M;
     for (int k = 0; k < MAXM; ++k) {
         a.dtype[k] = k < c.M ? c.dtype[k] : 0;
         a.conj[k] = k < c.M ? c.conj[k] : 0;
     }
     a.wg0 = 0;
-    a.W = g.varc ? g.W : 0;
-    a.consts = g.varc ? (const double*)g.d_consts : nullptr;
+    const bool varc = g.map.varc;
+    a.W = varc ? g.map.W : 0;
+    a.consts = varc ? (const double*)g.map.d_consts : nullptr;
     const unsigned grid = g.first_wg.back();
     // the members are independent and a workgroup serves one member: any contiguous block range can be launched on its own.  `a` is
     // the first kernel parameter of k_group and of the runtime-compiled entry alike, so wg0 has one kernarg offset in both
     mark_sliceable(1, (unsigned)offsetof(GroupArgs, wg0), 0);
     if constexpr (is_jit<F>::value) {
         // the kernel argument kc holds member 0's constants and goes unused under VARC; the text depends on f's structure only
-        if (g.varc) return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED, true);
+        if (varc) return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED, true);
         return launch_jit<T>(c, s, "group", "smr::GroupArgs", "group_body", "", grid, 256, 0, a, MIXED);
     } else {
         if constexpr (takes_consts<F>::value) {
-            if (g.varc)
+            if (varc)
                 return launch_native(nullptr, 0, "k_group_varc", [&] { SMR_LAUNCH((k_group_varc<T, F, MIXED>), dim3(grid), dim3(256), 0, s, a, f); });
-        } else if (g.varc) {
+        } else if (varc) {
             return set_error(SMR_EINVAL, "group: per-member scalars planned for an f without constants");
         }
         return launch_native(nullptr, 0, "k_group", [&] { SMR_LAUNCH((k_group<T, F, MIXED>), dim3(grid), dim3(256), 0, s, a, f); });

@@ -47,7 +47,7 @@ static bool contract_gate(const Canon& c, const ContractPlan& cp) {
 }
 
 // The shape rules alone, without the "contract" option and its gate: is `c` an outer-product reduction this family's tile body can
-// run, and along which kept dims is it tiled?  plan_contract asks it for a single call, the group planner (smr_group.cpp) for every
+// run, and along which kept dims is it tiled?  plan_contract asks it for a single call, the group planner (smr_plan_group.cpp) for every
 // member of a contraction group.
 bool contract_shape(const Canon& c, int& di, int& dj) {
     if (c.redop == SMR_RED_NONE || c.M != 3 || c.bitcopy) return false;

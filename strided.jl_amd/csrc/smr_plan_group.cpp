@@ -1,0 +1,319 @@
+// smr_plan_group.cpp -- the group planner (smr_group.h: plan_group).  Host arithmetic only, no HIP runtime call: like every planner
+// file it links into tools/plan_dump.cpp, which pins the device tables of a corpus of groups.  One loop over the members: each is
+// canonicalised like a single call, checked against member 0 (one kernel instantiation, one f; under SMR_GROUP_MEMBER_SCALARS the
+// values of f's constants are the member's own, a row of a third table) and given its descriptor; its operands' byte ranges are the
+// independence check's input and the footprint of a group recorded in a sequence.  What differs between the kinds are plain functions
+// called from that loop: a map member takes one of the kernel's two bodies and its workgroups at once, a contraction its workgroups
+// once the whole group has decided the tile.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "smr_contract.h"
+#include "smr_group.h"
+
+namespace smr {
+
+i64& group_contract_tile() { static i64 v = 0; return v; }
+
+namespace {
+
+typedef std::vector<std::pair<uintptr_t, uintptr_t>> Spans;  // (smr_sched.h)
+
+std::string member_tag(int i) { return "smr_group_create: member " + std::to_string(i); }
+
+// does member `c` run the same kernel instantiation with the same functor as member 0 (`r`)?  Empty = yes, else what differs.
+// `own_scalars` (SMR_GROUP_MEMBER_SCALARS): the values of f's constants may differ, nothing else.
+std::string mismatch(const Canon& r, const Canon& c, bool own_scalars) {
+    if (c.bitcopy != r.bitcopy || (!c.bitcopy && c.ct != r.ct)) return "computes in another class than member 0";
+    if (c.mixed != r.mixed) return "differs from member 0 in whether operand types are converted";
+    if (c.M != r.M) return "has another number of distinct operands than member 0 (" + std::to_string(c.M) + " != " + std::to_string(r.M) + ")";
+    for (int k = 0; k < c.M; ++k) {
+        if (c.dtype[k] != r.dtype[k]) return "operand " + std::to_string(c.orig[k]) + " has another dtype than in member 0";
+        if (c.conj[k] != r.conj[k]) return "operand " + std::to_string(c.orig[k]) + " has another conj flag than in member 0";
+    }
+    const ProgD &p = c.prog, &q = r.prog;
+    if (p.len != q.len || p.nconst != q.nconst || std::memcmp(p.code, q.code, (size_t)(2 * p.len)) != 0 ||
+        (!own_scalars && std::memcmp(p.consts, q.consts, sizeof(double) * (size_t)(2 * p.nconst)) != 0))
+        return own_scalars ? "has another f-program than member 0 (only the values of its constants may differ)" : "has another f (program or constants) than member 0";
+    // recognition (smr_canon.cpp) looks at the program's structure, FK_EXPR5 also at a constant's value: one launch runs ONE functor
+    if (own_scalars && c.fkind != r.fkind) return "is recognised as another functor than member 0";
+    if (r.redop != SMR_RED_NONE) {  // a contraction group: one op and one initop code as well; beta (initarg) is the member's own
+        if (c.redop != r.redop) return "reduces with another op than member 0";
+        if (c.initop != r.initop) return "has another kind of initop than member 0 (only its argument, beta, may differ)";
+    }
+    return std::string();
+}
+
+// does the launch run a natively compiled functor that keeps constants in fields (with_functor, smr_dispatch.h)?  Its per-member
+// row is Canon::fc; every other f with constants is a program (runtime-compiled or interpreted) and its row is ProgD::consts.
+bool native_with_consts(const Canon& c) {
+    if (c.bitcopy || c.mixed || !(GROUP_FMASK & fbit(c.fkind))) return false;
+    const int k = c.fkind;
+    return k == FK_SCALE || k == FK_AXPY || k == FK_AXPBY || (k == FK_SYM && c.ct != SMR_I64) || (k == FK_EXPR5 && (c.ct == SMR_F32 || c.ct == SMR_F64));
+}
+
+// picks the body of one member and fills its descriptor; returns its number of workgroups
+i64 plan_member(const Canon& c, GroupMemberD& m) {
+    std::memset(&m, 0, sizeof m);
+    m.N = c.N;
+    m.total = (uint32_t)c.total;
+    for (int k = 0; k < c.M; ++k) {
+        m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+        for (int d = 0; d < c.N; ++d) m.strides[k][d] = c.strides[k][d];
+    }
+    for (int d = 0; d < MAXN; ++d) m.dims[d] = d < c.N ? (uint32_t)c.dims[d] : 1u;
+    {   // 256 in the mixed radix of the dims (what does not fit is beyond the box and never reached)
+        i64 rem = 256;
+        for (int d = 0; d < c.N; ++d) {
+            m.step[d] = (uint32_t)(rem % c.dims[d]);
+            rem /= c.dims[d];
+        }
+    }
+    // inputs whose unit-stride dim is another one than the destination's fastest dim (canonical dim 0)
+    int ntransposed = 0, kt = 0, q = 0;
+    for (int k = 1; k < c.M; ++k) {
+        const i64 s0 = c.strides[k][0] < 0 ? -c.strides[k][0] : c.strides[k][0];
+        if (s0 <= 1) continue;  // unit-stride or broadcast along dim 0
+        for (int d = 1; d < c.N; ++d)
+            if (c.strides[k][d] == 1 || c.strides[k][d] == -1) {
+                ++ntransposed;
+                kt = k;
+                q = d;
+                break;
+            }
+    }
+    if (ntransposed == 1 && c.dims[0] >= GROUP_TMIN && c.dims[q] >= GROUP_TMIN) {
+        m.form = GROUP_FORM_TRANSPOSING;
+        m.kt = kt;
+        m.q = q;
+        m.tbase = m.base[kt];
+        m.tsp = c.strides[kt][0];
+        m.tsq = c.strides[kt][q];
+        m.tdtype = c.dtype[kt];
+        m.tconj = c.conj[kt];
+        for (int k = 0; k < c.M; ++k) m.qstride[k] = c.strides[k][q];
+        m.ntp = (uint32_t)((c.dims[0] + GROUP_TILE - 1) / GROUP_TILE);
+        m.ntq = (uint32_t)((c.dims[q] + GROUP_TILE - 1) / GROUP_TILE);
+        i64 wgs = (i64)m.ntp * m.ntq;
+        for (int d = 1; d < c.N; ++d)
+            if (d != q) wgs *= c.dims[d];
+        return wgs;
+    }
+    m.form = GROUP_FORM_LINEAR;
+    return (c.total + GROUP_CHUNK - 1) / GROUP_CHUNK;
+}
+
+// Independence: no member's destination range may meet a range of ANOTHER member.  One sweep over the ranges sorted by their
+// start: a range meets an earlier one iff that one ends behind its start, so the two furthest-reaching ends seen so far (of
+// different members) decide -- among all ranges for a destination, among the destinations for an input.
+struct Range {
+    uintptr_t lo, hi;
+    int member;
+    bool write;
+};
+struct Reach {  // the furthest ends seen so far, of two different members
+    uintptr_t hi[2] = {0, 0};
+    int member[2] = {-1, -1};
+    void add(uintptr_t h, int mem) {
+        if (mem == member[0]) hi[0] = std::max(hi[0], h);
+        else if (member[0] < 0 || h > hi[0]) {
+            if (member[0] >= 0) { hi[1] = hi[0]; member[1] = member[0]; }
+            hi[0] = h;
+            member[0] = mem;
+        } else if (mem == member[1]) hi[1] = std::max(hi[1], h);
+        else if (member[1] < 0 || h > hi[1]) { hi[1] = h; member[1] = mem; }
+    }
+    // a member other than `mem` whose range ends behind `lo`, or -1
+    int meets(uintptr_t lo, int mem) const {
+        for (int i = 0; i < 2; ++i)
+            if (member[i] >= 0 && member[i] != mem && hi[i] > lo) return member[i];
+        return -1;
+    }
+};
+
+int check_independent(std::vector<Range>& rs) {
+    std::sort(rs.begin(), rs.end(), [](const Range& a, const Range& b) { return a.lo != b.lo ? a.lo < b.lo : a.member < b.member; });
+    Reach all, writes;
+    for (const Range& r : rs) {
+        const int other = (r.write ? all : writes).meets(r.lo, r.member);
+        if (other >= 0) {
+            const int wm = r.write ? r.member : other, om = r.write ? other : r.member;
+            return set_error(SMR_EUNSUPPORTED, member_tag(std::max(wm, om)) + ": the destination's byte range of member " + std::to_string(wm) +
+                                                   " meets a byte range of member " + std::to_string(om) +
+                                                   " (pass SMR_GROUP_INDEPENDENT if no element is shared, e.g. interleaved blocks of one parent)");
+        }
+        all.add(r.hi, r.member);
+        if (r.write) writes.add(r.hi, r.member);
+    }
+    return SMR_OK;
+}
+
+// the union of `rs` as sorted ranges, overlapping and adjacent ones merged (a 128-member group hands a sequence's scheduler a
+// handful of ranges, not 256)
+Spans merged(Spans rs) {
+    std::sort(rs.begin(), rs.end());
+    Spans out;
+    for (const auto& r : rs) {
+        if (r.second <= r.first) continue;
+        if (!out.empty() && r.first <= out.back().second) out.back().second = std::max(out.back().second, r.second);
+        else out.push_back(r);
+    }
+    return out;
+}
+
+// workgroups [first_wg[i], first_wg[i] + wgs) go to member i: the one place the group's grid grows
+int assign_workgroups(GroupPlan& g, int i, i64 wgs) {
+    const i64 grid = (i64)g.first_wg[(size_t)i] + wgs;
+    if (grid > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, member_tag(i) + ": the group needs more than 2^31 - 1 workgroups");
+    g.first_wg[(size_t)i + 1] = (uint32_t)grid;
+    return SMR_OK;
+}
+
+// ---- map groups ------------------------------------------------------------------------------------------------------------------
+// member i: under SMR_GROUP_MEMBER_SCALARS its row of the constant table (what its own canonicalisation handed the functor), its body
+int map_member(GroupPlan& g, int i, const Canon& c, bool own_scalars) {
+    GroupMapPlan& mp = g.map;
+    if (own_scalars) {
+        const bool native_row = native_with_consts(g.c);
+        if (i == 0) mp.W = native_row ? 4 : (c.bitcopy ? 0 : 2 * c.prog.nconst);
+        const double* row = native_row ? c.fc : c.prog.consts;
+        mp.consts.insert(mp.consts.end(), row, row + mp.W);
+    }
+    const i64 wgs = plan_member(c, mp.members[(size_t)i]);
+    (mp.members[(size_t)i].form ? mp.ntrans : mp.nlinear) += 1;
+    return assign_workgroups(g, i, wgs);
+}
+
+// bit-equal rows (-0.0 differs from 0.0), or none: the group is the one the call without the flag plans, no third table
+void map_finish(GroupMapPlan& mp, int count) {
+    const size_t row = sizeof(double) * (size_t)mp.W;
+    for (int i = 1; i < count && !mp.varc; ++i) mp.varc = row && std::memcmp(mp.consts.data(), mp.consts.data() + (size_t)i * mp.W, row) != 0;
+    if (!mp.varc) {
+        std::vector<double>().swap(mp.consts);
+        mp.W = 0;
+    }
+}
+
+const char* independent_tag(uint32_t flags) { return (flags & SMR_GROUP_INDEPENDENT) ? " independent=asserted" : ""; }
+
+void map_describe(GroupPlan& g, uint32_t flags) {
+    static const char* names[FK_COUNT] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
+    const Canon& c = g.c;
+    // what launch_group_ct() does: with_prog (runtime compilation first) for a mixed group and for an f without a native functor.
+    // FK_PROG has a bit in GROUP_FMASK like every kind, so the mask alone does not tell
+    const int fk = (!c.mixed && (GROUP_FMASK & fbit(c.fkind))) ? c.fkind : FK_PROG;
+    g.jit = options().jit && !c.bitcopy && fk == FK_PROG;
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "family=group members=%zu grid=%u linear=%d transposing=%d f=%s jit=%d bytes=%lld%s%s", g.rank.size(), g.first_wg.back(),
+                  g.map.nlinear, g.map.ntrans, c.bitcopy ? "bitcopy" : names[fk], g.jit ? 1 : 0, (long long)g.algbytes, independent_tag(flags),
+                  (flags & SMR_GROUP_MEMBER_SCALARS) ? (g.map.varc ? " scalars=member" : " scalars=shared") : "");
+    g.desc = buf;
+}
+
+// ---- contraction groups ------------------------------------------------------------------------------------------------------
+// the descriptor of a member tiled along di / dj (the tile-dependent fields are set again by contract_finish)
+void contract_member(GroupContractMemberD& m, const Canon& c, int di, int dj) {
+    std::memset(&m, 0, sizeof m);
+    for (int k = 0; k < 3; ++k) m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+    contract_fill(m, c, di, dj, contract_vec_of(c, di, dj, nullptr), 1);
+}
+
+// the group's tile, then every member's tiles and workgroups
+int contract_finish(GroupPlan& g) {
+    i64 wgs32 = 0, outputs = 0;  // over the group: workgroups on 32 x 32 tiles, destination elements
+    for (const GroupContractMemberD& m : g.contract.members) {
+        i64 rest = 1;
+        for (int n = 0; n < m.nrd; ++n) rest *= m.dims[m.rdim[n]];
+        wgs32 += ((m.dims[m.di] + 31) / 32) * ((m.dims[m.dj] + 31) / 32) * rest;
+        outputs += m.dims[m.di] * m.dims[m.dj] * rest;
+    }
+    // One tile size per group.  The single call's rule, read over the whole group: 32 x 32 (2 x 2 outputs per lane) when the group
+    // then still has a workgroup per CU -- 256, the threshold measured for single calls (smr_plan_contract.cpp) -- AND those tiles are
+    // at least half full over the group (outputs >= 1/2 * 1024 * tiles): members of 16 or 24 along a dim would otherwise stage and
+    // compute mostly padding.  Measured (tools/group_contract_vs_single.py, profiles/group_contract.txt): 64 blocks of 64^3 Float64,
+    // every tile of either size full, 32 x 32 7.82 us against 16 x 16 8.15 us -- what this rule picks there.  The half-full condition
+    // is NOT measured: that is the only row timed under both tiles, and none has partly filled 32 x 32 tiles.
+    const int es = dtype_size(g.c.ct);
+    const i64 force = group_contract_tile();
+    int rb = force == 32 ? 2 : (force == 16 ? 1 : ((wgs32 >= 256 && 2 * outputs >= 1024 * wgs32) ? 2 : 1));
+    // the LDS is static: a budget below the tile's takes 16 x 16, or refuses
+    const i64 cap = std::min<i64>(options().max_lds_bytes, 65536);
+    while (rb >= 1 && (i64)contract_lds(es, rb) > cap) rb >>= 1;
+    if (rb < 1) return set_error(SMR_EUNSUPPORTED, "smr_group_create: the 16 x 16 tile of a contraction group does not fit max_lds_bytes");
+    g.contract.rb = rb;
+    for (size_t i = 0; i < g.contract.members.size(); ++i)
+        if (int rc = assign_workgroups(g, (int)i, contract_set_tile(g.contract.members[i], es, rb))) return rc;
+    return SMR_OK;
+}
+
+void contract_describe(GroupPlan& g, uint32_t flags) {
+    static const char* ops[] = {"none", "+", "*", "min", "max", "&", "|"};
+    // launch_group_contract_ct(): the product of same-typed operands is native, every other f a program
+    const bool native = !g.c.mixed && g.c.fkind == FK_MUL2;
+    const int es = dtype_size(g.c.ct), rb = g.contract.rb;
+    g.jit = options().jit && !native;
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "family=group kind=contract members=%zu grid=%u tile=%d k=%d lds=%zu f=%s op=%s jit=%d bytes=%lld%s", g.rank.size(), g.first_wg.back(),
+                  CONTRACT_LANES * rb, contract_tk(es, rb), contract_lds(es, rb), native ? "mul2" : "prog", g.c.redop >= 0 && g.c.redop < 7 ? ops[g.c.redop] : "?",
+                  g.jit ? 1 : 0, (long long)g.algbytes, independent_tag(flags));
+    g.desc = buf;
+}
+
+}  // namespace
+
+int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g) {
+    const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0, independent = (flags & SMR_GROUP_INDEPENDENT) != 0;
+    const bool contraction = members[0].redop != SMR_RED_NONE;  // the kind is member 0's
+    if (contraction && own_scalars)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a contraction group (member 0 is a reduction): per-member constants of f are not supported there");
+    g.kind = contraction ? GROUP_CONTRACT : GROUP_MAP;
+    g.first_wg.assign((size_t)count + 1, 0);
+    g.rank.resize((size_t)count);
+    if (contraction) g.contract.members.resize((size_t)count);
+    else g.map.members.resize((size_t)count);
+    std::vector<Range> ranges;
+    Spans rd, wr;
+    for (int i = 0; i < count; ++i) {
+        const smr_problem& p = members[i];
+        // admit: a map group holds maps only, a contraction group reductions of the contraction shape only
+        if ((p.redop != SMR_RED_NONE) != contraction)
+            return set_error(SMR_EUNSUPPORTED, member_tag(i) + (contraction ? " is a map; a contraction group (member 0 is a reduction) holds contractions only"
+                                                                             : " is a reduction; a group holds maps only"));
+        Canon ci;
+        Canon& c = i == 0 ? g.c : ci;
+        if (int rc = canonicalise(&p, c)) return set_error(rc, member_tag(i) + ": " + smr_last_error());
+        int di = -1, dj = -1;
+        if (contraction && !contract_shape(c, di, dj))
+            return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction, but not of the contraction shape: two inputs that vary along different kept dims of "
+                                                                "extent > 1 and both along a reduced dim, neither on the destination's buffer; a group holds maps only, or such contractions only");
+        if (i > 0) {
+            const std::string why = mismatch(g.c, c, own_scalars);
+            if (!why.empty()) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
+        }
+        if (c.total > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " has more than 2^31 - 1 box elements");
+        g.rank[(size_t)i] = c.N;
+        g.algbytes += c.algbytes;
+        // the bounding byte range of every operand: compared for the independence check (skipped under SMR_GROUP_INDEPENDENT) and
+        // always kept as the group's footprint, which stays conservative for interleaved members
+        for (int k = 0; k < c.M; ++k) {
+            Range r{0, 0, i, k == 0};
+            operand_span(c, k, c.base[k], r.lo, r.hi);
+            (r.write ? wr : rd).emplace_back(r.lo, r.hi);
+            if (!independent) ranges.push_back(r);
+        }
+        // a map member takes its workgroups here; a contraction's depend on the tile, which contract_finish picks for the whole group
+        if (contraction) contract_member(g.contract.members[(size_t)i], c, di, dj);
+        else if (int rc = map_member(g, i, c, own_scalars)) return rc;
+    }
+    if (!contraction) map_finish(g.map, count);
+    else if (int rc = contract_finish(g)) return rc;
+    if (int rc = independent ? SMR_OK : check_independent(ranges)) return rc;
+    g.rd = merged(std::move(rd));
+    g.wr = merged(std::move(wr));
+    if (contraction) contract_describe(g, flags);
+    else map_describe(g, flags);
+    return SMR_OK;
+}
+
+}  // namespace smr

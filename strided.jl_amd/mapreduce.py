@@ -491,13 +491,15 @@ class group:
         # another kernel signature, and one bucket of them would be refused as a group
         ops = [(a._base, a.offset, a.op, tuple(st for d, st in zip(c.dims, a.strides) if d != 1)) for a in arrays[1:]]
         same = tuple(ops.index(o) for o in ops)
-        if self.member_scalars:  # not the values, only what they decide in canonicalise(): count, complex or not, integer class or not
+        # what the constants contribute.  A contraction group has one f: their values, whatever member_scalars says.  Under
+        # member_scalars a map contributes only what they decide in canonicalise(): count, complex or not, integer class or not
+        if self.member_scalars and op is None:
             ck = (len(consts), any(v.imag != 0 for v in consts), all(_integer_valued(v) for v in consts))
         else:
             ck = tuple(consts)
-        c.bucket = (bytes(code), ck, tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream)
-        if op is not None:  # one f (the constants' values whatever member_scalars says), one op, one kind of initop; beta is the member's
-            c.bucket = c.bucket[:1] + (tuple(consts),) + c.bucket[2:] + ("contract", _redop_code(op), _initop_code(initop)[0])
+        # a bucket of contractions also has one op and one kind of initop; beta is the member's
+        tail = () if op is None else ("contract", _redop_code(op), _initop_code(initop)[0])
+        c.bucket = (bytes(code), ck, tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream) + tail
         c.wr = _byte_range(arrays[0])  # (a reduction also reads its destination: a write range conflicts with everything a read does)
         c.rd = [_byte_range(a) for a in arrays[1:]]
         c.key = _problem_key(f, op, initop, c.dims, arrays)
@@ -517,11 +519,14 @@ class group:
             self._launch(members, members[0].stream)
 
     def _launch(self, calls, stream):
+        # a bucket of contractions: the library is not passed member_scalars, and plans under the forced tile, if any
+        if calls[0].op is not None:
+            scalars, tile = False, L.get_option("group_contract_tile")
+        else:
+            scalars, tile = self.member_scalars, 0
         key = None
-        reducing = calls[0].op is not None  # a bucket of contractions: the library is not passed member_scalars
-        scalars = self.member_scalars and not reducing
         if all(c.key is not None for c in calls):
-            key = (tuple(c.key for c in calls), self.independent, scalars, stream, L.get_option("group_contract_tile") if reducing else 0)
+            key = (tuple(c.key for c in calls), self.independent, scalars, stream, tile)
         grp = None
         if key is not None:
             try:

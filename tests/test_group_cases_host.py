@@ -1,7 +1,7 @@
 """Grouped launches, host side (no device): every recipe of tests/group_cases.py is planned on its host views through L.Group /
 smr_group_create, and smr_group_layout / smr_group_describe must show that it hits what it claims -- the body of each member, the
 canonical ranks, the position of the tiled dim, ragged last chunks, the member counts, the functor names.  A reader without a GPU can
-check here what tests/test_gpu_group_fuzz.py covers.  Then: check_independent (csrc/smr_group.cpp) against a brute-force pairwise test."""
+check here what tests/test_gpu_group_fuzz.py covers.  Then: check_independent (csrc/smr_plan_group.cpp) against a brute-force pairwise test."""
 import re
 
 import numpy as np

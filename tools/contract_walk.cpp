@@ -15,6 +15,7 @@ namespace smr {
 int set_error(int code, const std::string&) { return code; }
 int cu_count() { return 256; }
 }  // namespace smr
+extern "C" const char* smr_last_error(void) { return ""; }  // (the group planner, linked with the other planner files, quotes it)
 using namespace smr;
 
 int main() {

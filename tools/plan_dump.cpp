@@ -7,19 +7,31 @@
 //   cd strided.jl_amd/csrc && hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -x hip \
 //       ../../tools/plan_dump.cpp smr_plan*.cpp smr_canon.cpp -fsanitize=address,undefined -o /tmp/plan_dump_asan
 // To count which builder made a TILED work list, every such problem is planned twice more with one planner switch set (list_with).
-// It exits with status 1 when too few problems reach one of the work-list builders or input variants (`need`): a comparison of nothing passes.
+// The last section plans a fixed corpus of GROUPS through plan_group (smr_plan_group.cpp): one line per group, "group <id>", with
+// describe()'s string and a digest over the kind, the raw bytes of the device tables (member descriptors, first_wg, scalar rows),
+// W, varc, rb, rank, jit, algbytes and the rd / wr footprint -- or, for a group the planner refuses, its status and message.  The
+// corpus restates the recipes and the refusals of tests/group_cases.py, group_scalar_cases.py, group_contract_cases.py and the group
+// host tests over fake addresses.  (smr_group_create's own argument checks -- null, count, unknown flag -- are not the planner's.)
+// It exits with status 1 when too few problems reach one of the work-list builders or input variants (`need`), when a group kind, body,
+// tile, scalar form or refusal is not reached (`gneed`), or when a group is refused or accepted against its recipe: a comparison of
+// nothing passes.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../strided.jl_amd/csrc/smr_internal.h"
+#include "../strided.jl_amd/csrc/smr_group.h"
 
+static std::string last_error;  // what a refused group prints
 namespace smr {
-int set_error(int code, const std::string&) { return code; }
+int set_error(int code, const std::string& msg) {
+    last_error = msg;
+    return code;
+}
 int cu_count() { return 256; }
 }  // namespace smr
+extern "C" const char* smr_last_error(void) { return last_error.c_str(); }
 using namespace smr;
 
 struct Fnv {
@@ -204,6 +216,314 @@ static std::string ident(const std::vector<i64>& dims, int dtype, const std::vec
     return s + " " + what;
 }
 
+// ---- groups (smr_plan_group.cpp: plan_group) -----------------------------------------------------------------------------------------
+// The recipes of tests/group_cases.py, tests/group_scalar_cases.py and tests/group_contract_cases.py and the refusals of the group
+// host tests, restated over fake addresses: operand k of member `slot` has a 16 MiB region of its own unless a recipe shares one.
+static uint64_t digest(const GroupPlan& g) {
+    Fnv f;
+    f.v((int)g.kind);
+    f.v(g.map.members.size()); f.bytes(g.map.members.data(), g.map.members.size() * sizeof(GroupMemberD));
+    f.v(g.contract.members.size()); f.bytes(g.contract.members.data(), g.contract.members.size() * sizeof(GroupContractMemberD));
+    f.vec(g.first_wg); f.vec(g.map.consts);
+    f.v(g.map.W); f.v((int)g.map.varc); f.v(g.contract.rb); f.vec(g.rank); f.v((int)g.jit); f.v(g.algbytes);
+    for (const auto* spans : {&g.rd, &g.wr}) {
+        f.v(spans->size());
+        for (const auto& r : *spans) { f.v(r.first); f.v(r.second); }
+    }
+    return f.h;
+}
+
+enum { G_MAP, G_CONTRACT, G_LINEAR, G_TRANSPOSING, G_TILE16, G_TILE32, G_RULE16, G_RULE32, G_SCALARS_MEMBER, G_SCALARS_SHARED, G_REFUSED, G_COUNT };
+static const char* gname[] = {"group_map", "group_contract", "group_body_linear", "group_body_transposing", "group_tile_16", "group_tile_32",
+                              "group_rule_picks_16", "group_rule_picks_32", "group_scalars_member", "group_scalars_shared", "group_refusals"};
+static const long gneed[G_COUNT] = {20, 10, 20, 8, 4, 4, 2, 2, 5, 3, 34};  // (refusals: every one the corpus lists)
+static long gcounts[G_COUNT], glines, gwrong;
+
+static char* gaddr(int slot, int k) { return (char*)0x7c0000000000ull + ((i64)slot << 28) + ((i64)k << 24); }
+static const double* consts_of(std::initializer_list<double> re_im) {
+    static std::vector<std::vector<double>> pool;  // (kept for the run: problems point into it)
+    pool.emplace_back(re_im);
+    return pool.back().data();
+}
+typedef std::vector<uint8_t> Prog;
+static const Prog P_IDENT = {}, P_ADD2 = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_ADD, 0}, P_SCALE = {SMR_OP_ARG, 1, SMR_OP_CONST, 0, SMR_OP_MUL, 0},
+                  P_PLUSC = {SMR_OP_ARG, 1, SMR_OP_CONST, 0, SMR_OP_ADD, 0}, P_MUL = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0},
+                  P_AXPBY = {SMR_OP_CONST, 0, SMR_OP_ARG, 1, SMR_OP_MUL, 0, SMR_OP_CONST, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0, SMR_OP_ADD, 0},
+                  P_AXPBY_MERGED = {SMR_OP_CONST, 0, SMR_OP_ARG, 1, SMR_OP_MUL, 0, SMR_OP_CONST, 0, SMR_OP_ARG, 2, SMR_OP_MUL, 0, SMR_OP_ADD, 0},
+                  P_AXPY = {SMR_OP_CONST, 0, SMR_OP_ARG, 1, SMR_OP_MUL, 0, SMR_OP_ARG, 2, SMR_OP_ADD, 0},
+                  P_PROG = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0, SMR_OP_ARG, 1, SMR_OP_CONST, 0, SMR_OP_DIV, 0, SMR_OP_SUB, 0},
+                  P_MATH = {SMR_OP_ARG, 1, SMR_OP_TAN, 0, SMR_OP_ARG, 2, SMR_OP_ADD, 0}, P_MULC = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0, SMR_OP_CONST, 0, SMR_OP_MUL, 0},
+                  P_DIST = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_SUB, 0, SMR_OP_ABS, 0};
+static void set_f(smr_problem& p, const Prog& prog, std::initializer_list<double> re_im = {}) {
+    p.fprog = prog.empty() ? nullptr : prog.data();
+    p.fprog_len = (int)prog.size() / 2;
+    p.nconsts = (int)re_im.size() / 2;
+    p.fconsts = re_im.size() ? consts_of(re_im) : nullptr;
+}
+// a map member: column-major destination of `dims`, input k the view `views[k]` of a column-major parent (add_input)
+static smr_problem gmap(int slot, const std::vector<i64>& dims, const std::vector<Perm>& views, const Prog& prog = P_IDENT,
+                        std::initializer_list<double> re_im = {}, int dtype = SMR_F64, int in_dtype = -1) {
+    smr_problem p = problem(dims, dtype, views, DISTINCT, ~0u, false);
+    p.ops[0].base = gaddr(slot, 0);
+    for (int k = 1; k < p.M; ++k) {
+        p.ops[k].base = gaddr(slot, k);
+        if (in_dtype >= 0) p.ops[k].dtype = in_dtype;
+    }
+    set_f(p, prog, re_im);
+    return p;
+}
+static smr_problem gcopy(int slot, const std::vector<i64>& dims, int dtype = SMR_F64) { return gmap(slot, dims, {rotation((int)dims.size(), 0)}, P_IDENT, {}, dtype); }
+static smr_problem gtrans(int slot, i64 m, i64 n, const Prog& prog = P_IDENT, std::initializer_list<double> re_im = {}) { return gmap(slot, {m, n}, {{1, 0}}, prog, re_im); }
+// a contraction member over box (m, n, [batch], k, [k2]): the destination varies along m, n and batch, input 1 along all but n, input 2
+// along all but m; `kfirst` bit k: that input's parent is laid out reduced dims first; `pad` extends every parent dim by that much
+static smr_problem gmul(int slot, const std::vector<i64>& dims, int nkept, int dtype = SMR_F64, unsigned kfirst = 0, int pad = 0, int initop = SMR_INIT_ZERO, double beta = 0) {
+    smr_problem p;
+    std::memset(&p, 0, sizeof p);
+    p.N = (int)dims.size();
+    p.M = 3;
+    for (int d = 0; d < p.N; ++d) p.dims[d] = dims[d];
+    for (int o = 0; o < 3; ++o) {
+        i64 acc = 1;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int d = 0; d < p.N; ++d) {
+                const bool varies = o == 0 ? d < nkept : (o == 1 ? d != 1 : d != 0);
+                const bool first = (o > 0 && (kfirst >> o & 1)) ? d >= nkept : d < nkept;
+                if (varies && first == (pass == 0)) {
+                    p.ops[o].strides[d] = acc;
+                    acc *= dims[d] + pad;
+                }
+            }
+        p.ops[o].base = gaddr(slot, o);
+        p.ops[o].dtype = dtype;
+    }
+    set_f(p, P_MUL);
+    p.redop = SMR_RED_ADD;
+    p.initop = initop;
+    p.initarg[0] = beta;
+    return p;
+}
+static smr_problem gmm(int slot, i64 m, i64 n, i64 k, int dtype = SMR_F64, unsigned kfirst = 0, int pad = 0, int initop = SMR_INIT_ZERO, double beta = 0) {
+    return gmul(slot, {m, n, k}, 2, dtype, kfirst, pad, initop, beta);
+}
+
+// plans one group and prints its line; `refused`: the recipe is one the library refuses (the line then holds status and message)
+static void plan_one_group(const std::string& id, const std::vector<smr_problem>& ms, uint32_t flags = 0, bool refused = false, i64 tile = 0) {
+    const i64 saved = group_contract_tile();
+    group_contract_tile() = tile;
+    GroupPlan g;
+    const int rc = plan_group(ms.data(), (int)ms.size(), flags, g);
+    group_contract_tile() = saved;
+    ++glines;
+    if ((rc != 0) != refused) ++gwrong;
+    if (rc) {
+        std::printf("group %s | rc=%d | %s\n", id.c_str(), rc, last_error.c_str());
+        ++gcounts[G_REFUSED];
+        return;
+    }
+    std::printf("group %s | %s | %016llx\n", id.c_str(), g.desc.c_str(), (unsigned long long)digest(g));
+    if (g.kind == GROUP_CONTRACT) {
+        ++gcounts[G_CONTRACT];
+        ++gcounts[g.contract.rb == 2 ? G_TILE32 : G_TILE16];
+        if (!tile) ++gcounts[g.contract.rb == 2 ? G_RULE32 : G_RULE16];
+    } else {
+        ++gcounts[G_MAP];
+        gcounts[G_LINEAR] += g.map.nlinear > 0;
+        gcounts[G_TRANSPOSING] += g.map.ntrans > 0;
+        if (flags & SMR_GROUP_MEMBER_SCALARS) ++gcounts[g.map.varc ? G_SCALARS_MEMBER : G_SCALARS_SHARED];
+    }
+}
+
+static void group_corpus() {
+    const uint32_t IND = SMR_GROUP_INDEPENDENT, OWN = SMR_GROUP_MEMBER_SCALARS;
+    typedef std::vector<smr_problem> Ms;
+    // the layout test's shapes: both bodies in one group, 1024 / 1025 elements on either side of a chunk, rank 8
+    const std::vector<std::vector<i64>> shapes = {{1}, {5, 7}, {31, 33}, {33, 31}, {64, 1, 3}, {4, 4, 4, 4, 4, 4, 4, 4}, {1024}, {1025}, {40, 40, 3}};
+    auto layout_members = [&](const Prog& prog, bool own) {
+        Ms ms;
+        for (size_t i = 0; i < shapes.size(); ++i) {
+            const int N = (int)shapes[i].size();
+            Perm v(N);
+            std::vector<i64> dims(N);
+            for (int d = 0; d < N; ++d) v[d] = i % 2 ? N - 1 - d : d;
+            for (int d = 0; d < N; ++d) dims[d] = shapes[i][v[d]];
+            ms.push_back(prog.empty() ? gmap((int)i, dims, {v}) : gmap((int)i, dims, {v}, prog, {own ? 1 + (double)i / 8 : 2.5, 0}));
+        }
+        return ms;
+    };
+    for (uint32_t flags : {0u, IND}) plan_one_group("layout ident flags=" + std::to_string(flags), layout_members(P_IDENT, false), flags);
+    plan_one_group("layout scale", layout_members(P_SCALE, false));
+    plan_one_group("layout scale own=shared", layout_members(P_SCALE, false), OWN);
+    plan_one_group("layout scale own=member", layout_members(P_SCALE, true), OWN);
+    // GROUP_TMIN: 15 and 16 along dim 0 and along the staged input's unit-stride dim q, each alone and all in one group
+    Ms tmin;
+    for (i64 e : {15, 16})
+        for (int side = 0; side < 2; ++side) {
+            tmin.push_back(side ? gtrans((int)tmin.size(), 40, e) : gtrans((int)tmin.size(), e, 40));
+            plan_one_group("tmin " + std::to_string(e) + (side ? " along q" : " along dim 0"), {tmin.back()});
+        }
+    plan_one_group("tmin all", tmin);
+    for (int dt : {SMR_F32, SMR_F64, SMR_C32, SMR_C64}) {  // per type: one member per body, two and three inputs, outer dims around the plane
+        const std::string t = dt_name[dt];
+        plan_one_group("bodies " + t, {gmap(0, {33, 31}, {{0, 1}}, P_IDENT, {}, dt), gmap(1, {31, 33}, {{1, 0}}, P_IDENT, {}, dt), gmap(2, {20, 24, 28}, {{1, 2, 0}}, P_IDENT, {}, dt),
+                                      gmap(3, {17, 3, 40}, {{2, 1, 0}}, P_IDENT, {}, dt), gmap(4, {1, 1}, {{0, 1}}, P_IDENT, {}, dt)});
+        plan_one_group("add2 " + t, {gmap(0, {40, 33}, {{0, 1}, {1, 0}}, P_ADD2, {}, dt), gmap(1, {17, 5}, {{0, 1}, {1, 0}}, P_ADD2, {}, dt), gmap(2, {3, 3, 3}, {{0, 1, 2}, {2, 1, 0}}, P_ADD2, {}, dt),
+                                    gmap(3, {24, 28, 20}, {{1, 2, 0}, {2, 0, 1}}, P_ADD2, {}, dt)});
+        plan_one_group("prog " + t, {gmap(0, {17, 5}, {{0, 1}, {1, 0}}, P_PROG, {3, 0}, dt), gmap(1, {40, 33}, {{0, 1}, {1, 0}}, P_PROG, {3, 0}, dt), gmap(2, {3, 3, 3}, {{0, 1, 2}, {2, 1, 0}}, P_PROG, {3, 0}, dt)}, IND);
+    }
+    // a bitcopy group (every integer width), a mixed group (Float32 inputs, Float64 destination) and an integer group (Int64 sums)
+    for (int dt : {SMR_I8, SMR_I16, SMR_I32, SMR_U64}) plan_one_group("bitcopy dtype=" + std::to_string(dt), {gcopy(0, {6, 5}, dt), gmap(1, {31, 33}, {{1, 0}}, P_IDENT, {}, dt), gcopy(2, {1025}, dt)});
+    plan_one_group("mixed", {gmap(0, {6, 5}, {{0, 1}}, P_IDENT, {}, SMR_F64, SMR_F32), gmap(1, {33, 40}, {{1, 0}}, P_IDENT, {}, SMR_F64, SMR_F32), gmap(2, {12}, {{0}}, P_IDENT, {}, SMR_F64, SMR_F32)});
+    plan_one_group("mixed scale own", {gmap(0, {4, 4}, {{0, 1}}, P_SCALE, {0.1, 0}, SMR_F32), gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {1.1, 0}, SMR_F32)}, OWN);
+    plan_one_group("integer add2", {gmap(0, {6, 5}, {{0, 1}, {1, 0}}, P_ADD2, {}, SMR_I64), gmap(1, {40, 33}, {{0, 1}, {1, 0}}, P_ADD2, {}, SMR_I64)});
+    plan_one_group("integer scale own", {gmap(0, {4, 4}, {{0, 1}}, P_SCALE, {3, 0}, SMR_I32), gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {5, 0}, SMR_I32)}, OWN);
+    // scalar rows: differing, bit-equal, -0.0 against 0.0 (differing), an f without constants; Canon::fc rows and ProgD::consts rows
+    auto scaled = [&](std::initializer_list<double> cs) {
+        Ms ms;
+        for (double v : cs) ms.push_back(gmap((int)ms.size(), {4, 4}, {{0, 1}}, P_SCALE, {v, 0}));
+        return ms;
+    };
+    plan_one_group("scalars differ", scaled({1, 1.125, 1.25}), OWN);
+    plan_one_group("scalars differ independent", scaled({1, 1.125, 1.25}), OWN | IND);
+    plan_one_group("scalars equal", scaled({2.5, 2.5, 2.5}), OWN);
+    plan_one_group("scalars equal, no flag", scaled({2.5, 2.5, 2.5}));
+    plan_one_group("scalars 0.0 and -0.0", scaled({0.0, -0.0}), OWN);
+    plan_one_group("scalars of an f without constants", {gcopy(0, {4, 4}), gcopy(1, {4, 4})}, OWN);
+    for (const Prog* f : {&P_AXPBY, &P_AXPY, &P_PROG}) {
+        Ms ms;
+        for (int i = 0; i < 3; ++i) ms.push_back(gmap(i, {33, 40}, {{0, 1}, {1, 0}}, *f, {1 + i / 8.0, 0, 2 - i / 16.0, 0}));
+        if (f != &P_AXPBY)
+            for (auto& m : ms) m.nconsts = 1;
+        plan_one_group(std::string("scalars rows of ") + (f == &P_AXPBY ? "axpby" : (f == &P_AXPY ? "axpy" : "prog")), ms, OWN);
+    }
+    plan_one_group("scalars complex", {gmap(0, {4, 4}, {{0, 1}}, P_SCALE, {2, 1}, SMR_C64), gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {2, -1}, SMR_C64)}, OWN);
+    // SMR_GROUP_INDEPENDENT: even and odd columns of one parent into even and odd columns of another; shared inputs, an in-place member
+    auto interleaved = [&](bool contraction) {
+        Ms ms;
+        for (int j = 0; j < 2; ++j) {
+            smr_problem p = contraction ? gmm(j, 16, 8, 5) : gcopy(j, {8, 4});
+            for (int k = 0; k < (contraction ? 1 : 2); ++k) {
+                p.ops[k].base = gaddr(0, k);
+                p.ops[k].offset = j * p.dims[0];
+                p.ops[k].strides[1] = 2 * p.dims[0];
+            }
+            ms.push_back(p);
+        }
+        return ms;
+    };
+    plan_one_group("interleaved maps", interleaved(false), 0, true);
+    plan_one_group("interleaved maps independent", interleaved(false), IND);
+    plan_one_group("interleaved contractions", interleaved(true), 0, true);
+    plan_one_group("interleaved contractions independent", interleaved(true), IND);
+    {
+        smr_problem ab = gcopy(0, {4, 4}), bc = gcopy(1, {4, 4}), ac = gcopy(1, {4, 4}), dd = gcopy(2, {4, 4});
+        bc.ops[1].base = ab.ops[0].base;  // reads what member 0 writes
+        ac.ops[1].base = ab.ops[1].base;  // shares member 0's input
+        dd.ops[1].base = dd.ops[0].base;  // in place
+        plan_one_group("chain", {ab, bc}, 0, true);
+        plan_one_group("shared input, in place", {ab, ac, dd});
+    }
+    // refusals of map groups
+    {
+        smr_problem red = problem({8, 8}, SMR_F64, {{0, 1}}, DISTINCT, 0u, true), bad = gcopy(1, {6, 5});
+        bad.dims[0] = 0;
+        plan_one_group("refused: a reduction in a map group", {gcopy(0, {6, 5}), red}, 0, true);
+        plan_one_group("refused: dtype", {gcopy(0, {6, 5}), gcopy(1, {6, 5}), gcopy(2, {6, 5}, SMR_F32)}, 0, true);
+        plan_one_group("refused: another constant", scaled({2, 3}), 0, true);
+        plan_one_group("refused: another program", {scaled({2})[0], gmap(1, {4, 4}, {{0, 1}}, P_PLUSC, {2, 0})}, 0, true);
+        plan_one_group("refused: a malformed member", {gcopy(0, {6, 5}), bad}, 0, true);
+        plan_one_group("refused: another number of operands", {gcopy(0, {6, 5}), gmap(1, {6, 5}, {{0, 1}, {1, 0}}, P_ADD2)}, 0, true);
+        plan_one_group("refused: converting and not", {gcopy(0, {6, 5}), gmap(1, {6, 5}, {{0, 1}}, P_IDENT, {}, SMR_F64, SMR_F32)}, 0, true);
+        smr_problem cj = gcopy(1, {6, 5}, SMR_C64);
+        cj.ops[1].conj = 1;
+        plan_one_group("refused: dtype of a bit copy", {gcopy(0, {6, 5}, SMR_I32), gcopy(1, {6, 5}, SMR_U32)}, 0, true);
+        plan_one_group("refused: conj flag", {gcopy(0, {6, 5}, SMR_C64), cj}, 0, true);
+        plan_one_group("refused own: another program", {scaled({2})[0], gmap(1, {4, 4}, {{0, 1}}, P_PLUSC, {2, 0})}, OWN, true);
+        plan_one_group("refused own: another program in member 2", {scaled({2})[0], gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {5, 0}), gmap(2, {4, 4}, {{0, 1}}, P_PLUSC, {2, 0})}, OWN, true);
+        plan_one_group("refused own: a complex scalar among real ones", {scaled({2})[0], gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {2, 1})}, OWN, true);
+        plan_one_group("refused own: leaves the integer class", {gmap(0, {4, 4}, {{0, 1}}, P_SCALE, {3, 0}, SMR_I32), gmap(1, {4, 4}, {{0, 1}}, P_SCALE, {2.5, 0}, SMR_I32)}, OWN, true);
+        smr_problem merged = gmap(1, {4, 4}, {{0, 1}, {1, 0}}, P_AXPBY_MERGED, {2, 0});
+        plan_one_group("refused own: equal constants merged", {gmap(0, {4, 4}, {{0, 1}, {1, 0}}, P_AXPBY, {2, 0, 3, 0}), merged}, OWN, true);
+        const Options saved = options();
+        options().jit = 0;
+        plan_one_group("refused: a math opcode without runtime compilation", {gmap(0, {6, 5}, {{0, 1}, {1, 0}}, P_MATH)}, 0, true);
+        options() = saved;
+        plan_one_group("refused: box elements", {gcopy(0, {6, 5}), gcopy(1, {65536, 32768})}, 0, true);
+        Ms many;  // 46340^2 elements are 2097066 workgroups: the sum crosses 2^31 - 1 at member 1024
+        for (int i = 0; i < 1100; ++i) many.push_back(gcopy(0, {46340, 46340}));
+        plan_one_group("refused: workgroups", many, IND, true);
+    }
+    // contraction groups: the rule's tile (16 x 16 under a workgroup per CU or under half-full 32 x 32 tiles, else 32 x 32), both forced
+    // tiles, ragged and whole tiles, padded parents (no vector loads), k-major inputs, a batch dim, two reduced dims, beta per member
+    auto blocks = [&](int count, i64 m, i64 n, i64 k, int dt = SMR_F64) {
+        Ms ms;
+        for (int i = 0; i < count; ++i) ms.push_back(gmm(i % 2048, m, n, k, dt));
+        return ms;
+    };
+    for (i64 tile : {0, 16, 32}) {
+        const std::string t = " tile=" + std::to_string(tile);
+        plan_one_group("contract 255 x 32^3" + t, blocks(255, 32, 32, 32), 0, false, tile);
+        plan_one_group("contract 256 x 32^3" + t, blocks(256, 32, 32, 32), 0, false, tile);
+        plan_one_group("contract 300 x 17x17x8" + t, blocks(300, 17, 17, 8), 0, false, tile);
+        plan_one_group("contract 300 x 24x24x8" + t, blocks(300, 24, 24, 8), 0, false, tile);
+        for (int dt : {SMR_F32, SMR_F64, SMR_C32, SMR_C64, SMR_I64}) {
+            const i64 tk = contract_tk(dtype_size(dt), 1);
+            Ms ms = {gmm(0, 15, 2, 2, dt), gmul(1, {48, 48, 3, 2}, 3, dt, 2u), gmm(2, 32, 32, tk, dt), gmm(3, 32, 32, 2 * tk, dt, 6u), gmm(4, 32, 32, 2 * tk + 1, dt, 2u),
+                     gmm(5, 32, 32, tk + 1, dt, 0, 1), gmm(6, 33, 17, 2 * tk + 1, dt, 4u, 1), gmul(7, {17, 33, 3, tk + 1}, 3, dt, 2u), gmul(8, {33, 15, tk + 1, 2}, 2, dt),
+                     gmm(9, 17, 31, 5, dt, 6u), gmm(10, 31, 17, 5, dt), gmm(11, 2, 15, tk, dt, 2u)};
+            for (size_t i = 0; i < ms.size(); ++i) {
+                ms[i].initop = SMR_INIT_SCALE;
+                ms[i].initarg[0] = 2 + (double)(i % 3);
+            }
+            plan_one_group("contract paths dtype=" + std::to_string(dt) + t, ms, 0, false, tile);
+            plan_one_group("contract one dtype=" + std::to_string(dt) + t, {gmm(0, 15, 16, tk + 1, dt, 4u)}, 0, false, tile);
+        }
+    }
+    {
+        Ms dist = blocks(3, 20, 24, 9), mn = blocks(3, 20, 24, 9), cst = blocks(2, 20, 24, 9);
+        for (auto& m : dist) set_f(m, P_DIST);
+        for (auto& m : mn) { m.redop = SMR_RED_MIN; m.initop = SMR_INIT_NONE; }
+        for (size_t i = 0; i < cst.size(); ++i) { cst[i].initop = SMR_INIT_CONST; cst[i].initarg[0] = 2 + (double)i; }
+        plan_one_group("contract another f", dist);
+        plan_one_group("contract min", mn);
+        plan_one_group("contract const beta", cst);
+        plan_one_group("contract two shapes", {gmm(0, 20, 24, 9, SMR_F32), gmm(1, 33, 17, 5, SMR_F32)});
+        Ms mixed = blocks(2, 20, 24, 9, SMR_F32);
+        for (auto& m : mixed) m.ops[0].dtype = SMR_F64;
+        plan_one_group("contract converting", mixed);
+        const Options saved = options();
+        options().max_lds_bytes = 20000;
+        plan_one_group("contract 32 forced, 20000 bytes of LDS", blocks(255, 32, 32, 32), 0, false, 32);
+        options().max_lds_bytes = 1000;
+        plan_one_group("refused: max_lds_bytes", blocks(2, 32, 32, 32), 0, true);
+        options() = saved;
+    }
+    // refusals of contraction groups
+    {
+        const smr_problem ok = gmm(0, 20, 24, 9), ok1 = gmm(1, 20, 24, 9), plain = problem({8, 8}, SMR_F64, {{0, 1}}, DISTINCT, 0u, true);
+        smr_problem mx = gmm(2, 20, 24, 9), sc = gmm(0, 20, 24, 9, SMR_F64, 0, 0, SMR_INIT_SCALE, 2), c2 = ok, c3 = ok1, onbuf = gmm(1, 8, 4, 4);
+        mx.redop = SMR_RED_MAX;
+        set_f(c2, P_MULC, {2, 0});
+        set_f(c3, P_MULC, {3, 0});
+        onbuf.ops[1].base = onbuf.ops[0].base;  // C[:, 0:4] = C[:, 4:8] * B
+        onbuf.ops[1].offset = 32;
+        plan_one_group("refused: a map in a contraction group", {ok, ok1, gcopy(2, {6, 5})}, 0, true);
+        plan_one_group("refused: member 0 is another reduction", {plain}, 0, true);
+        plan_one_group("refused: member 1 is another reduction", {ok, plain}, 0, true);
+        plan_one_group("refused: m = 1", {ok, gmm(1, 1, 24, 9)}, 0, true);
+        plan_one_group("refused: another op", {ok, ok1, mx}, 0, true);
+        plan_one_group("refused: another kind of initop", {sc, ok1}, 0, true);
+        plan_one_group("refused: another alpha", {c2, c3}, 0, true);
+        plan_one_group("refused: dtype of a contraction", {ok, gmm(1, 20, 24, 9, SMR_F32)}, 0, true);
+        plan_one_group("refused: an input on the destination's buffer", {ok, onbuf}, 0, true);
+        plan_one_group("refused: member scalars of a contraction group", {ok, ok1}, OWN, true);
+        plan_one_group("refused: a contraction in a map group", {gcopy(0, {6, 5}), ok1}, 0, true);
+        plan_one_group("refused: box elements of a contraction", {ok, gmm(1, 32768, 32768, 2)}, 0, true);
+        Ms many;  // 2^21 tiles of 16 x 16 each: the sum crosses 2^31 - 1 at member 1023
+        for (int i = 0; i < 1100; ++i) many.push_back(gmm(0, 32768, 16384, 2));
+        plan_one_group("refused: workgroups of a contraction group", many, IND, true, 16);
+    }
+}
+
 int main() {
     const int dtypes[] = {SMR_F32, SMR_F64, SMR_C64};
     const i64 ext[] = {3, 7, 8, 24, 32, 40, 48, 64, 100};
@@ -293,6 +613,7 @@ int main() {
             (void)n;
             plan_all(ident(mnk, dt, {}, "contraction"), p, DISTINCT);
         }
+    group_corpus();
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     std::fprintf(stderr, "%ld lines:", lines);
     for (int f = 1; f < 9; ++f) std::fprintf(stderr, " %s=%ld", fam[f], fam_lines[f]);
@@ -304,5 +625,11 @@ int main() {
     };
     for (int i = 0; i < C_COUNT; ++i) report(cname[i], counts[i]);
     for (int v = ONE; v <= STEPPED; ++v) report(var_name[v], var_lines[v]);
+    std::fprintf(stderr, "%ld group lines, %ld accepted or refused against the recipe's word\n", glines, gwrong);
+    if (gwrong) rc = 1;
+    for (int i = 0; i < G_COUNT; ++i) {
+        std::fprintf(stderr, "  %s: %ld%s\n", gname[i], gcounts[i], gcounts[i] < gneed[i] ? "  -- TOO FEW: the group corpus no longer covers this" : "");
+        if (gcounts[i] < gneed[i]) rc = 1;
+    }
     return rc;
 }
