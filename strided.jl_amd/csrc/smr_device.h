@@ -203,8 +203,26 @@ template <class R> SMR_DEV cplx<R> operator-(cplx<R> a) { return cplx<R>{-a.re, 
 template <class R> SMR_DEV cplx<R> operator*(cplx<R> a, cplx<R> b) {
     return cplx<R>{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
 }
-template <class R> SMR_DEV cplx<R> operator/(cplx<R> a, cplx<R> b) {
-    // scaled (Smith) division: avoids overflow of |b|^2
+// The ends of the range, per real type: a complex value whose larger part is >= big or < small is multiplied by a power of two
+// before hypot(x, y) + |x|, x*x + y*y or Smith's denominator is formed from it, and the result is scaled back (exact steps).
+//   big    hypot and b.re + b.im * r stay finite below it (2 * sqrt(2) * big < floatmax)
+//   small  above it nothing formed from the parts is subnormal; up = 4^upq brings every subnormal above it
+template <class R> struct cxlim;
+template <> struct cxlim<float> {
+    static constexpr float big = 0x1p124f, small = 0x1p-100f, up = 0x1p48f, up_sqrt_inv = 0x1p-24f, up_inv = 0x1p-48f, up_log2 = 48.f;
+    static constexpr float tanh_one = 22.5f;   // Base: 4|x| > asinh(floatmax): tanh(x + iy) is 1 to the last bit
+};
+template <> struct cxlim<double> {
+    static constexpr double big = 0x1p1020, small = 0x1p-900, up = 0x1p108, up_sqrt_inv = 0x1p-54, up_inv = 0x1p-108, up_log2 = 108.;
+    static constexpr double tanh_one = 177.75;
+};
+// 1/4, 1 or `up`: the factor that brings the larger part of (x, y) away from the ends of the range
+template <class R> SMR_DEV R mid_scale(R x, R y) {
+    const R m = fmax(fabs(x), fabs(y));
+    return m >= cxlim<R>::big ? R(0.25) : (m < cxlim<R>::small ? cxlim<R>::up : R(1));
+}
+// Smith's division: avoids overflow of |b|^2
+template <class R> SMR_DEV cplx<R> div_smith(cplx<R> a, cplx<R> b) {
     if (fabs(b.re) >= fabs(b.im)) {
         R r = b.im / b.re, den = b.re + b.im * r;
         return cplx<R>{(a.re + a.im * r) / den, (a.im - a.re * r) / den};
@@ -212,6 +230,19 @@ template <class R> SMR_DEV cplx<R> operator/(cplx<R> a, cplx<R> b) {
         R r = b.re / b.im, den = b.re * r + b.im;
         return cplx<R>{(a.re * r + a.im) / den, (a.im * r - a.re) / den};
     }
+}
+template <class R> SMR_DEV cplx<R> operator/(cplx<R> a, cplx<R> b) {
+    // Smith's division of operands that are scaled first where they lie at the ends of the range, each by its own power of two
+    // (Base's inv(::ComplexF64) does it for the divisor), so that neither the denominator nor a numerator overflows or goes
+    // subnormal where the quotient is representable; in the middle of the range (sa = sb = 1) every step is what it was
+    const R sa = mid_scale(a.re, a.im), sb = mid_scale(b.re, b.im);
+    a.re *= sa; a.im *= sa; b.re *= sb; b.im *= sb;
+    cplx<R> q = div_smith(a, b);
+    if (sa != sb) {  // q * (sb / sa), a power of two
+        const R back = sb * (sa == R(1) ? R(1) : (sa < R(1) ? R(4) : cxlim<R>::up_inv));
+        q.re *= back; q.im *= back;
+    }
+    return q;
 }
 
 template <class T> struct mathx;  // unary / binary ops of the f-program per compute type
@@ -273,7 +304,18 @@ struct mathx_real {
     static SMR_DEV R fma3(R a, R b, R c) { return fma(a, b, c); }
     template <int OP>
     static SMR_DEV R ext_un(R a) {
-        if constexpr (OP == SMR_OP_TAN) return tan(a);
+        // Float32 asin, atan and log10 of the device library miss both neighbours of the exact value on some arguments (by one step:
+        // tests/test_gpu_fprog_conformance.py); the Float64 function rounded once never does
+        if constexpr (sizeof(R) == 4 && (OP == SMR_OP_ASIN || OP == SMR_OP_ATAN || OP == SMR_OP_LOG10))
+            return (R)mathx_real<double>::template ext_un<OP>((double)a);
+        // expm1(x) and log1p(x) are x -+ x^2/2...: below 2^-54 (2^-25) x itself is a neighbour of the exact value.  The library returns
+        // +0.0 for -0.0 and flushes subnormal arguments.
+        else if constexpr (OP == SMR_OP_EXPM1 || OP == SMR_OP_LOG1P) {
+            if (fabs(a) < (sizeof(R) == 8 ? R(0x1p-54) : R(0x1p-25))) return a;
+            if constexpr (OP == SMR_OP_EXPM1) return expm1(a);
+            else return log1p(a);
+        }
+        else if constexpr (OP == SMR_OP_TAN) return tan(a);
         else if constexpr (OP == SMR_OP_ASIN) return asin(a);
         else if constexpr (OP == SMR_OP_ACOS) return acos(a);
         else if constexpr (OP == SMR_OP_ATAN) return atan(a);
@@ -297,7 +339,13 @@ struct mathx_real {
     static SMR_DEV R ext_bin(R a, R b) {
         if constexpr (OP == SMR_OP_POW) return pow(a, b);
         else if constexpr (OP == SMR_OP_ATAN2) return atan2(a, b);
-        else if constexpr (OP == SMR_OP_HYPOT) return hypot(a, b);
+        else if constexpr (OP == SMR_OP_HYPOT) {
+            if constexpr (sizeof(R) == 4) {  // the squares are exact in Float64 and cannot overflow: two roundings there, one to Float32
+                const double x = a, y = b;   // (the Float32 entry point misses both neighbours of the exact value on some arguments)
+                const R h = (R)sqrt(x * x + y * y);
+                return (fabs(a) == __builtin_huge_valf() || fabs(b) == __builtin_huge_valf()) ? (R)__builtin_huge_valf() : h;
+            } else return hypot(a, b);
+        }
         else if constexpr (OP == SMR_OP_REM) return fmod(a, b);
         else if constexpr (OP == SMR_OP_MOD) {  // Julia's mod(::T, ::T) for floats: floored, the result takes the sign of b
             const R r = fmod(a, b);
@@ -388,15 +436,35 @@ template <> struct mathx<ix64> {
 template <class R>
 struct mathx_cx {
     typedef cplx<R> T;
+    typedef cxlim<R> L;
+    // The complex functions follow Base/complex.jl where the textbook formulas lose a result that is representable: operands at the
+    // ends of the range are scaled by a power of four (mid_scale), |re| beyond the point where tanh is 1 takes its own branch, and on
+    // the real axis (imaginary part +-0) the real function is called and the zero keeps its sign, so that Inf * 0 never forms.
     static SMR_DEV T csqrt(T a) {
-        R r = hypot(a.re, a.im);
+        const R s = mid_scale(a.re, a.im);             // sqrt(z) = sqrt(z * s) / sqrt(s), s a power of four
+        const R x = a.re * s, y = a.im * s;
+        const R back = s == R(1) ? R(1) : (s < R(1) ? R(2) : L::up_sqrt_inv);
+        R r = hypot(x, y);
         if (r == R(0)) return T{R(0), a.im};
-        if (a.re >= R(0)) {
-            R t = sqrt((r + a.re) * R(0.5));
-            return T{t, a.im / (t + t)};
+        R t = sqrt((r + fabs(x)) * R(0.5));
+        const R u = (fabs(y) / (t + t)) * back;
+        t *= back;
+        if (x >= R(0)) return T{t, copysign(u, y)};
+        return T{u, copysign(t, y)};
+    }
+    static SMR_DEV T clog(T a) {
+        const R ax = fabs(a.re), ay = fabs(a.im);
+        const R be = fmax(ax, ay), th = fmin(ax, ay);
+        R re;
+        if (be * be > R(0.5) && (be <= R(1.25) || be * be + th * th < R(3))) {
+            // near the unit circle log|z| is small: log1p of |z|^2 - 1, formed without cancellation in its leading part
+            re = log1p((be - R(1)) * (be + R(1)) + th * th) * R(0.5);
+        } else {
+            const R s = mid_scale(a.re, a.im);
+            re = log(hypot(a.re * s, a.im * s));
+            if (s != R(1)) re += (s < R(1) ? R(2) : -L::up_log2) * R(0.69314718055994530942);
         }
-        R t = sqrt((r - a.re) * R(0.5));
-        return T{fabs(a.im) / (t + t), copysign(t, a.im)};
+        return T{re, atan2(a.im, a.re)};
     }
     static SMR_DEV T un(int op, T a) {
         switch (op) {
@@ -409,15 +477,25 @@ struct mathx_cx {
             case SMR_OP_SQRT: return csqrt(a);
             case SMR_OP_EXP: {
                 R e = exp(a.re);
+                if (a.im == R(0)) return T{e, a.im};
                 return T{e * cos(a.im), e * sin(a.im)};
             }
-            case SMR_OP_LOG: return T{log(hypot(a.re, a.im)), atan2(a.im, a.re)};
-            case SMR_OP_SIN: return T{sin(a.re) * cosh(a.im), cos(a.re) * sinh(a.im)};
-            case SMR_OP_COS: return T{cos(a.re) * cosh(a.im), -sin(a.re) * sinh(a.im)};
+            case SMR_OP_LOG: return clog(a);
+            case SMR_OP_SIN:  // re = +-0: sin(iy) = i sinh(y), and 0 * cosh(y) must not meet an infinite cosh
+                if (a.re == R(0)) return T{a.re, sinh(a.im)};
+                return T{sin(a.re) * cosh(a.im), cos(a.re) * sinh(a.im)};
+            case SMR_OP_COS:
+                if (a.re == R(0)) return T{cosh(a.im), __builtin_signbit(a.im) ? a.re : -a.re};
+                return T{cos(a.re) * cosh(a.im), -sin(a.re) * sinh(a.im)};
             case SMR_OP_TANH: {
-                R x2 = a.re + a.re, y2 = a.im + a.im;
-                R den = cosh(x2) + cos(y2);
-                return T{sinh(x2) / den, sin(y2) / den};
+                if (a.im == R(0)) return T{tanh(a.re), a.im};
+                if (fabs(a.re) > L::tanh_one)  // cosh(2x) would overflow long after the quotient has become 1
+                    return T{copysign(R(1), a.re), copysign(R(0), a.im * sin(fabs(a.im) + fabs(a.im)))};
+                // Base's form: with t = tan(y), b = sec(y)^2, s = sinh(x), c = cosh(x): tanh(z) = (b c s + i t) / (1 + b s^2)
+                const R t = tan(a.im), b = R(1) + t * t, s = sinh(a.re), c = sqrt(R(1) + s * s);
+                if (t - t != R(0)) return T{c / s, R(1) / t};  // tan overflowed
+                const R den = R(1) + b * s * s;
+                return T{b * c * s / den, t / den};
             }
             case SMR_OP_INV: return T{R(1), R(0)} / a;
             case SMR_OP_ROUND32: return T{(R)(float)a.re, (R)(float)a.im};
@@ -475,20 +553,29 @@ struct mathx_cx {
     }
     template <int OP>
     static SMR_DEV T ext_un(T a) {
-        if constexpr (OP == SMR_OP_SINH) return T{sinh(a.re) * cos(a.im), cosh(a.re) * sin(a.im)};
-        else if constexpr (OP == SMR_OP_COSH) return T{cosh(a.re) * cos(a.im), sinh(a.re) * sin(a.im)};
+        if constexpr (OP == SMR_OP_SINH) {  // im = +-0: the real function, and an infinite cosh must not meet the zero
+            if (a.im == R(0)) return T{sinh(a.re), a.im};
+            return T{sinh(a.re) * cos(a.im), cosh(a.re) * sin(a.im)};
+        }
+        else if constexpr (OP == SMR_OP_COSH) {
+            if (a.im == R(0)) return T{cosh(a.re), __builtin_signbit(a.re) ? -a.im : a.im};
+            return T{cosh(a.re) * cos(a.im), sinh(a.re) * sin(a.im)};
+        }
         else if constexpr (OP == SMR_OP_EXP2) {
             const R e = exp2(a.re), th = a.im * R(0.69314718055994530942);
+            if (a.im == R(0)) return T{e, a.im};
             return T{e * cos(th), e * sin(th)};
         }
         else if constexpr (OP == SMR_OP_LOG2 || OP == SMR_OP_LOG10) {  // log(z) / log(oftype(real(z), 2 or 10))
             const R d = OP == SMR_OP_LOG2 ? R(0.69314718055994530942) : R(2.30258509299404568402);
-            return T{log(hypot(a.re, a.im)) / d, atan2(a.im, a.re) / d};
+            const T l = clog(a);
+            return T{l.re / d, l.im / d};
         }
         else if constexpr (OP == SMR_OP_SIGN) {
             if (a.re == R(0) && a.im == R(0)) return a;
-            const R r = hypot(a.re, a.im);
-            return T{a.re / r, a.im / r};
+            const R s = mid_scale(a.re, a.im);  // z / |z| of the scaled value: hypot neither overflows nor rounds among the subnormals
+            const R x = a.re * s, y = a.im * s, r = hypot(x, y);
+            return T{x / r, y / r};
         }
         else if constexpr (OP == SMR_OP_ROUND) return T{rint(a.re), rint(a.im)};
         else return T{mathx_real<R>::template ext_un<OP>(a.re), R(0)};
@@ -643,7 +730,12 @@ template <class T> struct FSym {
     static constexpr int NIN = 2;
     T c;
     template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
-    SMR_DEV T operator()(const T* a) const { return mathx<T>::bin(SMR_OP_DIV, a[0] + a[1], c); }
+    SMR_DEV T operator()(const T* a) const {
+        // complex: the plain Smith quotient (no scaling at the ends of the range: the divisor is the call's constant, and the scaled
+        // form costs the pipelined ComplexF64 TILED kernel of this functor 12 bytes of scratch, which a recorded sequence cannot take)
+        if constexpr (tr<T>::cx) return div_smith(a[0] + a[1], c);
+        else return mathx<T>::bin(SMR_OP_DIV, a[0] + a[1], c);
+    }
 };
 template <class T> struct FAxpy {
     static constexpr int NIN = 2;

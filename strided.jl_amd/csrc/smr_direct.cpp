@@ -376,14 +376,22 @@ hsa_status_t scan_code_object(hsa_executable_t, hsa_loaded_code_object_t lco, vo
     if (get(lco, HSA_VEN_AMD_LOADER_LOADED_CODE_OBJECT_INFO_CODE_OBJECT_STORAGE_MEMORY_BASE, &base) != HSA_STATUS_SUCCESS ||
         get(lco, HSA_VEN_AMD_LOADER_LOADED_CODE_OBJECT_INFO_CODE_OBJECT_STORAGE_MEMORY_SIZE, &size) != HSA_STATUS_SUCCESS || !base || !size)
         return HSA_STATUS_SUCCESS;
-    auto it = l->d->code_objects.find(base);
-    if (it == l->d->code_objects.end()) {
+    auto parse = [&] {
         std::map<std::string, KernargLayout> kernels;
         std::string why;
         if (range_mapped((const void*)base, (size_t)size)) (void)kmeta_parse((const void*)base, (size_t)size, kernels, why);
-        it = l->d->code_objects.emplace(base, std::move(kernels)).first;  // (an image that did not parse stays as an empty entry)
-    }
+        return kernels;  // (an image that did not parse gives an empty entry)
+    };
+    auto it = l->d->code_objects.find(base);
+    const bool cached = it != l->d->code_objects.end();
+    if (!cached) it = l->d->code_objects.emplace(base, parse()).first;
     auto k = it->second.find(l->kd);
+    if (k == it->second.end() && cached) {
+        // The entry is keyed by the address of the image.  A runtime-compiled module that the JIT cache unloaded frees its image, and
+        // the next one may be stored where it was: what was parsed then says nothing about the image that is there now.
+        it->second = parse();
+        k = it->second.find(l->kd);
+    }
     if (k == it->second.end()) return HSA_STATUS_SUCCESS;
     l->out.layout = k->second;
     l->out.from_metadata = true;

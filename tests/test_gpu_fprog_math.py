@@ -1,7 +1,9 @@
 """The math opcodes on the MI355X: powers, fma / muladd, more of Base's math, rem / mod and the bitwise operations, in every compute
 class, kernel family and reduction, against NumPy -- bit-exact where the operation is exact (rounding functions, x ^ n for
 n in {0, 1, 2, -1}, rem / mod, fma against the correctly rounded exact result, bit operations), within the suite's tolerance
-(sqrt(eps) relative, an absolute floor near zero) for the transcendentals."""
+(sqrt(eps) relative, an absolute floor near zero) for the transcendentals.  That tolerance pins the plumbing (families, reductions,
+mixed precision, dispatch paths), not the accuracy: each opcode's arithmetic is held to exact values, at the edges of its domain, by
+test_gpu_fprog_conformance.py."""
 from fractions import Fraction
 
 import numpy as np
