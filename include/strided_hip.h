@@ -395,7 +395,18 @@ int smr_plan_prepare(smr_plan* plan);
  * chunk of TK reduced elements and every lane keeps a block of outputs in registers (tiles of 64, 32 or 16 squared).
  * Its accumulation order is defined: one lane per output, from the operator's neutral element, over the outer reduced
  * index and then the inner reduced dim, ascending, the (init-ed) old destination combined last -- for real floats
- * bit-identical to the sequential loop.                                                                              */
+ * bit-identical to the sequential loop.
+ * Option "contract_split" (default 0 = never; negative: SMR_EINVAL) adds the SPLIT FORM, whose plans append
+ * "kparts=<S> cps=<chunks per slice> fold=second-launch scratch=<bytes>": the chunk walk over (outer reduced index, k) is
+ * cut into S contiguous, non-empty slices, one workgroup per (tile, slice) stores its block of accumulators as partials
+ * (plan-owned scratch, allocated by the first execution or smr_plan_prepare), and a second launch folds every output's
+ * partials in slice order and applies initop / the destination's type: dest = op(initop(old), op(...op(P_0, P_1)..., P_{S-1})),
+ * P_s accumulated sequentially from the neutral element over slice s.  Run-to-run identical; for real floats bit-identical
+ * to that loop, NOT to the unsplit one -- hence opt-in.  1 = by the planner's rule (problems whose unsplit plan has fewer
+ * than 256 workgroups and a long reduced range); N >= 2 = N slices (clamped to the chunks) wherever a CONTRACT plan is made.
+ * Option "contract_tile" (default 0 = the planner's rule; 16, 32 or 64; anything else: SMR_EINVAL) forces the tile of
+ * single-call CONTRACT plans, split or not; a forced tile that does not fit "max_lds_bytes" refuses the family for the problem.
+ * Contraction groups read neither option.                                                                             */
 int smr_plan_describe(const smr_plan* plan, char* buf, size_t buflen);
 /* Algorithmic bytes of one execution: every distinct operand footprint counted once
  * (SURVEY.md section 8d).                                                                 */

@@ -286,8 +286,9 @@ static int plan_build(const smr_problem* p, smr_plan** out) {
 // reduction partials are allocated on first execution (planning itself needs no device)
 static int ensure_scratch(smr_plan* h) {
     std::lock_guard<std::mutex> g(*h->plan.build_mu);
-    if (h->plan.scratch || h->plan.red.scratch_bytes == 0) return SMR_OK;
-    const size_t coff = (h->plan.red.scratch_bytes + 255) & ~(size_t)255;
+    const size_t need = h->plan.family == FAM_CONTRACT ? h->plan.contract.scratch_bytes : h->plan.red.scratch_bytes;  // (at most one of the two)
+    if (h->plan.scratch || need == 0) return SMR_OK;
+    const size_t coff = (need + 255) & ~(size_t)255;
     void* buf = nullptr;
     hipError_t e = hipMalloc(&buf, coff + RED_COUNTERS * sizeof(unsigned));
     if (e != hipSuccess) return hip_error(e, "hipMalloc(reduction partials)");
@@ -452,6 +453,8 @@ const OptionField OPTION_FIELDS[] = {
     {"flat_wide", &Options::flat_wide},
     {"flat2", &Options::flat2},
     {"contract", &Options::contract},
+    {"contract_split", &Options::contract_split},
+    {"contract_tile", &Options::contract_tile},
     {"flat2_pair", &Options::flat2_pair},
     {"flat2_bytes", &Options::flat2_bytes},
     {"flat2_lead_bytes", &Options::flat2_lead_bytes},
@@ -919,6 +922,8 @@ int smr_set_option(const char* name, int64_t value) {
         group_contract_tile() = value;
         return SMR_OK;
     }
+    if (n == "contract_split" && value < 0) return set_error(SMR_EINVAL, "contract_split must be 0 (never), 1 (the rule) or the number of slices to force");
+    if (n == "contract_tile" && value != 0 && value != 16 && value != 32 && value != 64) return set_error(SMR_EINVAL, "contract_tile must be 0 (the rule), 16, 32 or 64");
     if (i64 Options::*f = option_field(n)) o.*f = value;
     else if (const int d = tile_lg_dim(n); d >= 0) o.tile_lg[d] = value;
     else return set_error(SMR_EINVAL, "unknown option " + n);

@@ -27,6 +27,16 @@ struct ContractArgs {
     i64 nti, ntj, K, Q, nkc;  // tiles along di / dj, extent of dim NK, outer reduced indices, chunks per q
 };
 
+// The split form (smr_k_contract.hip: k_contract_split / k_contract_fold): the geometry above, and how the chunk walk over (q, k)
+// is cut.  Workgroup b of the main launch is (tile = b % tiles, slice = b / tiles) and walks chunks [slice * cps, min((slice + 1) *
+// cps, Q * nkc)); its register block goes to partials[tile][slice][register r * RB + s][lane 0..255], compute-class values.
+struct ContractSplitArgs {
+    ContractArgs c;
+    void* partials;
+    i64 tiles, cps;
+    int32_t kparts, pad_;
+};
+
 template <class T, int V>
 struct alignas(sizeof(T) * V >= 16 ? 16 : sizeof(T) * V) CVec {
     T v[V];
@@ -157,9 +167,12 @@ SMR_DEV void contract_epilogue(A& a, const OpTab& ops, i64 off0, T acc) {
     store_op<T, MIXED>(ops, off0, red_apply<T>(a.redop, old, acc));
 }
 
-// one workgroup's tile: origin (i0, j0), `boff` the operands' offsets of the workgroup's `rest` index
-template <class T, class F, bool MIXED, int RB, int OPC, bool EDGE, bool VEC, class A>
-SMR_DEV void contract_tile(A& a, const OpTab& ops, const F& f, T* lds, i64 i0, i64 j0, const i64* boff) {
+// one workgroup's tile: origin (i0, j0), `boff` the operands' offsets of the workgroup's `rest` index.  The workgroup walks chunks
+// [t_lo, t_hi) of the Q * nkc chunks of the reduced space (chunk t: outer reduced index q = t / nkc, rows [kc * TK, min((kc + 1) * TK,
+// K)) with kc = t % nkc); the whole range in the unsplit kernels.  SPLIT (compile time): the register block is not put through the
+// epilogue but stored, as it is, to `sink` -- [register r * RB + s][lane] -- by every lane, those past a ragged tile's end included.
+template <class T, class F, bool MIXED, int RB, int OPC, bool EDGE, bool VEC, bool SPLIT, class A>
+SMR_DEV void contract_tile(A& a, const OpTab& ops, const F& f, T* lds, i64 i0, i64 j0, const i64* boff, i64 t_lo, i64 t_hi, T* sink) {
     typedef CGeom<T, RB> G;
     const int redop = (OPC >= 0) ? OPC : a.redop;  // compile-time for the sum: no op switch inside the loops
     const int li = (int)threadIdx.x & (CONTRACT_LANES - 1), lj = (int)threadIdx.x >> 4;
@@ -169,20 +182,29 @@ SMR_DEV void contract_tile(A& a, const OpTab& ops, const F& f, T* lds, i64 i0, i
     for (int r = 0; r < RB; ++r)
 #pragma unroll
         for (int s = 0; s < RB; ++s) acc[r][s] = neutral<T>(redop);
-    const i64 nchunks = a.Q * a.nkc;
+    // (the unsplit copies are handed 0 and Q * nkc, and take them from here: they compile to what they did before the split form)
+    if constexpr (!SPLIT) {
+        t_lo = 0;
+        t_hi = a.Q * a.nkc;
+    }
     i64 qo[3] = {0, 0, 0};
     i64 q = 0, kc = 0;  // the chunk being fetched
+    if (t_lo != 0) {
+        q = t_lo / a.nkc;
+        kc = t_lo - q * a.nkc;
+        contract_qoff(a, q, qo);
+    }
     T ra[G::NR], rb[G::NR];
-    contract_fetch<T, MIXED, RB, EDGE, VEC>(a, ops, 1, a.di, ra, boff[1], i0, 0);
-    contract_fetch<T, MIXED, RB, EDGE, VEC>(a, ops, 2, a.dj, rb, boff[2], j0, 0);
+    contract_fetch<T, MIXED, RB, EDGE, VEC>(a, ops, 1, a.di, ra, boff[1] + qo[1], i0, kc * G::TK);
+    contract_fetch<T, MIXED, RB, EDGE, VEC>(a, ops, 2, a.dj, rb, boff[2] + qo[2], j0, kc * G::TK);
     contract_stash<T, RB, VEC>(a, 1, ra, lds);
     contract_stash<T, RB, VEC>(a, 2, rb, lds + TSZ);
     __syncthreads();
-    for (i64 t = 0; t < nchunks; ++t) {
-        const int cur = (int)(t & 1);
+    for (i64 t = t_lo; t < t_hi; ++t) {
+        const int cur = (int)((t - t_lo) & 1);
         const i64 kbeg = kc * G::TK;
         const int kn = (int)((a.K - kbeg < G::TK) ? a.K - kbeg : G::TK);  // rows of the chunk being consumed
-        const bool more = t + 1 < nchunks;
+        const bool more = t + 1 < t_hi;
         if (more) {
             if (++kc == a.nkc) {
                 kc = 0;
@@ -239,20 +261,28 @@ SMR_DEV void contract_tile(A& a, const OpTab& ops, const F& f, T* lds, i64 i0, i
         }
         __syncthreads();
     }
-    const i64 s0i = a.strides[0][a.di], s0j = a.strides[0][a.dj];
+    if constexpr (SPLIT) {
+        // every store instruction of a wave writes 64 consecutive values
 #pragma unroll
-    for (int s = 0; s < RB; ++s)
+        for (int r = 0; r < RB; ++r)
 #pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const i64 i = i0 + G::idx(li, r), j = j0 + G::idx(lj, s);
-            if (!EDGE || (i < a.dims[a.di] && j < a.dims[a.dj])) contract_epilogue<T, MIXED>(a, ops, boff[0] + i * s0i + j * s0j, acc[r][s]);
-        }
+            for (int s = 0; s < RB; ++s) sink[(r * RB + s) * 256 + (int)threadIdx.x] = acc[r][s];
+    } else {
+        const i64 s0i = a.strides[0][a.di], s0j = a.strides[0][a.dj];
+#pragma unroll
+        for (int s = 0; s < RB; ++s)
+#pragma unroll
+            for (int r = 0; r < RB; ++r) {
+                const i64 i = i0 + G::idx(li, r), j = j0 + G::idx(lj, s);
+                if (!EDGE || (i < a.dims[a.di] && j < a.dims[a.dj])) contract_epilogue<T, MIXED>(a, ops, boff[0] + i * s0i + j * s0j, acc[r][s]);
+            }
+    }
 }
 
 // workgroup `b` of the problem `a`: tile along di (fastest), tile along dj, the other kept dims.  (A single call passes blockIdx.x,
 // a group the workgroup's index inside its member.)
-template <class T, class F, bool MIXED, int RB, int OPC, class A>
-SMR_DEV void contract_impl(A& a, const OpTab& ops, const F& f, T* lds, i64 b) {
+template <class T, class F, bool MIXED, int RB, int OPC, bool SPLIT, class A>
+SMR_DEV void contract_impl(A& a, const OpTab& ops, const F& f, T* lds, i64 b, i64 t_lo, i64 t_hi, T* sink) {
     typedef CGeom<T, RB> G;
     const i64 bi = b % a.nti;
     b /= a.nti;
@@ -270,27 +300,27 @@ SMR_DEV void contract_impl(A& a, const OpTab& ops, const F& f, T* lds, i64 b) {
     const i64 i0 = bi * G::TILE, j0 = bj * G::TILE;
     const bool whole = i0 + G::TILE <= a.dims[a.di] && j0 + G::TILE <= a.dims[a.dj];
     if (!whole) {
-        contract_tile<T, F, MIXED, RB, OPC, true, false>(a, ops, f, lds, i0, j0, boff);
+        contract_tile<T, F, MIXED, RB, OPC, true, false, SPLIT>(a, ops, f, lds, i0, j0, boff, t_lo, t_hi, sink);
         return;
     }
     if constexpr (!MIXED && G::VE > 1) {
         if (a.vec > 1) {
-            contract_tile<T, F, MIXED, RB, OPC, false, true>(a, ops, f, lds, i0, j0, boff);
+            contract_tile<T, F, MIXED, RB, OPC, false, true, SPLIT>(a, ops, f, lds, i0, j0, boff, t_lo, t_hi, sink);
             return;
         }
     }
-    contract_tile<T, F, MIXED, RB, OPC, false, false>(a, ops, f, lds, i0, j0, boff);
+    contract_tile<T, F, MIXED, RB, OPC, false, false, SPLIT>(a, ops, f, lds, i0, j0, boff, t_lo, t_hi, sink);
 }
 
 // the sum gets a copy of the body with the operator fixed.  (Copies for min and max as well were measured and lost: registers are
 // allocated for the whole kernel, and the NaN-aware min / max blocks pushed every path, the sum included, into scratch memory:
 // 1024^3 Float32 87 -> 165 us.)
-template <class T, class F, bool MIXED, int RB, class A>
-SMR_DEV void contract_by_op(A& a, const OpTab& ops, int redop, const F& f, T* lds, i64 b) {
+template <class T, class F, bool MIXED, int RB, bool SPLIT, class A>
+SMR_DEV void contract_by_op(A& a, const OpTab& ops, int redop, const F& f, T* lds, i64 b, i64 t_lo, i64 t_hi, T* sink) {
     if (redop == SMR_RED_ADD)
-        contract_impl<T, F, MIXED, RB, SMR_RED_ADD>(a, ops, f, lds, b);
+        contract_impl<T, F, MIXED, RB, SMR_RED_ADD, SPLIT>(a, ops, f, lds, b, t_lo, t_hi, sink);
     else
-        contract_impl<T, F, MIXED, RB, -1>(a, ops, f, lds, b);
+        contract_impl<T, F, MIXED, RB, -1, SPLIT>(a, ops, f, lds, b, t_lo, t_hi, sink);
 }
 
 #ifndef SMR_JIT

@@ -127,6 +127,7 @@ template <int CT> int launch_reduce_part_ct(const Plan&, void* const*, hipStream
 template <int CT> int launch_orbit_map_ct(const Plan&, void* const*, hipStream_t);
 template <int CT> int launch_flat_map_ct(const Plan&, void* const*, hipStream_t);
 template <int CT> int launch_contract_ct(const Plan&, void* const*, hipStream_t);
+template <int CT> int launch_contract_split_ct(const Plan&, void* const*, hipStream_t);  // smr_k_contract.hip compiled with -DSMR_CONTRACT_SPLIT
 
 // Fills the kernel operand table: base pointers with the element offset folded in.
 inline OpTab make_optab(const Canon& c, void* const* bases) {

@@ -273,6 +273,12 @@ struct ContractPlan {
     i64 nti = 1, ntj = 1, nrest = 1;  // tiles along di, along dj, product of the other kept extents
     i64 grid = 1;
     size_t lds_bytes = 0;
+    // Split form (option "contract_split"): the chunk walk over (q, k) cut into kparts contiguous slices of cps chunks (the last may be
+    // shorter, none is empty); grid * kparts workgroups store their register blocks as partials, a second launch folds them in slice
+    // order: dest = op(initop(old), op(... op(P_0, P_1) ..., P_{kparts-1})).  kparts = 1: the unsplit plan above.
+    int kparts = 1;
+    i64 cps = 0;               // chunks per slice (0 when unsplit)
+    size_t scratch_bytes = 0;  // grid * kparts * (16 * rb)^2 * sizeof(compute type): the partials (Plan::scratch)
 };
 // the vector width (elements per 16-byte global load of whole tiles) one execution uses for the given operand bases (nullptr: the
 // bases the plan was made with): smr_plan_contract.cpp, read by the launcher and by describe()
@@ -295,7 +301,8 @@ struct Plan {
     ReducePlan red;
     ContractPlan contract;
     mutable bool eager_seen = false;  // the plan's device tables (uploaded by hipMemcpy on its first execution) have been made visible to the direct queues
-    void* scratch = nullptr;  // reductions: partials (owned, ReducePlan::scratch_bytes), followed by RED_COUNTERS arrival counters (zero between launches)
+    void* scratch = nullptr;  // reductions and split contractions: partials (owned, ReducePlan::scratch_bytes or ContractPlan::scratch_bytes -- a plan
+                              // has at most one of the two), followed by RED_COUNTERS arrival counters (zero between launches)
     size_t counter_off = 0;   // byte offset of the counters inside `scratch` (set when it is allocated)
     // TILED / ORBIT: a kernel form's arguments, built by the family's argument builder (smr_k_tiled.hip: build_tiled_args,
     // smr_k_orbit.hip: build_orbit_args / build_pair_args) on the plan's first execution of that form, together with the device
@@ -399,6 +406,9 @@ struct Options {
     i64 max_lds_bytes = 65536;
     i64 contract = 1;        // FAM_CONTRACT for outer-product reductions (the generic __mul! shape): 0 never, 1 when the shape qualifies and the problem is
                              // large enough (smr_plan_contract.cpp: contract_gate), 2 wherever the shape qualifies (tests, experiments)
+    i64 contract_split = 0;  // FAM_CONTRACT, split of the reduced range over workgroups (partials + a folding launch; another accumulation order, hence opt-in):
+                             // 0 never, 1 by the rule (smr_plan_contract.cpp: contract_split_rule), N >= 2 force N slices wherever a CONTRACT plan is made
+    i64 contract_tile = 0;   // FAM_CONTRACT, single calls: 0 = plan_contract's rule, 16 / 32 / 64 force the tile (refused when it does not fit max_lds_bytes)
     i64 tile_lg[MAXN] = {-1, -1, -1, -1, -1, -1, -1, -1};  // per canonical dim log2 tile extent override
 };
 Options& options();

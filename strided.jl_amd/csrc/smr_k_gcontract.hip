@@ -59,7 +59,7 @@ SMR_DEV void group_contract_body(const GroupContractArgs a, F f) {
         t.dtype[k] = a.dtype[k];
         t.conj[k] = a.conj[k];
     }
-    contract_by_op<T, F, MIXED, RB>(m, t, a.redop, f, lds, (i64)(b - first_wg[lo]));
+    contract_by_op<T, F, MIXED, RB, false>(m, t, a.redop, f, lds, (i64)(b - first_wg[lo]), 0, m.Q * m.nkc, (T*)nullptr);
 }
 
 #ifndef SMR_JIT

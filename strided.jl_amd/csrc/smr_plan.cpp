@@ -240,6 +240,8 @@ void describe(Plan& plan) {
     if (plan.family == FAM_CONTRACT) {  // vec: as launched with the bases the plan was made with
         const ContractPlan& cp = plan.contract;
         appendf(s, " tile=d%d:%dxd%d:%d k=%d grid=%lld lds=%zu vec=%d", cp.di, cp.ti, cp.dj, cp.tj, cp.tk, (long long)cp.grid, cp.lds_bytes, contract_vec(plan, nullptr));
+        // the split form ("split=" is REDUCE_PART's token: tests tell the families apart by it)
+        if (cp.kparts > 1) appendf(s, " kparts=%d cps=%lld fold=second-launch scratch=%zu", cp.kparts, (long long)cp.cps, cp.scratch_bytes);
     }
     if (plan.family == FAM_REDUCE_ALL || plan.family == FAM_REDUCE_PART) {
         // as launched with the bases the plan was made with (the partials buffer is allocated on the first execution)

@@ -42,7 +42,104 @@ static bool contract_gate(const Canon& c, const ContractPlan& cp) {
     if (!options().jit && (c.mixed || c.fkind != FK_MUL2)) return false;
     if (c.dims[cp.di] < 32 || c.dims[cp.dj] < 32) return false;
     if (c.dims[c.NK] < 16) return false;
-    if (cp.grid < 256) return false;
+    // a split plan (option "contract_split") runs grid * kparts workgroups: those keep the device busy
+    if (cp.grid * cp.kparts < 256) return false;
+    return true;
+}
+
+// Sets the tile-dependent fields of `cp` for register block rb; unsplit.
+static void contract_set_plan_tile(const Canon& c, ContractPlan& cp, int rb, i64 rest) {
+    const int es = dtype_size(c.ct);
+    cp.rb = rb;
+    cp.ti = cp.tj = CONTRACT_LANES * rb;
+    cp.tk = contract_tk(es, rb);
+    cp.nti = (c.dims[cp.di] + cp.ti - 1) / cp.ti;
+    cp.ntj = (c.dims[cp.dj] + cp.tj - 1) / cp.tj;
+    cp.nrest = rest;
+    cp.grid = cp.nti * cp.ntj * rest;
+    cp.lds_bytes = contract_lds(es, rb);
+    cp.kparts = 1;
+    cp.cps = 0;
+    cp.scratch_bytes = 0;
+}
+
+// chunks of the walk over (q, k) with the plan's tile
+static i64 contract_nchunks(const Canon& c, const ContractPlan& cp) {
+    const i64 K = c.dims[c.NK], Q = c.total / c.nout / K;
+    return Q * ((K + cp.tk - 1) / cp.tk);
+}
+
+// Cuts the chunk walk of `cp` (its tile set) into at most `want` slices: clamped to the chunks, then cps = ceil(nchunks / S) and
+// S = ceil(nchunks / cps), so no slice is empty.  One slice, partials beyond 2^31 bytes or a grid beyond 2^31 - 1: left unsplit.
+static void contract_cut(const Canon& c, ContractPlan& cp, i64 want) {
+    const i64 nchunks = contract_nchunks(c, cp);
+    i64 S = std::min(want, nchunks);
+    if (S < 2) return;
+    const i64 cps = (nchunks + S - 1) / S;
+    S = (nchunks + cps - 1) / cps;
+    if (S < 2) return;
+    const long double bytes = (long double)cp.grid * (long double)S * (long double)(cp.ti * cp.tj) * (long double)dtype_size(c.ct);
+    if (bytes > 2147483648.0L || (long double)cp.grid * (long double)S > 2147483647.0L) return;
+    cp.kparts = (int)S;
+    cp.cps = cps;
+    cp.scratch_bytes = (size_t)bytes;
+}
+
+// contract_split = 1: the tile and the number of slices of a problem whose unsplit plan has fewer than 256 workgroups.  Of the tiles
+// allowed (`rbs`, largest first) the largest whose tiles * S can reach the family's workgroup thresholds (512 for 64 x 64, else 256, as
+// plan_contract) with S inside the three bounds below; S is then what brings the launch to 512 workgroups, or the bound.  Where no
+// tile reaches its threshold, the tile whose bounds allow the most workgroups, if that is at least two slices; else the problem is not
+// split (false).  Measured with tools/contract_split_cases.py (profiles/contract_split.txt, MI355X; us per launch, the rows as that
+// file has them -- "c" is the rule's own plan; the first rule started from slices of 4 chunks, a quarter of the input bytes and the
+// thresholds alone):
+//   slices of at least 2 chunks (the prologue of the double buffer is one exposed fetch and barrier per slice): (64, 64, 4096)
+//     Float32 on 16 x 16 tiles: 4 chunks per slice (S16) 11.9, 2 chunks (c) 11.8, 1 chunk (S64) 13.8; (256, 256, 4096) Float32 forced
+//     onto 32 x 32 tiles: 4 chunks (S16) 29.5, 2 chunks (S32) 30.6, 1 chunk (S64) 35.3;
+//   S <= 64: the largest value measured, and the best one wherever it is what brings a row to its workgroups ((32, 32, 1048576)
+//     Float32: 64 slices (c) 315.7 against 32 slices 614.3); beyond 64: not measured;
+//   the partials' round trip, 2 * scratch_bytes, at most HALF the bytes the inputs move, (dims[di] + dims[dj]) * K * Q * es: at one half
+//     the split still gains ((128, 128, 16384) Float64, 32 x 32 tiles: 64 slices 41.6 against 32 slices (c) 47.3; (64, 64, 4096)
+//     Float32, 16 x 16: 32 slices (c) 11.8 against 16 slices 11.9), at the whole of it no longer ((64, 64, 4096) ComplexF64, 16 x 16:
+//     64 slices 19.0 against 32 slices (c) 18.6);
+//   512 workgroups: past a tile's threshold more slices keep gaining up to about two workgroups per CU -- (64, 64, 4096) on 16 x 16
+//     tiles, 256 / 512 / 1024 workgroups (S16 / c / S64): Float32 11.9 / 11.8 / 13.8, Float64 14.9 / 14.1 / 16.2, ComplexF64 24.8 /
+//     18.6 / 19.0; (128, 128, 16384) Float32 on 32 x 32 tiles 36.4 / 32.1 / 34.1 (Float64 and ComplexF64 gain another 12 % at 1024:
+//     47.3 -> 41.6, 108.7 -> 96.1 -- left alone: one target for every type);
+//   the larger tile first: (64, 64, 65536) Float32 32 x 32 with 256 workgroups (c) 41.1 against 16 x 16 with 1024 workgroups 55.6
+//     (Float64 80.3 against 87.8; ComplexF64 the other way round, 162.6 against 133.1: the choice is not type-dependent here).
+static bool contract_split_rule(const Canon& c, ContractPlan& cp, const int* rbs, int nrb, i64 rest) {
+    constexpr i64 MIN_CPS = 2, MAX_S = 64, TARGET = 512;
+    const int es = dtype_size(c.ct);
+    const i64 K = c.dims[c.NK], Q = c.total / c.nout / K;
+    const long double in_bytes = (long double)(c.dims[cp.di] + c.dims[cp.dj]) * (long double)K * (long double)Q * es;
+    int best_rb = 0;
+    i64 best_s = 0, best_wgs = 0;
+    for (int n = 0; n < nrb; ++n) {
+        ContractPlan t = cp;
+        contract_set_plan_tile(c, t, rbs[n], rest);
+        const i64 nchunks = contract_nchunks(c, t);
+        const long double per_slice = 2.0L * (long double)t.grid * (long double)(t.ti * t.tj) * es;  // round trip of one slice's partials
+        i64 smax = std::min<i64>(MAX_S, nchunks / MIN_CPS);
+        smax = std::min<i64>(smax, (i64)(in_bytes / 2 / per_slice));
+        if (smax < 2) continue;
+        const i64 thr = rbs[n] == 4 ? 512 : 256;
+        if (t.grid * smax >= thr) {
+            best_rb = rbs[n];
+            best_s = std::max<i64>(2, std::min<i64>(smax, (TARGET + t.grid - 1) / t.grid));
+            break;
+        }
+        if (t.grid * smax > best_wgs) {
+            best_wgs = t.grid * smax;
+            best_rb = rbs[n];
+            best_s = smax;
+        }
+    }
+    if (!best_rb) return false;
+    ContractPlan t = cp;
+    contract_set_plan_tile(c, t, best_rb, rest);
+    contract_cut(c, t, best_s);
+    if (t.kparts < 2) return false;
+    cp = t;
     return true;
 }
 
@@ -77,21 +174,28 @@ bool plan_contract(const Canon& c, ContractPlan& cp) {
         const i64 t = CONTRACT_LANES * rb;
         return ((c.dims[cp.di] + t - 1) / t) * ((c.dims[cp.dj] + t - 1) / t) * rest;
     };
-    const int want = tiles(4) >= 512 ? 4 : (tiles(2) >= 256 ? 2 : 1);
-    // the LDS is static: a budget below the tile's takes the next smaller tile that fits, or refuses the family
+    const int want = o.contract_tile ? (int)(o.contract_tile / CONTRACT_LANES) : (tiles(4) >= 512 ? 4 : (tiles(2) >= 256 ? 2 : 1));
+    // the LDS is static: a budget below the tile's takes the next smaller tile that fits, or refuses the family (a tile forced by
+    // "contract_tile" is not exchanged for a smaller one: it fits or the family is refused)
     const i64 cap = std::min<i64>(o.max_lds_bytes, 65536);
-    cp.rb = 0;
-    for (int rb = want; rb >= 1 && !cp.rb; rb >>= 1)
-        if ((i64)contract_lds(es, rb) <= cap) cp.rb = rb;
-    if (!cp.rb) return false;
-    cp.ti = cp.tj = CONTRACT_LANES * cp.rb;
-    cp.tk = contract_tk(es, cp.rb);
-    cp.nti = (c.dims[cp.di] + cp.ti - 1) / cp.ti;
-    cp.ntj = (c.dims[cp.dj] + cp.tj - 1) / cp.tj;
-    cp.nrest = rest;
-    cp.grid = tiles(cp.rb);
-    cp.lds_bytes = contract_lds(es, cp.rb);
+    int rb0 = 0;
+    for (int rb = want; rb >= 1 && !rb0; rb >>= 1) {
+        if ((i64)contract_lds(es, rb) <= cap) rb0 = rb;
+        if (o.contract_tile) break;
+    }
+    if (!rb0) return false;
+    contract_set_plan_tile(c, cp, rb0, rest);
     if (cp.grid > 0x7fffffffLL) return false;
+    // the split form (opt-in: another accumulation order): forced slices on the tile chosen above, or the rule, which only looks at
+    // launches with fewer workgroups than CUs and picks tile and slices together (a forced tile stays)
+    if (o.contract_split >= 2) {
+        contract_cut(c, cp, o.contract_split);
+    } else if (o.contract_split == 1 && cp.grid < 256) {
+        int rbs[3], nrb = 0;
+        for (int rb = 4; rb >= 1; rb >>= 1)
+            if (o.contract_tile ? rb == rb0 : (i64)contract_lds(es, rb) <= cap) rbs[nrb++] = rb;
+        contract_split_rule(c, cp, rbs, nrb, rest);
+    }
     return o.contract >= 2 || contract_gate(c, cp);
 }
 

@@ -9,6 +9,13 @@ as the LDS- and register-tiled CONTRACT kernel family (csrc/smr_k_contract.hip) 
 large enough -- `S.set_option("contract", 0 | 1 | 2)`: never / by size (default) / wherever the
 shape qualifies.  Each output is accumulated by one lane over k ascending: for real floats the
 result is bit-identical to the sequential loop.
+`S.set_option("contract_split", 0 | 1 | N)` (default 0: never) lets the family cut a long reduced
+range into slices, one workgroup per (output tile, slice), folded by a second launch in slice
+order: 1 = by the planner's rule (few output tiles, long k: `mul_` at (64, 64, 4096) and the like),
+N >= 2 = N slices wherever the family plans (tests, measurements).  The order is defined --
+dest = op(initop(old), ((P_0 op P_1) op P_2) ...), P_s the sequential accumulation over slice s --
+and run-to-run identical, but it is not the unsplit loop's: hence opt-in.
+`S.set_option("contract_tile", 0 | 16 | 32 | 64)` forces the tile of single calls (0: the rule).
 Many small products (the blocks of a block-sparse contraction) share ONE launch inside
 `with S.group(contract=True):` -- calls of `mul_` on matrices with the same alpha and the same kind of
 beta (0, 1, or anything else; the value is per call) are deferred and run as a contraction group

@@ -12,6 +12,9 @@
 // W, varc, rb, rank, jit, algbytes and the rd / wr footprint -- or, for a group the planner refuses, its status and message.  The
 // corpus restates the recipes and the refusals of tests/group_cases.py, group_scalar_cases.py, group_contract_cases.py and the group
 // host tests over fake addresses.  (smr_group_create's own argument checks -- null, count, unknown flag -- are not the planner's.)
+// Before the groups, a section "split <id> ..." plans the generic product box with "contract_split" / "contract_tile" set: both outcomes
+// of the rule, every tile, forced slices, slices clamped to the chunks, a forced tile refused (`sneed`).  The sections before it plan
+// with both options at their defaults.
 // It exits with status 1 when too few problems reach one of the work-list builders or input variants (`need`), when a group kind, body,
 // tile, scalar form or refusal is not reached (`gneed`), or when a group is refused or accepted against its recipe: a comparison of
 // nothing passes.
@@ -86,6 +89,7 @@ static uint64_t digest(const Plan& plan) {
         const ContractPlan& k = plan.contract;
         f.v(k.di); f.v(k.dj); f.v(k.rb); f.v(k.ti); f.v(k.tj); f.v(k.tk); f.v(k.nti); f.v(k.ntj); f.v(k.nrest); f.v(k.grid); f.v(k.lds_bytes);
         f.v(contract_vec(plan, nullptr));
+        if (k.kparts > 1) { f.v(k.kparts); f.v(k.cps); f.v(k.scratch_bytes); }  // (an unsplit plan's digest is the one from before the split form)
     }
     return f.h;
 }
@@ -524,6 +528,76 @@ static void group_corpus() {
     }
 }
 
+// ---- the split form of CONTRACT ("contract_split", "contract_tile") -------------------------------------------------------------------
+// The generic product box (m, n, k[, k2]) planned with the two options set: "split <id> contract=<c> split=<s> tile=<t>".  Both outcomes
+// of the rule (split; left alone: one chunk, enough workgroups already, the partials too large for the inputs), every tile by the rule
+// and forced, forced slices, slices clamped to the chunks, a forced tile beyond the LDS budget (refused: REDUCE_PART).
+enum { S_RULE_SPLIT, S_RULE_LEFT, S_TILE16, S_TILE32, S_TILE64, S_FORCED, S_CLAMPED, S_REFUSED, S_TWO_REDUCED, S_COUNT };
+static const char* sname[] = {"split_by_rule", "rule_leaves_alone", "split_tile_16", "split_tile_32", "split_tile_64", "split_forced", "split_clamped", "split_tile_refused", "split_two_reduced_dims"};
+static const long sneed[S_COUNT] = {6, 6, 6, 6, 6, 12, 6, 3, 12};
+static long scounts[S_COUNT];
+
+static smr_problem mul_box(const std::vector<i64>& dims, int dt) {
+    // C (m, n), A (m, k[, k2]) column-major, B (n, k[, k2]) with k fastest; with two reduced dims the parents are padded by one
+    // along k, so that the two do not fuse into one (Q > 1: slices that start inside and between outer reduced indices)
+    const int N = (int)dims.size();
+    smr_problem p = problem(dims, dt, {rotation(N, 0), rotation(N, 0)}, DISTINCT, 3u, true);
+    i64 sa = dims[0], sb = 1;
+    for (int d = 0; d < N; ++d) p.ops[1].strides[d] = p.ops[2].strides[d] = 0;
+    p.ops[1].strides[0] = 1;
+    for (int d = 2; d < N; ++d) {
+        p.ops[1].strides[d] = sa;
+        sa *= dims[d] + (N > 3 && d == 2 ? 1 : 0);
+        p.ops[2].strides[d] = sb;
+        sb *= dims[d] + (N > 3 && d == 2 ? 1 : 0);
+    }
+    p.ops[2].strides[1] = sb;
+    static const uint8_t mul[] = {SMR_OP_ARG, 1, SMR_OP_ARG, 2, SMR_OP_MUL, 0};
+    p.fprog = mul;
+    p.fprog_len = 3;
+    return p;
+}
+
+static void split_line(const std::string& id, const smr_problem& p, i64 contract, i64 split, i64 tile, i64 lds = 65536) {
+    const Options saved = options();
+    options().contract = contract;
+    options().contract_split = split;
+    options().contract_tile = tile;
+    options().max_lds_bytes = lds;
+    Plan plan;
+    const int rc = make_plan(&p, plan);
+    options() = saved;
+    if (rc) {
+        std::printf("split %s contract=%lld split=%lld tile=%lld rc=%d\n", id.c_str(), (long long)contract, (long long)split, (long long)tile, rc);
+        return;
+    }
+    std::printf("split %s contract=%lld split=%lld tile=%lld | %s | %016llx\n", id.c_str(), (long long)contract, (long long)split, (long long)tile, plan.desc.c_str(),
+                (unsigned long long)digest(plan));
+    const ContractPlan& k = plan.contract;
+    const bool is_split = plan.family == FAM_CONTRACT && k.kparts > 1;
+    if (split == 1) ++scounts[is_split ? S_RULE_SPLIT : S_RULE_LEFT];
+    if (is_split) ++scounts[k.rb == 1 ? S_TILE16 : (k.rb == 2 ? S_TILE32 : S_TILE64)];
+    if (split >= 2 && is_split) ++scounts[k.kparts == split ? S_FORCED : S_CLAMPED];
+    if (tile && lds < 65536 && plan.family != FAM_CONTRACT) ++scounts[S_REFUSED];
+    if (is_split && plan.c.N - plan.c.NK > 1) ++scounts[S_TWO_REDUCED];  // (the reduced dims did not fuse: Q > 1)
+}
+
+static void split_corpus() {
+    const std::vector<std::vector<i64>> boxes = {{64, 64, 4096},   {64, 64, 65536}, {32, 32, 1048576}, {128, 128, 16384}, {256, 256, 4096}, {16, 512, 32768},
+                                                 {100, 90, 80},    {1024, 1024, 1024}, {64, 64, 512, 64}, {40, 40, 40},   {128, 128, 64},   {512, 512, 512},
+                                                 {256, 256, 256},  {65, 63, 193},   {33, 33, 97, 3},   {2048, 2048, 64}};
+    for (const auto& dims : boxes)
+        for (int dt : {SMR_F32, SMR_F64, SMR_C64}) {
+            const smr_problem p = mul_box(dims, dt);
+            const std::string id = ident(dims, dt, {}, "product");
+            for (i64 contract : {1, 2}) split_line(id, p, contract, 1, 0);           // the rule
+            for (i64 tile : {16, 32, 64}) split_line(id, p, 2, 1, tile);              // the rule on a forced tile
+            for (i64 s : {2, 3, 8, 64, 100000})                                       // forced slices (clamped to the chunks, or refused: too large)
+                for (i64 tile : {0, 16, 32, 64}) split_line(id, p, 2, s, tile);
+            split_line(id, p, 2, 4, 64, 8192);                                        // the forced tile does not fit: REDUCE_PART
+        }
+}
+
 int main() {
     const int dtypes[] = {SMR_F32, SMR_F64, SMR_C64};
     const i64 ext[] = {3, 7, 8, 24, 32, 40, 48, 64, 100};
@@ -613,6 +687,7 @@ int main() {
             (void)n;
             plan_all(ident(mnk, dt, {}, "contraction"), p, DISTINCT);
         }
+    split_corpus();
     group_corpus();
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     std::fprintf(stderr, "%ld lines:", lines);
@@ -627,6 +702,10 @@ int main() {
     for (int v = ONE; v <= STEPPED; ++v) report(var_name[v], var_lines[v]);
     std::fprintf(stderr, "%ld group lines, %ld accepted or refused against the recipe's word\n", glines, gwrong);
     if (gwrong) rc = 1;
+    for (int i = 0; i < S_COUNT; ++i) {
+        std::fprintf(stderr, "  %s: %ld%s\n", sname[i], scounts[i], scounts[i] < sneed[i] ? "  -- TOO FEW: the split corpus no longer covers this" : "");
+        if (scounts[i] < sneed[i]) rc = 1;
+    }
     for (int i = 0; i < G_COUNT; ++i) {
         std::fprintf(stderr, "  %s: %ld%s\n", gname[i], gcounts[i], gcounts[i] < gneed[i] ? "  -- TOO FEW: the group corpus no longer covers this" : "");
         if (gcounts[i] < gneed[i]) rc = 1;
