@@ -13,6 +13,8 @@
 
 #include "smr_dispatch.h"
 #include "smr_group.h"
+#include "smr_orbit_args.h"
+#include "smr_tiled_args.h"
 
 namespace smr {
 
@@ -48,6 +50,108 @@ int cu_count() {
         return n;
     }();
     return ncu;
+}
+
+// ---- TILED / ORBIT: the arguments of one execution ---------------------------------------------------
+// The pure builders (smr_plan_tiled_args.cpp, smr_plan_orbit_args.cpp) compute a form's arguments and tables from the plan; what is
+// left lives here, next to upload_table: the plan's cache of built forms, the uploads, and the fields that change from call to call.
+template <class A>
+static bool cached_form(const Plan::FormCache& cached, A& a) {
+    if (cached.args.size() != sizeof a) return false;
+    std::memcpy(&a, cached.args.data(), sizeof a);
+    return true;
+}
+template <class A>
+static void cache_form(Plan::FormCache& cached, const A& a) {
+    cached.args.resize(sizeof a);
+    std::memcpy(cached.args.data(), &a, sizeof a);
+}
+template <class T>
+static int upload_once(void** dst, const std::vector<T>& rows, const char* what) {
+    return *dst ? SMR_OK : upload_table(dst, rows.data(), rows.size() * sizeof(T), what);
+}
+
+template <bool WIDE>
+int tiled_launch_args(const Plan& plan, void* const* base, int esize, const TiledVariant& tv, bool wt_store, TiledLaunch<WIDE>& L) {
+    const Canon& c = plan.c;
+    const TilePlan& t = plan.tile;
+    const Options& o = options();
+    TiledArgs<WIDE>& a = L.a;
+    L.lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * esize;
+    L.grid = t.ord.empty() ? (unsigned)t.grid : (unsigned)t.ord.size();
+    L.pgrid = tv.pgrid;  // the persistent, software-pipelined form (tiled_variant)
+    Plan::FormCache& cached = plan.tiled_cache[(WIDE ? 2 : 0) + (tv.V > 1 ? 1 : 0)];
+    if (!cached_form(cached, a)) {
+        TiledBuild<WIDE> b;
+        if (int rc = build_tiled_args<WIDE>(plan, esize, tv, b)) return rc;
+        a = b.a;
+        if (!jit_dry_run()) {
+            if (a.ordmode == 2)
+                if (int rc = upload_once(&plan.tiled_order, t.ord, "tile order")) return rc;
+            if (int rc = upload_once(&cached.tab, b.rows, "lane table")) return rc;
+            a.ordtab = reinterpret_cast<const uint32_t*>(plan.tiled_order);
+            a.lanetab = reinterpret_cast<const LaneRow<WIDE>*>(cached.tab);
+            cache_form(cached, a);
+        }
+    }
+    for (int k = 0; k < c.M; ++k) a.op[k].base = base[k];
+    // non-temporal stores: measured faster or equal whenever a tile writes whole 128-byte lines (32^4 Float64
+    // permutedims! 3.36 -> 2.76 us, 128^4 864 -> 818 us, never slower for a consumer kernel that follows);
+    // partial lines must meet in L2 first, so short destination runs keep plain stores
+    a.nts = (o.nt_store > 0) ? 1 : 0;
+    if (o.nt_store < 0) {
+        const i64 run = std::min<i64>(c.dims[0], (i64)1 << t.tlog[0]) * c.esize[0];
+        a.nts = (c.strides[0][0] == 1 && run >= 128) ? 1 : 0;
+    }
+    // write-through stores (policy 2): forced, or a launch recorded for a sequence (its packet then needs no release fence).  Only the
+    // one-shot vector form: there every store of the kernel is one of the vector stores below.
+    if (wt_store && L.pgrid == 0 && (o.nt_store == 2 || want_self_release(plan))) a.nts = 2;
+    return SMR_OK;
+}
+template int tiled_launch_args<false>(const Plan&, void* const*, int, const TiledVariant&, bool, TiledLaunch<false>&);
+template int tiled_launch_args<true>(const Plan&, void* const*, int, const TiledVariant&, bool, TiledLaunch<true>&);
+
+int orbit_launch_args(const Plan& plan, void* const* base, int esize, const OrbitVariant& v, bool wt_store, OrbitLaunch& L) {
+    const OrbitPlan& o = plan.orbit;
+    const Options& opt = options();
+    OrbitArgs& a = L.a;
+    Plan::FormCache& cached = v.pair ? plan.pair_cache : plan.orbit_cache[v.V > 1 ? 1 : 0];
+    if (!cached_form(cached, a)) {
+        OrbitBuild b;
+        if (int rc = v.pair ? build_pair_args(plan, esize, b) : build_orbit_args(plan, esize, v, b)) return rc;
+        a = b.a;
+        if (!jit_dry_run()) {
+            // the one-orbit form's origin rows serve both of its access widths; the PAIR form's work list is its own
+            void** list = v.pair ? &cached.tab : &plan.orbit_list;
+            if (int rc = upload_once(list, b.rows, v.pair ? "orbit pair table" : "orbit origins")) return rc;
+            a.list = reinterpret_cast<const uint32_t*>(*list);
+            cache_form(cached, a);
+        }
+    }
+    a.src = (const char*)base[o.k0];
+    a.dst = (char*)base[0];
+    if (v.pair) {
+        a.nts = opt.nt_store > 0 ? 1 : 0;  // (32- / 64-byte runs: partial lines meet in L2, plain stores -- as in the one-orbit form)
+        L.block = 256;
+        L.lds = 8 * ((size_t)esize << 8);
+    } else {
+        // automatic: only tiles that write whole 128-byte lines (symmetrise 4000^2: 40.2 -> 38.5 us); the 32-/64-byte
+        // runs of the 4-D orbits rely on line partners meeting in L2 and get slower (4.8 -> 6.3 us at 32^4)
+        a.nts = (opt.nt_store > 0 || (opt.nt_store < 0 && plan.c.strides[0][0] == 1 && (esize << o.lg[0]) >= 128)) ? 1 : 0;
+        L.block = 1u << a.ntlog;
+        L.lds = (size_t)v.ng * ((size_t)esize << o.tilelog);
+    }
+    // write-through stores: forced (nt_store = 2), or a launch recorded for a sequence that fits the caches several times over
+    // (want_self_release): its packet then needs no release fence
+    if (wt_store && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
+    L.grid = (unsigned)a.nlist;
+    if (v.pipe && !v.pair) {
+        // as many workgroups as the machine holds at once, a multiple of 8 so that a workgroup stays on its XCD's run
+        const unsigned cap = (unsigned)cu_count() * (unsigned)std::max<size_t>(1, (160 * 1024) / L.lds) / 8u * 8u;
+        if (cap >= 8) L.grid = std::min<unsigned>(L.grid, cap);
+        if (opt.orbit_wgs >= 8) L.grid = std::min<unsigned>(L.grid, (unsigned)opt.orbit_wgs / 8u * 8u);
+    }
+    return SMR_OK;
 }
 
 // ---- per-type dispatch ---------------------------------------------------------------------------

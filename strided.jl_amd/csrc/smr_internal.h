@@ -304,12 +304,13 @@ struct Plan {
     void* scratch = nullptr;  // reductions and split contractions: partials (owned, ReducePlan::scratch_bytes or ContractPlan::scratch_bytes -- a plan
                               // has at most one of the two), followed by RED_COUNTERS arrival counters (zero between launches)
     size_t counter_off = 0;   // byte offset of the counters inside `scratch` (set when it is allocated)
-    // TILED / ORBIT: a kernel form's arguments, built by the family's argument builder (smr_k_tiled.hip: build_tiled_args,
-    // smr_k_orbit.hip: build_orbit_args / build_pair_args) on the plan's first execution of that form, together with the device
-    // table it reads; later executions patch the operand addresses only.  Nothing is cached or uploaded by a dry run (jit_dry_run).
+    // TILED / ORBIT: a kernel form's arguments, built by the family's pure argument builder (smr_plan_tiled_args.cpp: build_tiled_args,
+    // smr_plan_orbit_args.cpp: build_orbit_args / build_pair_args) on the plan's first execution of that form and kept here by the
+    // family's wrapper (smr_api.cpp: tiled_launch_args, orbit_launch_args) together with the device table it uploaded; later
+    // executions patch the operand addresses and the store policy only.  Nothing is cached or uploaded by a dry run (jit_dry_run).
     struct FormCache {
         std::vector<unsigned char> args;  // the argument struct, empty until built
-        void* tab = nullptr;              // TILED: lane table; ORBIT: lane table; ORBIT PAIR: the work list of 8-word entries
+        void* tab = nullptr;              // TILED: lane table; ORBIT PAIR: the work list of 8-word entries; ORBIT one-orbit form: unused (Plan::orbit_list)
     };
     // first execution builds the caches below (upload_table); concurrent executions of one (cached) plan from
     // several host threads serialise on this
@@ -320,9 +321,8 @@ struct Plan {
     mutable void* orbit_list = nullptr;   // ORBIT one-orbit form: per workgroup the slot origins and the slot map
     mutable FormCache pair_cache;         // ORBIT PAIR form
     // every device table above, for plan_free
-    std::array<void**, 9> dev_tables() const {
-        return {&tiled_cache[0].tab, &tiled_cache[1].tab, &tiled_cache[2].tab, &tiled_cache[3].tab, &tiled_order,
-                &orbit_cache[0].tab, &orbit_cache[1].tab, &orbit_list, &pair_cache.tab};
+    std::array<void**, 7> dev_tables() const {
+        return {&tiled_cache[0].tab, &tiled_cache[1].tab, &tiled_cache[2].tab, &tiled_cache[3].tab, &tiled_order, &orbit_list, &pair_cache.tab};
     }
     // eager direct dispatch (smr_eager.cpp): argument blocks of this plan's launches that are resident in device memory, keyed by their
     // bytes -- a repeated execution (same base pointers) reuses the block: no write through the BAR, no read-back round trip
@@ -445,6 +445,20 @@ struct TiledVariant {
     unsigned pgrid = 0; // workgroups of the persistent, software-pipelined form (0: the one-shot form runs)
 };
 TiledVariant tiled_variant(const Plan& plan, void* const* bases, int esize, bool mixed);
+
+// ORBIT: the same question.  native_nin: F::NIN of a natively compiled functor, -1 for a runtime-compiled or interpreted one (the
+// PAIR form exists for native functors of 2..4 inputs only).  The launcher (smr_k_orbit.hip: go) dispatches on the result; the rules
+// live in orbit_variant() alone (smr_plan_orbit.cpp).  Returns SMR_OK, or an error when no kernel exists for the tile size or for
+// unaligned operands.
+struct OrbitVariant {
+    int V = 1;          // elements per global access (V * esize <= 16 bytes)
+    int nrep = 1;       // accesses per lane and slot
+    int ng = 4;         // LDS slots (|G| = 2: 2, else 4)
+    bool own0 = false;  // input 1 is the identity view: its value is the lane's own register
+    bool pipe = false;  // the persistent, software-pipelined form
+    bool pair = false;  // the PAIR form (orbit_pair_body); ng / pipe are then not read
+};
+int orbit_variant(const Plan& plan, void* const* bases, int esize, int native_nin, OrbitVariant& v);
 
 // ---- runtime compilation of f-programs without a natively compiled functor (smr_jit.cpp) ------------
 // The kernel family's own source file is compiled by hiprtc with the f-program turned into a

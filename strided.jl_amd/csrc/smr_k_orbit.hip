@@ -20,72 +20,17 @@
 // dependent memory round trip before the first global load).
 // Measured on MI355X (4-way sum, Float64): 32^4 6.6 -> 4.7 us, 64^4 83 -> 46 us, 128^4 1.73 -> 1.41 ms
 // (tools/c3_proto.hip is the design experiment this kernel follows).
-#ifndef SMR_JIT
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#endif
-
+// The kernel arguments (smr_orbit_args.h) are built once per plan by the device-free builders in smr_plan_orbit_args.cpp and cached
+// (smr_api.cpp: orbit_launch_args sets the operand addresses, the store policy and the persistent grid per call); which kernel runs
+// is orbit_variant()'s choice (smr_plan_orbit.cpp).  This file holds the kernels, the dispatch on that choice and the launches.
 #include "smr_dispatch.h"
+#include "smr_orbit_args.h"
 
 #ifndef SMR_CT
 #error "compile with -DSMR_CT=0..3 or 7"
 #endif
 
-// 1: the per-lane offsets (byte offset in a tile + one LDS read index per permuted view) come from a small
-// device table -- one vector load per lane, issued next to the origin row's scalar load -- instead of
-// bit-slice arithmetic on kernel arguments (measured on the classic kernel: the table is the faster form)
-#ifndef SMR_ORBIT_TABLE
-#define SMR_ORBIT_TABLE 0  // measured: no difference (5.01 vs 5.00 us at 32^4) -> arithmetic, no table to upload
-#endif
-
 namespace smr {
-
-constexpr int OMAXT = 4;  // tiled dims = dims of the unit class <= |G| <= 4
-
-struct OrbitArgs {
-    const char* src;  // the shared buffer, element offset applied
-    char* dst;
-    const uint32_t* list;  // per workgroup a row of 2 * NG words: the NG slot origins (element offsets; [0] = 0xffffffff: idle), then the
-                           // 64-bit slot map -- field (g * 8 + k) * 2: the LDS slot an output of slot g reads input k from.  (The
-                           // natively compiled kernels receive this pointer once more as their FIRST parameter: it is preloaded
-                           // into SGPRs with the wave, and the row's load leaves before the kernel arguments have been fetched.)
-    const uint32_t* lanetab;  // [(r * NT + tid) * rowlen]: byte offset, then the LDS read index of every non-own view
-    int32_t nin, tilelog, ntlog, conj0, nts, nlist;  // nlist: rows of `list` (PIPE form)
-    uint32_t swz_s1, swz_s2, swz_mask, pad1;
-    // element enumeration inside a tile (natural order of the buffer); unused tiled dims have elen = 0
-    int32_t esh[OMAXT], elen[OMAXT];
-    uint32_t estride[OMAXT];       // byte stride of tiled dim j
-    int32_t lsh[MAXIN][OMAXT];     // LDS bit position of tiled dim j as seen through view k
-    uint32_t conjbit[MAXIN];       // 0x80000000 when view k is conjugated (complex types)
-};
-
-// What a wave needs before its first global load can leave: the natively compiled kernels receive these as LEADING SCALAR
-// parameters, which gfx950 preloads into SGPRs with the wave (Makefile: -mllvm -amdgpu-kernarg-preload-count=16) -- the only
-// memory round trip in front of the loads is then the origin row's.  (Left in the argument struct the compiler fetched them in
-// two dependent batches of scalar loads: tools/orbit32_probe.hip, profiles/r06_orbit_phases.txt.)
-struct OrbitHead {
-    const uint32_t* list;  // = OrbitArgs::list
-    const char* src;       // = OrbitArgs::src
-    char* dst;             // = OrbitArgs::dst (left in the struct, its scalar load was sunk between the LDS reads and the adds)
-    uint32_t eshp, elenp;  // esh[j] / elen[j] in byte j
-    uint32_t estride[OMAXT];
-    uint32_t ntlog;
-};
-static inline __host__ __device__ OrbitHead orbit_head(const OrbitArgs& a) {
-    OrbitHead h;
-    h.list = a.list;
-    h.src = a.src;
-    h.dst = a.dst;
-    h.eshp = h.elenp = 0;
-    for (int j = 0; j < OMAXT; ++j) {
-        h.eshp |= (uint32_t)a.esh[j] << (8 * j);
-        h.elenp |= (uint32_t)a.elen[j] << (8 * j);
-        h.estride[j] = a.estride[j];
-    }
-    h.ntlog = (uint32_t)a.ntlog;
-    return h;
-}
 
 template <class T, int V>
 struct alignas(sizeof(T) * V) OVec {
@@ -160,25 +105,8 @@ SMR_DEV void orbit_map_body(const OrbitArgs a, const OrbitHead h, F f) {
 
     // ---- per-lane byte offsets inside a tile + LDS read indices -----------------------------------------
     constexpr int NLR = NK - (OWN0 ? 1 : 0);      // views read from LDS
-    constexpr int ROWLEN = (1 + NLR) <= 2 ? 2 : ((1 + NLR) <= 4 ? 4 : 8);
-    (void)ROWLEN;
     uint32_t goff[NREP];
     uint32_t lr[NK][NREP];  // LDS index of the lane's first element seen through view k
-#if SMR_ORBIT_TABLE
-    {
-        typedef uint32_t trow __attribute__((ext_vector_type(ROWLEN)));
-#pragma unroll
-        for (int r = 0; r < NREP; ++r) {
-            const trow t = reinterpret_cast<const trow*>(a.lanetab)[((uint32_t)r << h.ntlog) | tid];
-            goff[r] = t[0];
-#pragma unroll
-            for (int k = 0; k < NK; ++k) {
-                lr[k][r] = 0;
-                if (!(OWN0 && k == 0)) lr[k][r] = t[1 + k - (OWN0 ? 1 : 0)];
-            }
-        }
-    }
-#else
     uint32_t cj[NREP][OMAXT];
 #pragma unroll
     for (int r = 0; r < NREP; ++r) {
@@ -191,7 +119,6 @@ SMR_DEV void orbit_map_body(const OrbitArgs a, const OrbitHead h, F f) {
         }
         goff[r] = g;
     }
-#endif
 
     // ---- load every slot (natural order) --------------------------------------------------------------
     VT x[NG][NREP];
@@ -203,7 +130,6 @@ SMR_DEV void orbit_map_body(const OrbitArgs a, const OrbitHead h, F f) {
     // ---- while the loads fly: everything the exchange needs from the kernel arguments ---------------
     // (left to itself the compiler sinks these scalar loads below the barrier: one more serial scalar-memory
     // round trip in a 5 us launch; the empty asm statements pin the values in registers here)
-#if !SMR_ORBIT_TABLE
 #pragma unroll
     for (int r = 0; r < NREP; ++r)
 #pragma unroll
@@ -215,7 +141,6 @@ SMR_DEV void orbit_map_body(const OrbitArgs a, const OrbitHead h, F f) {
             }
             lr[k][r] = l;
         }
-#endif
     uint32_t swz_s1 = a.swz_s1, swz_s2 = a.swz_s2, swz_mask = a.swz_mask;
     asm volatile("" : "+s"(swz_s1), "+s"(swz_s2), "+s"(swz_mask));
     uint32_t sbase[NG][NK], hbit[NK], cbit[NK];
@@ -640,254 +565,6 @@ __global__ void __launch_bounds__(1024) k_orbit_map(const uint32_t* list, const 
     SMR_STAMP_END
 }
 
-// XOR-fold swizzle l ^ (((l >> s1) ^ (l >> s2)) & mask): parameters picked per plan by counting the
-// bank conflicts of the transposing LDS reads (a lane group of the hardware must hit distinct banks)
-struct OSwz {
-    uint32_t s1 = 31, s2 = 31, mask = 0;
-    uint32_t operator()(uint32_t i) const { return i ^ (((i >> s1) ^ (i >> s2)) & mask); }
-};
-
-static OSwz choose_orbit_swizzle(const OrbitArgs& a, int nin, bool own0, int esize, int V, int NREP) {
-    // lane group / bank-slot model: ds_read_b32/b64 are served in two halves of 32 lanes over 32 slots
-    // of the access width; ds_read_b128 in groups of 16 lanes over 16 slots
-    const int group = esize >= 16 ? 16 : 32;
-    const uint32_t slots = (uint32_t)group;
-    const uint32_t nt = 1u << a.ntlog;
-    auto cost = [&](const OSwz& s) {
-        long c = 0;
-        for (int k = own0 ? 1 : 0; k < nin; ++k)
-            for (int r = 0; r < NREP; ++r)
-                for (int h = 0; h < V; ++h)
-                    for (uint32_t w0 = 0; w0 < std::min(nt, 256u); w0 += group) {
-                        uint32_t first[32];
-                        int cnt[32];
-                        int worst = 0;
-                        for (uint32_t q = 0; q < slots; ++q) cnt[q] = 0;
-                        for (int lane = 0; lane < group; ++lane) {
-                            const uint32_t e = (((uint32_t)r << a.ntlog) | (w0 + lane)) * V + h;
-                            uint32_t idx = 0;
-                            for (int j = 0; j < OMAXT; ++j) idx |= ((e >> a.esh[j]) & ((1u << a.elen[j]) - 1u)) << a.lsh[k][j];
-                            const uint32_t l = s(idx), q = l % slots;
-                            if (cnt[q] == 0) {
-                                first[q] = l;
-                                cnt[q] = 1;
-                            } else if (first[q] != l) {
-                                ++cnt[q];
-                            }
-                        }
-                        for (uint32_t q = 0; q < slots; ++q) worst = std::max(worst, cnt[q]);
-                        c += worst - 1;
-                    }
-        return c;
-    };
-    OSwz best;
-    long bc = cost(best);
-    auto consider = [&](uint32_t s1, uint32_t s2) {
-        OSwz t;
-        t.s1 = s1;
-        t.s2 = s2;
-        t.mask = slots - 1;
-        const long cc = cost(t);
-        if (cc < bc) {
-            bc = cc;
-            best = t;
-        }
-    };
-    for (uint32_t s1 = 2; s1 <= 6 && bc > 0; ++s1) {
-        consider(s1, 31);  // one-term fold
-        for (uint32_t s2 = s1 + 1; s2 <= 13 && bc > 0; ++s2) consider(s1, s2);
-    }
-    if (std::getenv("SMR_DEBUG_SWIZZLE"))
-        std::fprintf(stderr, "[smr] orbit swizzle: s1=%u s2=%u mask=%u conflict cost %ld\n", best.s1, best.s2, best.mask, bc);
-    return best;
-}
-
-// An ORBIT launch apart from the kernel itself
-struct OrbitLaunch {
-    OrbitArgs a;
-    unsigned grid = 0, block = 0;
-    size_t lds = 0;
-};
-
-// The part of the arguments both forms share: tiled dims in canonical (= natural) order, each view's LDS bit positions and conjugation
-static int orbit_dims(const Plan& plan, const OpTab& tab, int esize, OrbitArgs& a) {
-    const Canon& c = plan.c;
-    const OrbitPlan& o = plan.orbit;
-    a.nin = c.M - 1;
-    a.tilelog = o.tilelog;
-    a.conj0 = tab.conj[0];
-    int nt = 0, sh = 0, jof[MAXN];
-    for (int d = 0; d < c.N; ++d) {
-        jof[d] = -1;
-        if (o.lg[d] == 0) continue;
-        if (nt >= OMAXT) return set_error(SMR_EUNSUPPORTED, "orbit: too many tiled dims");
-        jof[d] = nt;
-        a.esh[nt] = sh;
-        a.elen[nt] = o.lg[d];
-        a.estride[nt] = (uint32_t)(c.strides[o.k0][d] * esize);
-        sh += o.lg[d];
-        ++nt;
-    }
-    for (int k = 1; k < c.M; ++k) {
-        for (int d = 0; d < c.N; ++d)
-            if (jof[d] >= 0) a.lsh[k - 1][jof[d]] = a.esh[jof[o.pdim[k][d]]];
-        a.conjbit[k - 1] = tab.conj[k] ? 0x80000000u : 0u;
-    }
-    return SMR_OK;
-}
-
-// element offset of tile `id` (canonical tile index) in the shared buffer
-static uint32_t orbit_tile_origin(const Plan& plan, i64 id) {
-    const OrbitPlan& o = plan.orbit;
-    i64 org = 0;
-    for (int d = 0; d < plan.c.N; ++d) {
-        org += (id % o.ntiles[d]) * (plan.c.strides[o.k0][d] << o.lg[d]);
-        id /= o.ntiles[d];
-    }
-    return (uint32_t)org;
-}
-
-// Builds the arguments of the one-orbit form (V elements per access, NREP repeats, NG slots, view 0 the identity view when OWN0, the
-// persistent form when PIPE; nk = inputs of the device functor).  Built on the plan's first execution of the form with the work list
-// and the lane table, and cached in the plan (Plan::orbit_cache, orbit_list); the operand addresses, the grid and the store policy
-// are set per call.  wt_store: the kernel's vector type has write-through stores.
-static int build_orbit_args(const Plan& plan, const OpTab& tab, int esize, int V, int NREP, int NG, bool OWN0, bool PIPE, int nk,
-                            bool wt_store, OrbitLaunch& L) {
-    const Canon& c = plan.c;
-    const OrbitPlan& o = plan.orbit;
-    OrbitArgs& a = L.a;
-    Plan::FormCache& cached = plan.orbit_cache[V > 1 ? 1 : 0];
-    if (cached.args.size() == sizeof a) {
-        std::memcpy(&a, cached.args.data(), sizeof a);
-    } else {
-        std::memset(&a, 0, sizeof a);
-        int vlog = 0, nreplog = 0;
-        while ((1 << vlog) < V) ++vlog;
-        while ((1 << nreplog) < NREP) ++nreplog;
-        a.ntlog = o.tilelog - vlog - nreplog;
-        if (int rc = orbit_dims(plan, tab, esize, a)) return rc;
-        if (o.nslots != NG) return set_error(SMR_EINVAL, "orbit: slot count mismatch");
-        const OSwz sw = choose_orbit_swizzle(a, c.M - 1, OWN0, esize, V, NREP);
-        a.swz_s1 = sw.s1;
-        a.swz_s2 = sw.s2;
-        a.swz_mask = sw.mask;
-        if (!plan.orbit_list && !jit_dry_run()) {
-            // one row per workgroup: the NG slot origins (element offset of the tile in each slot), then the slot map (plan_orbit)
-            const size_t nwg = o.wmap.size();
-            std::vector<uint32_t> rows(nwg * 2 * NG, 0u);
-            for (size_t w = 0; w < nwg; ++w) {
-                uint32_t* row = &rows[w * 2 * NG];
-                if (o.wtile[w * NG] == 0xffffffffu) {
-                    row[0] = 0xffffffffu;
-                    continue;
-                }
-                for (int g = 0; g < NG; ++g) row[g] = orbit_tile_origin(plan, o.wtile[w * NG + g]);
-                row[NG] = (uint32_t)o.wmap[w];
-                row[NG + 1] = (uint32_t)(o.wmap[w] >> 32);
-            }
-            if (int rc = upload_table(&plan.orbit_list, rows.data(), rows.size() * sizeof(uint32_t), "orbit origins")) return rc;
-        }
-        a.list = reinterpret_cast<const uint32_t*>(plan.orbit_list);
-        if (!cached.tab && !jit_dry_run()) {
-            // per-lane rows: {byte offset in a tile, LDS read index of every view read from LDS}
-            const int nlr = nk - (OWN0 ? 1 : 0);
-            const int rowlen = (1 + nlr) <= 2 ? 2 : ((1 + nlr) <= 4 ? 4 : 8);
-            const uint32_t nt = 1u << a.ntlog;
-            std::vector<uint32_t> rows((size_t)NREP * nt * rowlen, 0u);
-            for (uint32_t r = 0; r < (uint32_t)NREP; ++r)
-                for (uint32_t tid = 0; tid < nt; ++tid) {
-                    const uint32_t e = ((r << a.ntlog) | tid) * V;
-                    uint32_t* row = &rows[((size_t)(r << a.ntlog) | tid) * rowlen];
-                    for (int j = 0; j < OMAXT; ++j) {
-                        const uint32_t cj = (e >> a.esh[j]) & ((1u << a.elen[j]) - 1u);
-                        row[0] += cj * a.estride[j];
-                        for (int k = OWN0 ? 1 : 0; k < nk && k < c.M - 1; ++k) row[1 + k - (OWN0 ? 1 : 0)] |= cj << a.lsh[k][j];
-                    }
-                }
-            if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(uint32_t), "orbit lane table")) return rc;
-        }
-        a.lanetab = reinterpret_cast<const uint32_t*>(cached.tab);
-        if (!jit_dry_run()) {
-            cached.args.resize(sizeof a);
-            std::memcpy(cached.args.data(), &a, sizeof a);
-        }
-    }
-    a.src = (const char*)tab.base[o.k0];
-    a.dst = (char*)tab.base[0];
-    const Options& opt = options();
-    // automatic: only tiles that write whole 128-byte lines (symmetrise 4000^2: 40.2 -> 38.5 us); the 32-/64-byte
-    // runs of the 4-D orbits rely on line partners meeting in L2 and get slower (4.8 -> 6.3 us at 32^4)
-    a.nts = (opt.nt_store > 0 || (opt.nt_store < 0 && plan.c.strides[0][0] == 1 && (esize << o.lg[0]) >= 128)) ? 1 : 0;
-    // write-through stores: forced (nt_store = 2), or a launch recorded for a sequence that fits the caches several times over
-    // (want_self_release): its packet then needs no release fence
-    if (wt_store && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
-    L.block = 1u << a.ntlog;
-    L.lds = (size_t)NG * ((size_t)esize << o.tilelog);
-    a.nlist = (int32_t)o.wmap.size();
-    L.grid = (unsigned)o.wmap.size();
-    if (PIPE) {
-        // as many workgroups as the machine holds at once, a multiple of 8 so that a workgroup stays on its XCD's run
-        const unsigned cap = (unsigned)cu_count() * (unsigned)std::max<size_t>(1, (160 * 1024) / L.lds) / 8u * 8u;
-        if (cap >= 8) L.grid = std::min<unsigned>(L.grid, cap);
-        if (opt.orbit_wgs >= 8) L.grid = std::min<unsigned>(L.grid, (unsigned)opt.orbit_wgs / 8u * 8u);
-    }
-    return SMR_OK;
-}
-
-// The same for the PAIR form (orbit_pair_body: 256 lanes per two slot sets, 2 elements per access): its work list of 8-word entries is
-// built once per plan (Plan::pair_cache)
-static int build_pair_args(const Plan& plan, const OpTab& tab, int esize, bool wt_store, OrbitLaunch& L) {
-    const Canon& c = plan.c;
-    const OrbitPlan& o = plan.orbit;
-    constexpr int NS = 4;
-    OrbitArgs& a = L.a;
-    Plan::FormCache& cached = plan.pair_cache;
-    if (cached.args.size() == sizeof a) {
-        std::memcpy(&a, cached.args.data(), sizeof a);
-    } else {
-        std::memset(&a, 0, sizeof a);
-        a.ntlog = 8;
-        if (int rc = orbit_dims(plan, tab, esize, a)) return rc;
-        if (!cached.tab && !jit_dry_run()) {
-            const size_t nwg = o.pmap.size() / 2;
-            std::vector<uint32_t> rows(nwg * 4 * 8, 0u);
-            auto region = [](int slot, int b) { return (uint32_t)(((2 * slot + b) << 8) | (b ? 17 : 0)); };
-            for (size_t w = 0; w < nwg; ++w) {
-                if (o.ptile[w * 8] == 0xffffffffu) {
-                    rows[w * 32] = 0xffffffffu;
-                    continue;
-                }
-                for (int j = 0; j < NS; ++j) {
-                    uint32_t* en = &rows[(w * 4 + (size_t)j) * 8];
-                    for (int b = 0; b < 2; ++b) {
-                        en[b] = orbit_tile_origin(plan, o.ptile[w * 8 + (size_t)b * 4 + (size_t)j]);
-                        en[2] |= region(j, b) << (16 * b);
-                        const uint64_t mp = o.pmap[w * 2 + (size_t)b];
-                        // view k of the kernel = input k + 1; input 1 is the identity view (the lane's own registers)
-                        for (int k = 1; k < c.M - 1 && k < 4; ++k) en[2 + k] |= region((int)((mp >> ((j * 8 + k) * 2)) & 3u), b) << (16 * b);
-                    }
-                }
-            }
-            if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(uint32_t), "orbit pair table")) return rc;
-        }
-        a.list = reinterpret_cast<const uint32_t*>(cached.tab);
-        if (!jit_dry_run()) {
-            cached.args.resize(sizeof a);
-            std::memcpy(cached.args.data(), &a, sizeof a);
-        }
-    }
-    a.src = (const char*)tab.base[o.k0];
-    a.dst = (char*)tab.base[0];
-    const Options& opt = options();
-    a.nts = opt.nt_store > 0 ? 1 : 0;  // (32- / 64-byte runs: partial lines meet in L2, plain stores -- as in the one-orbit form)
-    if (wt_store && (opt.nt_store == 2 || want_self_release(plan))) a.nts = 2;
-    a.nlist = (int32_t)(o.pmap.size() / 2);
-    L.grid = (unsigned)(o.pmap.size() / 2);
-    L.block = 256;
-    L.lds = 8 * ((size_t)esize << 8);
-    return SMR_OK;
-}
-
 // the natively compiled kernels take OrbitHead as leading scalar parameters (preloaded into SGPRs), then the struct
 #define SMR_ORBIT_LAUNCH(kern, L, s, f)                                                                                                  \
     do {                                                                                                                                 \
@@ -896,11 +573,13 @@ static int build_pair_args(const Plan& plan, const OpTab& tab, int esize, bool w
                    h_.estride[1], h_.estride[2], h_.estride[3], h_.ntlog, (L).a, f SMR_STAMP_ARG((L).grid, (L).block));                  \
     } while (0)
 
+// native_nin of orbit_variant(): the PAIR form exists for natively compiled functors only
+template <class F> constexpr int orbit_native_nin() { return is_jit<F>::value ? -1 : F::NIN; }
+
 template <class T, class F, int V, int NREP, int NG, bool OWN0, bool PIPE>
-static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
-    const int nk = is_jit<F>::value ? plan.c.M - 1 : ((F::NIN >= 0) ? F::NIN : MAXIN);  // = NK of the device functor
+static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const OrbitVariant& ov) {
     OrbitLaunch L;
-    if (int rc = build_orbit_args(plan, tab, (int)sizeof(T), V, NREP, NG, OWN0, PIPE, nk, has_wt_store<OVec<T, V>>::value, L)) return rc;
+    if (int rc = orbit_launch_args(plan, tab.base, (int)sizeof(T), ov, has_wt_store<OVec<T, V>>::value, L)) return rc;
     if constexpr (is_jit<F>::value) {
         return launch_jit<T>(plan.c, s, "orbit", "smr::OrbitArgs", "orbit_map_body", "smr::orbit_head(a), ", L.grid, L.block, L.lds, L.a, V, NREP,
                              NG, OWN0, PIPE);
@@ -915,9 +594,9 @@ static int go4(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
 }
 
 template <class T, class F>
-static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
+static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const OrbitVariant& ov) {
     OrbitLaunch L;
-    if (int rc = build_pair_args(plan, tab, (int)sizeof(T), has_wt_store<OVec<T, 2>>::value, L)) return rc;
+    if (int rc = orbit_launch_args(plan, tab.base, (int)sizeof(T), ov, has_wt_store<OVec<T, 2>>::value, L)) return rc;
     return launch_native(nullptr, L.lds, "k_orbit_pair", [&] {
         mark_sliceable(2, 0u, (unsigned)(4 * 8 * sizeof(uint32_t)));  // one table row (four entries) per workgroup; the pointer is parameter 0
         if (L.a.nts == 2) mark_self_released();
@@ -931,41 +610,27 @@ static int go_pair(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
     });
 }
 
-// persistent pipelined form: when the LDS footprint leaves one workgroup per CU and every CU gets several orbits
+// The kernel of orbit_variant()'s choice (smr_plan_orbit.cpp) among those compiled for (V, NREP): the PAIR form (go2), or the
+// one-orbit form with 2 or 4 slots, view 0 the identity view or not (go2), one-shot or persistent (go3)
+// The `if constexpr` conditions below say which kernels are compiled; orbit_variant() says which one runs.  The three "no ... kernel
+// of this variant" errors (go3, go2, go) can fire only if the two ever drift apart: they guard, no plan reaches them.
 template <class T, class F, int V, int NREP, int NG, bool OWN0>
-static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
-    const OrbitPlan& o = plan.orbit;
-    const size_t lds = (size_t)NG * (sizeof(T) << o.tilelog);
-    const i64 want = options().orbit_pipe;
-    bool pipe = false;
+static int go3(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const OrbitVariant& ov) {
     if constexpr (V * sizeof(T) == 16) {
-        // at least 8 orbits per CU: with 4 (64^4) the pipelined ComplexF32 kernel -- 128 VGPRs, 20 bytes of scratch -- loses
-        // (68.4 vs 47.6 us) and the Float64 one ties; from 80^4 on it gains 2-4 % (tools/orbit_cplx.py)
-        pipe = want > 0 ? o.list.size() > 256 : (want < 0 && lds > 80 * 1024 && o.list.size() >= 8 * 256);
-        if (pipe) return go4<T, F, V, NREP, NG, OWN0, true>(plan, s, f, tab);
+        if (ov.pipe) return go4<T, F, V, NREP, NG, OWN0, true>(plan, s, f, tab, ov);
     }
-    return go4<T, F, V, NREP, NG, OWN0, false>(plan, s, f, tab);
+    if (ov.pipe) return set_error(SMR_EINVAL, "orbit: no persistent kernel of this variant");
+    return go4<T, F, V, NREP, NG, OWN0, false>(plan, s, f, tab, ov);
 }
 
 template <class T, class F, int V, int NREP>
-static int go2(const Plan& plan, hipStream_t s, F f, const OpTab& tab) {
-    const OrbitPlan& o = plan.orbit;
-    bool own0 = true;  // is input 1 the identity view?
-    for (int d = 0; d < plan.c.N; ++d)
-        if (o.pdim[1][d] != d) own0 = false;
-    if constexpr (!is_jit<F>::value && V == 2 && NREP == 1 && sizeof(T) == 8) {
-        if constexpr (F::NIN >= 2 && F::NIN <= 4) {
-            // Write-through launches (store policy 2: recorded sequences, eager calls on library-owned streams) gain most -- every store
-            // travels to the memory side on its own and 64-byte pieces pay: replay of the 4-way sum at 32^4 4.72 -> 4.31 us on one queue,
-            // 3.66 -> 3.04 cut in two, bench step 5.65 -> 5.2 us -- plain-store launches through HIP 4.40 -> 4.27 us.  (With the first
-            // work list -- an orbit's smallest tile paired with whatever sat next to it -- the form LOST through HIP, 4.72 us: the list
-            // matters as much as the kernel, smr_plan_orbit.cpp.)  orbit_pair = 0 switches the form off (tests, tools/cold_orbit_sweep.py).
-            if (o.pair_ok && own0 && o.ng == 4 && plan.c.M - 1 == F::NIN && options().orbit_pair >= 1)
-                return go_pair<T, F>(plan, s, f, tab);
-        }
+static int go2(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const OrbitVariant& ov) {
+    if constexpr (V == 2 && NREP == 1 && sizeof(T) == 8 && orbit_native_nin<F>() >= 2 && orbit_native_nin<F>() <= 4) {
+        if (ov.pair) return go_pair<T, F>(plan, s, f, tab, ov);
     }
-    if (o.ng == 2) return own0 ? go3<T, F, V, NREP, 2, true>(plan, s, f, tab) : go3<T, F, V, NREP, 2, false>(plan, s, f, tab);
-    return own0 ? go3<T, F, V, NREP, 4, true>(plan, s, f, tab) : go3<T, F, V, NREP, 4, false>(plan, s, f, tab);
+    if (ov.pair) return set_error(SMR_EINVAL, "orbit: no PAIR kernel of this variant");
+    if (ov.ng == 2) return ov.own0 ? go3<T, F, V, NREP, 2, true>(plan, s, f, tab, ov) : go3<T, F, V, NREP, 2, false>(plan, s, f, tab, ov);
+    return ov.own0 ? go3<T, F, V, NREP, 4, true>(plan, s, f, tab, ov) : go3<T, F, V, NREP, 4, false>(plan, s, f, tab, ov);
 }
 
 template <class T, class F>
@@ -976,27 +641,19 @@ static int go(const Plan& plan, void* const* bases, hipStream_t s, F f) {
     // every view must still be a view of ONE buffer after rebinding
     for (int k = 1; k < c.M; ++k)
         if (tab.base[k] != tab.base[o.k0]) return set_error(SMR_EINVAL, "orbit plan: the inputs must stay views of one buffer");
+    OrbitVariant ov;
+    if (int rc = orbit_variant(plan, bases, (int)sizeof(T), orbit_native_nin<F>(), ov)) return rc;
     constexpr int VMAX = (16 / sizeof(T)) > 1 ? (int)(16 / sizeof(T)) : 1;
-    bool vec = o.vec == VMAX && VMAX > 1;
-    if (vec && ((((uintptr_t)tab.base[0]) | ((uintptr_t)tab.base[o.k0])) % 16)) vec = false;
-    const int tile = 1 << o.tilelog;
-    if constexpr (VMAX > 1) {
-        if (vec) {
-            const int nrep = std::max(1, tile / (VMAX * 1024));
-            if (nrep == 1) return go2<T, F, VMAX, 1>(plan, s, f, tab);
-            if (nrep == 2) return go2<T, F, VMAX, 2>(plan, s, f, tab);
-            return set_error(SMR_EINVAL, "orbit: unexpected tile size");
-        }
-        // element-wise accesses (operands not 16-byte aligned): only instantiated for tiles of up to 1024 elements
-        if (tile <= 1024) return go2<T, F, 1, 1>(plan, s, f, tab);
-        return set_error(SMR_EUNSUPPORTED, "orbit plan: operands must be 16-byte aligned (rebind aligned pointers or create a new plan)");
+    if constexpr (VMAX > 1) {  // 16-byte accesses; element-wise ones (operands not 16-byte aligned) for tiles of up to 1024 elements
+        if (ov.V == VMAX && ov.nrep == 1) return go2<T, F, VMAX, 1>(plan, s, f, tab, ov);
+        if (ov.V == VMAX && ov.nrep == 2) return go2<T, F, VMAX, 2>(plan, s, f, tab, ov);
+        if (ov.V == 1 && ov.nrep == 1) return go2<T, F, 1, 1>(plan, s, f, tab, ov);
     } else {
-        const int nrep = std::max(1, tile / 1024);
-        if (nrep == 1) return go2<T, F, 1, 1>(plan, s, f, tab);
-        if (nrep == 2) return go2<T, F, 1, 2>(plan, s, f, tab);
-        if (nrep == 4) return go2<T, F, 1, 4>(plan, s, f, tab);
-        return set_error(SMR_EINVAL, "orbit: unexpected tile size");
+        if (ov.V == 1 && ov.nrep == 1) return go2<T, F, 1, 1>(plan, s, f, tab, ov);
+        if (ov.V == 1 && ov.nrep == 2) return go2<T, F, 1, 2>(plan, s, f, tab, ov);
+        if (ov.V == 1 && ov.nrep == 4) return go2<T, F, 1, 4>(plan, s, f, tab, ov);
     }
+    return set_error(SMR_EINVAL, "orbit: no kernel of this variant");
 }
 
 template <>

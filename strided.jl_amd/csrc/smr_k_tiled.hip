@@ -9,7 +9,7 @@
 //     OWN stride order (consecutive lanes walk that input's unit-stride axis -> coalesced,
 //     16 bytes per lane), direct inputs in destination order;
 //   * phase B: transposed inputs are scattered into an LDS tile laid out in DESTINATION
-//     order, XOR-swizzled with masks searched on the host per plan (choose_swizzle: GF(2) rank
+//     order, XOR-swizzled with masks searched on the host per plan (build_tiled_args: GF(2) rank
 //     test of every staged operand's write pattern and of the read pattern) so that neither the
 //     strided writes nor the linear reads of a lane group collide on a bank;
 //   * phase C: linear (conflict-free) LDS reads, f applied in registers, 16-byte coalesced
@@ -29,91 +29,26 @@
 //     Gr[r], Lr[r], Lh[h] (kernel arguments): contribution of repeat index r / sub-element h,
 // so the kernel contains no index arithmetic beyond one add (address) and one xor (LDS) per
 // access.  Tile coordinates come from multiply-shift division of the workgroup id.  The kernel
-// arguments are built once per plan and cached (only the operand addresses are patched per call).
+// arguments (smr_tiled_args.h) are built once per plan by the device-free builder in smr_plan_tiled_args.cpp
+// and cached (smr_api.cpp: tiled_launch_args patches the operand addresses and the store policy per call);
+// this file holds the kernels, the dispatch on tiled_variant()'s choice and the launches.
 // Measured history (32^4 f64, permutedims! / 4-way sum, us per launch): generic per-dim decode
 // with dependent kernarg loads 11.5 / 28.5 (~2000 scalar instructions per wave: bound by the
 // CU's single scalar unit) -> per-bit tables 6.0 / 14.6 -> 16-B vectors + repeat tables
 // 4.4 / 9.9 -> all loads first, branch-free variants 4.1 / 8.9 -> lane tables 3.4 / 8.4 ->
 // 4096-element tiles on 1024 lanes, searched swizzle, orbit-major order 3.4 / 6.85 -> compile-time
 // modes 3.4 / 6.6 (a plain 16 MiB copy: 3.2; a 5-stream contiguous add: 5.4).
-#ifndef SMR_JIT
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-#endif
-
 #include "smr_dispatch.h"
+#include "smr_tiled_args.h"
 
 #ifndef SMR_CT
 #error "compile with -DSMR_CT=0..3 or 7"
-#endif
-// 1: compute the per-lane rows (bit slices of the lane id, fold swizzle) instead of loading them from the
-// device table.  Measured on MI355X (tools/perm_ab.py, round 2): SLOWER where it was meant to help -- permutedims!
-// 32^4 f64 3.57 vs 3.32 us, f32 2.79 vs 2.57 us, transpose 8192^2 225 vs 209 us (only permutedims! 128^4 f64
-// gained, 866 vs 935 us) -- the table row is one coalesced 8-byte load that overlaps the kernel-argument loads,
-// the arithmetic needs ~30 more scalar argument words and ~15 VALU per operand.  Kept as a build-time experiment.
-#ifndef SMR_TILED_BITS
-#define SMR_TILED_BITS 0
 #endif
 #ifndef SMR_TILED_NTL
 #define SMR_TILED_NTL 0
 #endif
 
 namespace smr {
-
-constexpr int MAXT = 5;
-constexpr int NG = TILED_NG;  // grid dims decoded branch-free; further ones in a (rare) loop
-constexpr int EPL = 4;  // elements per lane (tile elements / workgroup size)
-constexpr int NORD16 = 512;  // tile-order entries that fit into the kernel arguments
-
-template <bool WIDE> struct off_t_of { typedef uint32_t type; };
-template <> struct off_t_of<true> { typedef i64 type; };
-
-// one row of the per-lane table
-template <bool WIDE> struct LaneRow { uint32_t g; uint32_t l; };
-template <> struct alignas(16) LaneRow<true> { i64 g; uint32_t l; uint32_t pad; };
-
-// Wave-uniform description of one operand (a few wide scalar loads).
-template <bool WIDE>
-struct OpDesc {
-    typedef typename off_t_of<WIDE>::type O;
-    void* base;            // element offset already applied
-    uint32_t tstep32[NG];  // byte offset of one tile step along grid dim g (when base32)
-    O Gr[EPL];             // byte offset of repeat index r (own order if staged, else dst order)
-    uint32_t Lr[EPL];      // staged: swizzled LDS index of repeat index r (own order)
-    uint32_t Lh[EPL];      // staged: ... of sub-element h
-    int32_t dtype, conj;
-};
-
-template <bool WIDE>
-struct TiledArgs {
-    // header + tile decode first: they arrive with the first batch of scalar loads
-    int32_t M, ng, tilelog, nstaged, base32, nt, ordmode, nwork;  // nwork: entries of the work list (persistent form)
-    int32_t nts;           // nts: non-temporal stores (small destinations: see Options::nt_store)
-    uint32_t blk0;         // first workgroup of a block-range slice (smr_seq.cpp); 0 for a whole launch.  One-shot form only
-    int32_t pad_[2];
-    int32_t staged[MAXM];  // [1 + i]: LDS slot of input i or -1 ([0] unused)
-    uint32_t ntiles[MAXN], div_m[MAXN], div_s[MAXN], last_ragged[MAXN];
-    const LaneRow<WIDE>* lanetab;  // [(operand k) * T + tid], k = 0 destination
-    const uint32_t* ordtab;        // ordmode 2: tile executed by workgroup b (0xffffffff = none)
-    OpDesc<WIDE> op[MAXM];         // [0] destination, [1 + i] input i
-    uint32_t Lrd[EPL], Lhd[EPL];   // destination-order LDS index of repeat r / sub-element h
-    i64 tstep[MAXM][MAXN];         // 64-bit tile steps (only read when !base32)
-    // edge tiles only
-    uint32_t gflip, gflip_pad;        // bit g: grid coordinate g counts DOWN (ragged dims: their last, partly filled tiles start first)
-    int32_t ej_g[MAXT];               // per tiled dim j: its grid slot (-1: none), the index of its LAST tile and the valid elements in
-    uint32_t ej_ntm1[MAXT], ej_last[MAXT];  // that tile (round 6: one batch of scalar loads instead of a dependent chain through tgrid / gdims / glog)
-    int32_t tgrid[MAXT], tlog[MAXT];  // grid dim / log2 extent of tiled dim j
-    int32_t esh[MAXM][MAXT];          // bit position of tiled dim j in operand k's enumeration
-    i64 gdims[MAXN];
-    int32_t glog[MAXN];
-    uint32_t ord16[NORD16 / 2];  // ordmode 1: the same as 16-bit entries inside the kernel arguments
-    // BITS form (narrow offsets, variants 0 / 1 / 2): the per-lane table rows are COMPUTED -- bit slices of the lane
-    // id -- instead of loaded, which takes one dependent memory round trip out of the prologue
-    int32_t bpos[MAXM][MAXT], blen[MAXM][MAXT], blsh[MAXM][MAXT];  // slice p of operand k's enumeration (blen 0 = unused)
-    uint32_t bstr[MAXM][MAXT];                                     // its byte stride
-    uint32_t fs1, fs2, fmask, fpad;                                // fold swizzle l ^ (((l >> fs1) ^ (l >> fs2)) & fmask)
-};
 
 SMR_DEV uint32_t fastdiv(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(m, n) + n) >> s; }
 
@@ -179,29 +114,13 @@ SMR_DEV void tiled_map_body(const TiledArgs<WIDE> a, F f) {
     const uint32_t tid = threadIdx.x;
 
     // ---- per-lane rows (byte offset + swizzled LDS index of the lane's first element, per operand) ----
-    // tables in device memory (first memory instructions of the kernel) or, BITS, bit slices of the lane id
-    constexpr bool BITS = SMR_TILED_BITS && !WIDE && (MODE & 4) == 0;
+    // tables in device memory: the first memory instructions of the kernel
     LaneRow<WIDE> row[NINMAX + 1];
 #pragma unroll
     for (int k = 0; k <= NINMAX; ++k) {
         row[k].g = 0;
         row[k].l = 0;
-        if constexpr (BITS) {
-            if (NIN_STATIC >= 0 || k <= nin) {
-                const uint32_t e0 = tid << VLOG;
-                uint32_t g = 0, idx = 0;
-#pragma unroll
-                for (int p = 0; p < MAXT; ++p) {
-                    const uint32_t c = __builtin_amdgcn_ubfe(e0, (uint32_t)a.bpos[k][p], (uint32_t)a.blen[k][p]);
-                    g += c * a.bstr[k][p];
-                    idx |= c << a.blsh[k][p];
-                }
-                row[k].g = g;
-                row[k].l = idx ^ (((idx >> a.fs1) ^ (idx >> a.fs2)) & a.fmask);
-            }
-        } else {
-            if (k <= nin) row[k] = a.lanetab[k * NT + tid];
-        }
+        if (k <= nin) row[k] = a.lanetab[k * NT + tid];
     }
 
     // ---- which tile ---------------------------------------------------------------------------------
@@ -569,29 +488,12 @@ SMR_DEV void tiled_map_pipe_body(const TiledArgs<WIDE> a, F f) {
     const int nin = (NIN_STATIC >= 0) ? NIN_STATIC : a.M - 1;
     const uint32_t tid = threadIdx.x;
 
-    constexpr bool BITS = SMR_TILED_BITS && !WIDE;
-    constexpr int VLOGP = (V == 1) ? 0 : (V == 2 ? 1 : 2);
     LaneRow<WIDE> row[NINMAX + 1];
 #pragma unroll
     for (int k = 0; k <= NINMAX; ++k) {
         row[k].g = 0;
         row[k].l = 0;
-        if constexpr (BITS) {
-            if (NIN_STATIC >= 0 || k <= nin) {
-                const uint32_t e0 = tid << VLOGP;
-                uint32_t g = 0, idx = 0;
-#pragma unroll
-                for (int p = 0; p < MAXT; ++p) {
-                    const uint32_t c = __builtin_amdgcn_ubfe(e0, (uint32_t)a.bpos[k][p], (uint32_t)a.blen[k][p]);
-                    g += c * a.bstr[k][p];
-                    idx |= c << a.blsh[k][p];
-                }
-                row[k].g = g;
-                row[k].l = idx ^ (((idx >> a.fs1) ^ (idx >> a.fs2)) & a.fmask);
-            }
-        } else {
-            if (k <= nin) row[k] = a.lanetab[k * NT + tid];
-        }
+        if (k <= nin) row[k] = a.lanetab[k * NT + tid];
     }
 
     // work-list entry -> tile id (0xffffffff: none, and none after it for this workgroup)
@@ -761,407 +663,11 @@ __global__ void __launch_bounds__(1 << THRLOG) k_tiled_map_pipe(const TiledArgs<
     SMR_STAMP_END
 }
 
-// ---- LDS swizzle ------------------------------------------------------------------------------------
-// l' = l ^ XOR_{b >= w, bit b of l set} mask[b]: the low w index bits (the 128 B one LDS write
-// group spans, in elements) are XORed with one w-bit mask per higher index bit.  A lane group's
-// accesses are conflict-free iff the slot images of the index bits its lanes toggle are linearly
-// independent over GF(2).  The masks are searched on the host (a small hill climb, once per plan)
-// against the write pattern of every staged operand and the destination-order read pattern; the
-// start point is the plain fold mask[b] = 1 << ((b - w) mod w).
-struct Swizzle {
-    int w;
-    uint32_t mask[32];
-    uint32_t apply(uint32_t l) const {
-        uint32_t r = l;
-        for (int b = w; b < 32; ++b)
-            if ((l >> b) & 1u) r ^= mask[b];
-        return r;
-    }
-};
-
-static int gf2_rank(const uint32_t* v, int n) {
-    uint32_t basis[32];
-    int r = 0;
-    for (int i = 0; i < n; ++i) {
-        uint32_t x = v[i];
-        for (int j = 0; j < r; ++j)
-            if ((x ^ basis[j]) < x) x ^= basis[j];
-        if (x) {
-            basis[r++] = x;
-            for (int j = r - 1; j > 0 && basis[j] > basis[j - 1]; --j) std::swap(basis[j], basis[j - 1]);
-        }
-    }
-    return r;
-}
-
-// the index bits one hardware lane group toggles + the width of the bank-slot space it lands in
-struct LanePattern {
-    int n;
-    int bits[8];
-    int slotbits;
-};
-
-static Swizzle choose_swizzle(int tilelog, int w, const std::vector<LanePattern>& pats, int* cost0 = nullptr, int* cost1 = nullptr) {
-    Swizzle sw;
-    sw.w = (w > 0 && tilelog > w) ? w : 32;
-    for (int b = 0; b < 32; ++b) sw.mask[b] = 0;
-    if (sw.w == 32) return sw;
-    for (int b = w; b < tilelog; ++b) sw.mask[b] = 1u << ((b - w) % w);
-    auto cost = [&](const Swizzle& s) {
-        int c = 0;
-        for (const LanePattern& p : pats) {
-            uint32_t img[8];
-            const uint32_t sm = (1u << p.slotbits) - 1u;
-            for (int i = 0; i < p.n; ++i) {
-                const int b = p.bits[i];
-                uint32_t v = 1u << b;          // the bit itself (dropped below if outside the slot space)
-                if (b >= w) v ^= s.mask[b];   // its swizzle mask (acts on the low w bits)
-                img[i] = v & sm;
-            }
-            c += (1 << (p.n - gf2_rank(img, p.n))) - 1;
-        }
-        return c;
-    };
-    int best = cost(sw);
-    if (cost0) *cost0 = best;
-    uint64_t rng = 0x9E3779B97F4A7C15ull;
-    for (int it = 0; it < 6000 && best > 0; ++it) {
-        rng = rng * 6364136223846793005ull + 1442695040888963407ull;
-        const int b = w + (int)((rng >> 33) % (uint64_t)(tilelog - w));
-        const uint32_t m = (uint32_t)((rng >> 20) & ((1u << w) - 1u));
-        Swizzle t = sw;
-        t.mask[b] = m;
-        const int c = cost(t);
-        if (c <= best) {
-            best = c;
-            sw = t;
-        }
-    }
-    if (cost1) *cost1 = best;
-    return sw;
-}
-
-// A TILED launch of kernel variant (WIDE, V, MODE, THRLOG) apart from the kernel itself
-template <bool WIDE>
-struct TiledLaunch {
-    TiledArgs<WIDE> a;
-    unsigned grid = 0;        // workgroups of the one-shot form
-    unsigned pgrid = 0;       // of the persistent, software-pipelined form (0: the one-shot form runs)
-    size_t lds = 0;
-};
-
-// Builds the arguments of a TILED launch.  They depend on the plan only, except for the operand addresses: built on the plan's
-// first execution of the variant (WIDE, V) with its lane and tile-order tables, and cached in the plan (Plan::tiled_cache).  The operand
-// addresses, the persistent grid and the store policy are set per call; wt_store: the kernel's vector type has write-through stores.
-template <bool WIDE>
-static int build_tiled_args(const Plan& plan, const OpTab& tab, int esize, const TiledVariant& tv, bool wt_store, TiledLaunch<WIDE>& L) {
-    typedef typename off_t_of<WIDE>::type O;
-    const int V = tv.V, MODE = tv.mode, THRLOG = tv.thrlog;
-    const bool EDGE = (MODE & 1) != 0, LEAN = (MODE & 4) == 0;
-    const int NREP = EPL / V, NT = 1 << THRLOG;
-    const Canon& c = plan.c;
-    const TilePlan& t = plan.tile;
-    const Options& o = options();
-    int vlog = 0;
-    while ((1 << vlog) < V) ++vlog;
-    TiledArgs<WIDE>& a = L.a;
-    L.lds = (size_t)t.nstaged * ((size_t)1 << t.tilelog) * esize;
-    L.grid = t.ord.empty() ? (unsigned)t.grid : (unsigned)t.ord.size();
-    L.pgrid = tv.pgrid;  // the persistent, software-pipelined form (tiled_variant)
-    // non-temporal stores: measured faster or equal whenever a tile writes whole 128-byte lines (32^4 Float64
-    // permutedims! 3.36 -> 2.76 us, 128^4 864 -> 818 us, never slower for a consumer kernel that follows);
-    // partial lines must meet in L2 first, so short destination runs keep plain stores
-    int nts_now = (o.nt_store > 0) ? 1 : 0;
-    if (o.nt_store < 0) {
-        const i64 run = std::min<i64>(c.dims[0], (i64)1 << t.tlog[0]) * c.esize[0];
-        nts_now = (c.strides[0][0] == 1 && run >= 128) ? 1 : 0;
-    }
-    // write-through stores (policy 2): forced, or a launch recorded for a sequence (its packet then needs no release fence).  Only the
-    // one-shot vector form: there every store of the kernel is one of the vector stores below.
-    if (wt_store && L.pgrid == 0 && (o.nt_store == 2 || want_self_release(plan))) nts_now = 2;
-    const int variant = (WIDE ? 2 : 0) + (V > 1 ? 1 : 0);
-    Plan::FormCache& cached = plan.tiled_cache[variant];
-    if (cached.args.size() == sizeof a) {
-        std::memcpy(&a, cached.args.data(), sizeof a);
-        for (int k = 0; k < c.M; ++k) a.op[k].base = tab.base[k];
-        a.nts = nts_now;
-        return SMR_OK;
-    }
-    std::memset(&a, 0, sizeof a);
-    a.nwork = (int32_t)L.grid;
-    if (!t.ord.empty() && t.ord.size() <= (size_t)NORD16 && t.grid < 0xffff) {
-        a.ordmode = 1;
-        for (size_t i = 0; i < t.ord.size(); ++i) {
-            const uint32_t v = t.ord[i] == 0xffffffffu ? 0xffffu : t.ord[i];
-            a.ord16[i >> 1] |= v << (16 * (i & 1));
-        }
-    } else if (!t.ord.empty()) {
-        a.ordmode = 2;
-        if (!plan.tiled_order && !jit_dry_run())
-            if (int rc = upload_table(&plan.tiled_order, t.ord.data(), t.ord.size() * sizeof(uint32_t), "tile order")) return rc;
-        a.ordtab = reinterpret_cast<const uint32_t*>(plan.tiled_order);
-    }
-    a.M = c.M;
-    a.nt = t.nt;
-    a.tilelog = t.tilelog;
-    a.nstaged = t.nstaged;
-    int tlogdim[MAXN] = {0};
-    int lsh[MAXT];
-    int sh = 0;
-    for (int j = 0; j < t.nt; ++j) {
-        lsh[j] = sh;
-        tlogdim[t.tdim[j]] = t.tlog[j];
-        sh += t.tlog[j];
-    }
-    // LDS swizzle: slot width = the 128 B an LDS write group spans, in elements
-    int w = 0;
-    while ((esize << w) < 128) ++w;
-    std::vector<LanePattern> pats;
-    if (esize >= 4 && t.tilelog > w) {
-        const int nread = esize == 16 ? 4 : 5;  // ds_read_b32/b64: 32 lanes, b128: 16 lanes per pass
-        for (int k = 1; k < c.M; ++k) {
-            if (t.staged[k] < 0) continue;
-            // operand k's enumeration: its bit (vlog + i) is lane bit i of the write group
-            int bitpos[32], pos = 0;
-            for (int jj = 0; jj < t.nt; ++jj) {
-                const int j = t.order[k][jj];
-                for (int bit = 0; bit < t.tlog[j]; ++bit) bitpos[pos++] = lsh[j] + bit;
-            }
-            LanePattern p;
-            p.n = w;
-            p.slotbits = w;
-            for (int i2 = 0; i2 < w; ++i2) p.bits[i2] = bitpos[vlog + i2];
-            pats.push_back(p);
-        }
-        LanePattern r;
-        r.n = nread;
-        r.slotbits = nread;
-        for (int i2 = 0; i2 < nread; ++i2) r.bits[i2] = vlog + i2;
-        pats.push_back(r);
-    }
-    int cost0 = 0, cost1 = 0;
-    const bool BITS = SMR_TILED_BITS && !WIDE && LEAN;
-    Swizzle swz = choose_swizzle(t.tilelog, w, pats, &cost0, &cost1);
-    uint32_t fs1 = 31, fs2 = 31, fmask = 0;
-    if (BITS && swz.w != 32) {
-        // the kernel computes the swizzle itself: restrict it to XOR folds of the index onto its low w bits,
-        // i ^ (((i >> s1) ^ (i >> s2)) & (2^w - 1)), s1 >= w; pick the fold with the fewest bank conflicts
-        auto fold = [&](int s1, int s2) {
-            Swizzle f;
-            f.w = w;
-            for (int b = 0; b < 32; ++b) {
-                f.mask[b] = 0;
-                if (b >= s1 && b < t.tilelog) f.mask[b] ^= (1u << (b - s1)) & ((1u << w) - 1u);
-                if (b >= s2 && b < t.tilelog) f.mask[b] ^= (1u << (b - s2)) & ((1u << w) - 1u);
-            }
-            return f;
-        };
-        auto fcost = [&](const Swizzle& f) {
-            int cst = 0;
-            for (const LanePattern& pt : pats) {
-                uint32_t img[8];
-                const uint32_t sm = (1u << pt.slotbits) - 1u;
-                for (int i2 = 0; i2 < pt.n; ++i2) {
-                    const int b = pt.bits[i2];
-                    uint32_t v = 1u << b;
-                    if (b >= w) v ^= f.mask[b];
-                    img[i2] = v & sm;
-                }
-                cst += (1 << (pt.n - gf2_rank(img, pt.n))) - 1;
-            }
-            return cst;
-        };
-        int bestc = 1 << 30;
-        for (int s1 = w; s1 < t.tilelog; ++s1)
-            for (int s2 = s1 + 1; s2 <= t.tilelog; ++s2) {  // s2 == tilelog: one-term fold
-                const Swizzle f = fold(s1, s2 == t.tilelog ? 32 : s2);
-                const int cst = fcost(f);
-                if (cst < bestc) {
-                    bestc = cst;
-                    swz = f;
-                    fs1 = (uint32_t)s1;
-                    fs2 = s2 == t.tilelog ? 31u : (uint32_t)s2;
-                    fmask = (1u << w) - 1u;
-                }
-            }
-        cost1 = bestc;
-    }
-    if (std::getenv("SMR_DEBUG_SWIZZLE"))
-        std::fprintf(stderr, "[smr] tiled swizzle: w=%d V=%d patterns=%zu conflict cost fold=%d searched=%d\n", w, V, pats.size(), cost0, cost1);
-    // grid dims: canonical dims with more than one tile, in the order the planner chose (TilePlan::gorder: canonical order, or --
-    // HBM-sized transposes -- the tile index along the INPUT's unit axis second: plan_tiles)
-    int gof[MAXN], ng = 0;
-    for (int d = 0; d < c.N; ++d) gof[d] = -1;
-    for (int i = 0; i < c.N; ++i) {
-        const int d = t.gorder[i];
-        if (d >= 0 && d < c.N && gof[d] < 0 && t.ntiles[d] > 1) gof[d] = ng++;
-    }
-    for (int d = 0; d < c.N; ++d)  // (anything the planner's order left out: canonical order behind it)
-        if (gof[d] < 0 && t.ntiles[d] > 1) gof[d] = ng++;
-    a.gflip = 0;
-    auto is_ragged = [&](int d) { return tlogdim[d] > 0 && (c.dims[d] & (((i64)1 << tlogdim[d]) - 1)) != 0; };
-    int nragged = 0;
-    for (int d = 0; d < c.N; ++d)
-        if (gof[d] >= 0 && is_ragged(d)) ++nragged;
-    // (measured with ONE ragged grid dim: transposes of (7200,104) 4.05 -> 3.23 us, (7168,100) 4.08 -> 3.72, (96,9000) 3.42 -> 3.21;
-    // with two -- (100,90,80) permutes -- a tie or a loss: those keep the planner's order.  tiled_edge_first = 2: whenever it applies)
-    // ... with two or more they keep the planner's order and only count backwards ((257,129,65) 8.2 -> 7.8 us, (1400,1500) 6.6 -> 6.5;
-    // moved to the slow end as well: (300,301,35) 12.1 -> 13.1).  tiled_edge_first = 3: backwards only, 2: moved + backwards, always
-    if (EDGE && LEAN && t.ord.empty() && (o.tiled_edge_first == 3 || (o.tiled_edge_first == 1 && nragged >= 2))) {
-        for (int d = 0; d < c.N; ++d)
-            if (gof[d] >= 0 && gof[d] < NG && is_ragged(d)) a.gflip |= 1u << gof[d];
-    } else if (EDGE && LEAN && t.ord.empty() && (o.tiled_edge_first == 2 || (o.tiled_edge_first == 1 && nragged == 1))) {
-        // ragged dims to the slow end of the grid (stable), counted backwards
-        int order[MAXN], n2 = 0;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int g = 0; g < ng; ++g)
-                for (int d = 0; d < c.N; ++d)
-                    if (gof[d] == g && (is_ragged(d) ? 1 : 0) == pass) order[n2++] = d;
-        for (int i = 0; i < n2; ++i) {
-            gof[order[i]] = i;
-            if (is_ragged(order[i])) a.gflip |= 1u << i;
-        }
-    }
-    for (int g = 0; g < MAXN; ++g) {
-        a.ntiles[g] = 1;
-        a.div_m[g] = 0;
-        a.div_s[g] = 0;
-        a.last_ragged[g] = 0xffffffffu;
-        a.gdims[g] = 1;
-        a.glog[g] = 0;
-    }
-    for (int d = 0; d < c.N; ++d) {
-        const int g = gof[d];
-        if (g < 0) continue;
-        const uint32_t nt = (uint32_t)t.ntiles[d];
-        a.ntiles[g] = nt;
-        int l = 0;
-        while ((1ull << l) < nt) ++l;
-        a.div_m[g] = (uint32_t)((((1ull << 32) * ((1ull << l) - nt)) / nt) + 1);
-        a.div_s[g] = (uint32_t)l;
-        a.gdims[g] = c.dims[d];
-        a.glog[g] = tlogdim[d];
-        if (c.dims[d] & (((i64)1 << tlogdim[d]) - 1)) a.last_ragged[g] = nt - 1;
-    }
-    for (int j = 0; j < t.nt; ++j) {
-        a.tlog[j] = t.tlog[j];
-        int g = gof[t.tdim[j]];
-        if (g < 0 && (c.dims[t.tdim[j]] & (((i64)1 << t.tlog[j]) - 1))) {
-            // a tiled dim covered by a single, partly empty tile: give it a one-tile grid slot so
-            // that every workgroup takes the bounds-checked path
-            if (ng >= MAXN) return set_error(SMR_EUNSUPPORTED, "tiled: too many grid dims");
-            g = ng++;
-            a.gdims[g] = c.dims[t.tdim[j]];
-            a.glog[g] = t.tlog[j];
-            a.last_ragged[g] = 0;  // tc == 0 always
-        }
-        a.tgrid[j] = g;
-    }
-    for (int j = 0; j < MAXT; ++j) {
-        a.ej_g[j] = -1;
-        a.ej_ntm1[j] = 0;
-        a.ej_last[j] = 0x7fffffffu;
-        if (j < t.nt && a.tgrid[j] >= 0) {
-            const i64 ext = c.dims[t.tdim[j]], tile = (i64)1 << t.tlog[j], nt = (ext + tile - 1) / tile;
-            a.ej_g[j] = a.tgrid[j];
-            a.ej_ntm1[j] = (uint32_t)(nt - 1);
-            a.ej_last[j] = (uint32_t)(ext - (nt - 1) * tile);  // 1 .. tile (a whole last tile keeps every lane: lim = tile)
-        }
-    }
-    a.ng = ng;
-    // 32-bit tile-origin arithmetic when every operand's tile origins stay below 4 GiB (plan_tiles; tiled_variant picks variant 7 otherwise)
-    a.base32 = t.origins32 ? 1 : 0;
-    if (LEAN && (!t.origins32 || ng > NG)) return set_error(SMR_EINVAL, "tiled: a lean variant was picked for a plan without 32-bit tile origins");
-
-    // per-lane table: built once per (plan, kernel variant), kept in device memory (not needed by the BITS form)
-    const bool build_tab = !BITS && cached.tab == nullptr && !jit_dry_run();
-    a.fs1 = fs1;
-    a.fs2 = fs2;
-    a.fmask = fmask;
-    std::vector<LaneRow<WIDE>> rows;
-    if (build_tab) rows.assign((size_t)c.M * NT, LaneRow<WIDE>{});
-
-    for (int k = 0; k < MAXM; ++k) a.staged[k] = -1;
-    for (int k = 0; k < c.M; ++k) {
-        const bool own = k > 0 && t.staged[k] >= 0;
-        OpDesc<WIDE>& d = a.op[k];
-        const i64 es = c.esize[k];
-        a.staged[k] = own ? t.staged[k] : -1;
-        d.base = tab.base[k];
-        d.dtype = tab.dtype[k];
-        d.conj = tab.conj[k];
-        for (int dd = 0; dd < c.N; ++dd)
-            if (gof[dd] >= 0) {
-                const i64 st = c.strides[k][dd] * ((i64)1 << tlogdim[dd]) * es;
-                a.tstep[k][gof[dd]] = st;
-                if (gof[dd] < NG) d.tstep32[gof[dd]] = (uint32_t)st;
-            }
-        // per-bit contributions in this operand's enumeration order
-        i64 gbit[32] = {0};
-        uint32_t lbit[32] = {0};
-        int pos = 0;
-        for (int jj = 0; jj < t.nt; ++jj) {
-            const int j = own ? t.order[k][jj] : jj;
-            a.esh[k][j] = pos;
-            a.bpos[k][jj] = pos;
-            a.blen[k][jj] = t.tlog[j];
-            a.blsh[k][jj] = lsh[j];
-            a.bstr[k][jj] = (uint32_t)(c.strides[k][t.tdim[j]] * es);
-            for (int bit = 0; bit < t.tlog[j]; ++bit) {
-                gbit[pos + bit] = c.strides[k][t.tdim[j]] * ((i64)1 << bit) * es;
-                lbit[pos + bit] = swz.apply(1u << (lsh[j] + bit));
-            }
-            pos += t.tlog[j];
-        }
-        for (int h = 0; h < V; ++h) {
-            uint32_t l = 0;
-            for (int bit = 0; bit < vlog; ++bit)
-                if ((h >> bit) & 1) l ^= lbit[bit];
-            d.Lh[h] = l;
-        }
-        for (int r = 0; r < NREP; ++r) {
-            i64 g = 0;
-            uint32_t l = 0;
-            for (int bit = 0; bit < 5; ++bit)
-                if ((r >> bit) & 1) {
-                    g += gbit[vlog + THRLOG + bit];
-                    l ^= lbit[vlog + THRLOG + bit];
-                }
-            d.Gr[r] = (O)g;
-            d.Lr[r] = l;
-        }
-        if (build_tab)
-            for (int tid = 0; tid < NT; ++tid) {
-                i64 g = 0;
-                uint32_t l = 0;
-                for (int bit = 0; bit < THRLOG; ++bit)
-                    if ((tid >> bit) & 1) {
-                        g += gbit[vlog + bit];
-                        l ^= lbit[vlog + bit];
-                    }
-                rows[(size_t)k * NT + tid].g = (O)g;
-                rows[(size_t)k * NT + tid].l = l;
-            }
-    }
-    for (int r = 0; r < NREP; ++r) a.Lrd[r] = a.op[0].Lr[r];
-    for (int h = 0; h < V; ++h) a.Lhd[h] = a.op[0].Lh[h];
-    if (build_tab)
-        if (int rc = upload_table(&cached.tab, rows.data(), rows.size() * sizeof(LaneRow<WIDE>), "lane table")) return rc;
-    a.lanetab = reinterpret_cast<const LaneRow<WIDE>*>(cached.tab);
-
-    if (!jit_dry_run()) {
-        cached.args.resize(sizeof a);
-        std::memcpy(cached.args.data(), &a, sizeof a);
-    }
-    a.nts = nts_now;
-    return SMR_OK;
-}
-
 template <class T, class F, bool MIXED, bool WIDE, int V, int MODE, int THRLOG>
 static int go3e(const Plan& plan, hipStream_t s, F f, const OpTab& tab, const TiledVariant& tv) {
     TiledLaunch<WIDE> L;
     constexpr bool wt_store = V > 1 && !MIXED && has_wt_store<TVec<T, V>>::value;
-    if (int rc = build_tiled_args<WIDE>(plan, tab, (int)sizeof(T), tv, wt_store, L)) return rc;
+    if (int rc = tiled_launch_args<WIDE>(plan, tab.base, (int)sizeof(T), tv, wt_store, L)) return rc;
     const TiledArgs<WIDE>& ka = L.a;
     const unsigned block = 1u << THRLOG;
     auto launch = [&]() -> int {

@@ -314,4 +314,52 @@ bool plan_orbit(const Canon& c, OrbitPlan& o) {
     return true;
 }
 
+int orbit_variant(const Plan& plan, void* const* bases, int esize, int native_nin, OrbitVariant& v) {
+    const Canon& c = plan.c;
+    const OrbitPlan& o = plan.orbit;
+    v = OrbitVariant();
+    auto addr = [&](int k) { return (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]); };
+    const int VMAX = 16 / esize > 1 ? 16 / esize : 1;
+    bool vec = o.vec == VMAX && VMAX > 1;
+    if (vec && ((addr(0) | addr(o.k0)) % 16)) vec = false;
+    const int tile = 1 << o.tilelog;
+    if (VMAX > 1) {
+        if (vec) {
+            v.V = VMAX;
+            v.nrep = std::max(1, tile / (VMAX * 1024));
+            if (v.nrep != 1 && v.nrep != 2) return set_error(SMR_EINVAL, "orbit: unexpected tile size");
+        } else if (tile > 1024) {
+            // element-wise accesses (operands not 16-byte aligned): only instantiated for tiles of up to 1024 elements
+            return set_error(SMR_EUNSUPPORTED, "orbit plan: operands must be 16-byte aligned (rebind aligned pointers or create a new plan)");
+        }
+    } else {
+        v.nrep = std::max(1, tile / 1024);
+        if (v.nrep != 1 && v.nrep != 2 && v.nrep != 4) return set_error(SMR_EINVAL, "orbit: unexpected tile size");
+    }
+    v.own0 = true;  // is input 1 the identity view?
+    for (int d = 0; d < c.N; ++d)
+        if (o.pdim[1][d] != d) v.own0 = false;
+    v.ng = o.ng == 2 ? 2 : 4;
+    if (v.V == 2 && v.nrep == 1 && esize == 8 && native_nin >= 2 && native_nin <= 4) {
+        // Write-through launches (store policy 2: recorded sequences, eager calls on library-owned streams) gain most -- every store
+        // travels to the memory side on its own and 64-byte pieces pay: replay of the 4-way sum at 32^4 4.72 -> 4.31 us on one queue,
+        // 3.66 -> 3.04 cut in two, bench step 5.65 -> 5.2 us -- plain-store launches through HIP 4.40 -> 4.27 us.  (With the first
+        // work list -- an orbit's smallest tile paired with whatever sat next to it -- the form LOST through HIP, 4.72 us: the list
+        // matters as much as the kernel, plan_orbit.)  orbit_pair = 0 switches the form off (tests, tools/cold_orbit_sweep.py).
+        if (o.pair_ok && v.own0 && o.ng == 4 && c.M - 1 == native_nin && options().orbit_pair >= 1) {
+            v.pair = true;
+            return SMR_OK;
+        }
+    }
+    // persistent pipelined form: when the LDS footprint leaves one workgroup per CU and every CU gets several orbits
+    if (v.V * esize == 16) {
+        const size_t lds = (size_t)v.ng * ((size_t)esize << o.tilelog);
+        const i64 want = options().orbit_pipe;
+        // at least 8 orbits per CU: with 4 (64^4) the pipelined ComplexF32 kernel -- 128 VGPRs, 20 bytes of scratch -- loses
+        // (68.4 vs 47.6 us) and the Float64 one ties; from 80^4 on it gains 2-4 % (tools/orbit_cplx.py)
+        v.pipe = want > 0 ? o.list.size() > 256 : (want < 0 && lds > 80 * 1024 && o.list.size() >= 8 * 256);
+    }
+    return SMR_OK;
+}
+
 }  // namespace smr

@@ -15,16 +15,30 @@
 // Before the groups, a section "split <id> ..." plans the generic product box with "contract_split" / "contract_tile" set: both outcomes
 // of the rule, every tile, forced slices, slices clamped to the chunks, a forced tile refused (`sneed`).  The sections before it plan
 // with both options at their defaults.
+// Behind every TILED and ORBIT plan line come the launch arguments the family's pure builder makes for it (smr_plan_tiled_args.cpp,
+// smr_plan_orbit_args.cpp): "args <id> opt=<set> | <form> | <digest>" over the builder's status, the argument struct's bytes (pointers
+// null) and its tables -- TILED: the variant tiled_variant() names, struct and lane rows; ORBIT: "variant" lines with orbit_variant()'s
+// answer for a runtime-compiled functor (native_nin = -1) and for a native one of M - 1 inputs, the one-orbit form's struct and origin
+// rows, and the PAIR form's struct and work list where the native functor gets it.  Every form a launcher can reach must be digested
+// (`form_need`): TILED narrow with V = 1 (modes 0, 1, 2, 7) and V = VMAX (modes 0, 1, 2, 7, 9) and wide (V = 1; modes 0, 1, 2, 7);
+// ORBIT with 2 and 4 slots, with and without the identity view first, the PAIR form, and element-wise accesses (V = 1 where VMAX > 1:
+// reached by the "off1" variants, whose views begin one element into the buffer).  The present corpus reaches all of them.
+// Two combinations of the list (V in {1, VMAX}) x (narrow, wide) x (modes 0, 1, 2, 7, 9) are absent from `form_need` because no plan
+// can have them: tiled_variant() picks V > 1 only when the offsets are narrow (`!v.wide`), so there is no wide V > 1 form, and mode 9 is
+// mode 1 plus partial VECTORS, picked only when V > 1, so there is no mode 9 with V = 1 (narrow or wide).
 // It exits with status 1 when too few problems reach one of the work-list builders or input variants (`need`), when a group kind, body,
-// tile, scalar form or refusal is not reached (`gneed`), or when a group is refused or accepted against its recipe: a comparison of
+// tile, scalar form or refusal is not reached (`gneed`), when a form of the argument builders is not reached (`form_need`), or when a group is refused or accepted against its recipe: a comparison of
 // nothing passes.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
 #include "../strided.jl_amd/csrc/smr_group.h"
+#include "../strided.jl_amd/csrc/smr_orbit_args.h"
+#include "../strided.jl_amd/csrc/smr_tiled_args.h"
 
 static std::string last_error;  // what a refused group prints
 namespace smr {
@@ -171,6 +185,65 @@ static const char* cname[] = {"orbit_pair", "orbit_packed", "tiled_orbit_order",
 static long counts[C_COUNT], var_lines[6], fam_lines[9], lines;
 constexpr long need = 40;
 
+// ---- the launch arguments of TILED and ORBIT (the pure builders) -------------------------------------------------------------------
+static std::map<std::string, long> form_counts;
+static const char* const form_need[] = {"tiled narrow V=1 mode=0", "tiled narrow V=1 mode=1", "tiled narrow V=1 mode=2", "tiled narrow V=1 mode=7",
+                                        "tiled narrow V>1 mode=0", "tiled narrow V>1 mode=1", "tiled narrow V>1 mode=2", "tiled narrow V>1 mode=7",
+                                        "tiled narrow V>1 mode=9", "tiled wide V=1 mode=0",   "tiled wide V=1 mode=1",   "tiled wide V=1 mode=2",
+                                        "tiled wide V=1 mode=7",   "orbit ng=2",              "orbit ng=4",              "orbit own0=0",
+                                        "orbit own0=1",            "orbit pair",              "orbit V=1"};
+constexpr long form_min = 8;
+
+template <class A, class R>
+static uint64_t digest_args(int rc, const A& a, const std::vector<R>& rows) {
+    Fnv f;
+    f.v(rc);
+    f.bytes(&a, sizeof a);
+    f.v(rows.size());
+    f.bytes(rows.data(), rows.size() * sizeof(R));
+    return f.h;
+}
+template <bool WIDE>
+static void tiled_args_line(const std::string& head, const Plan& plan, int esize, const TiledVariant& tv) {
+    TiledBuild<WIDE> b;
+    const int rc = build_tiled_args<WIDE>(plan, esize, tv, b);
+    const std::string form = std::string("tiled ") + (WIDE ? "wide" : "narrow") + (tv.V > 1 ? " V>1" : " V=1") + " mode=" + std::to_string(tv.mode);
+    std::printf("%s | %s V=%d rc=%d | %016llx\n", head.c_str(), form.c_str(), tv.V, rc, (unsigned long long)digest_args(rc, b.a, b.rows));
+    if (!rc) ++form_counts[form];
+}
+static void args_lines(const std::string& head, const Plan& plan) {
+    const Canon& c = plan.c;
+    if (plan.family == FAM_TILED) {
+        const int esize = c.bitcopy ? c.esize[0] : dtype_size(c.ct);
+        const TiledVariant tv = tiled_variant(plan, nullptr, esize, c.mixed && !c.bitcopy);
+        if (tv.wide) tiled_args_line<true>(head, plan, esize, tv);
+        else tiled_args_line<false>(head, plan, esize, tv);
+    } else if (plan.family == FAM_ORBIT) {
+        const int esize = dtype_size(c.ct);
+        for (int nin : {-1, c.M - 1}) {
+            OrbitVariant v;
+            const int vrc = orbit_variant(plan, nullptr, esize, nin, v);
+            if (vrc) {
+                std::printf("%s | variant nin=%d rc=%d | %s\n", head.c_str(), nin, vrc, last_error.c_str());
+                continue;
+            }
+            std::printf("%s | variant nin=%d V=%d nrep=%d ng=%d own0=%d pipe=%d pair=%d\n", head.c_str(), nin, v.V, v.nrep, v.ng, (int)v.own0, (int)v.pipe, (int)v.pair);
+            if (nin >= 0 && !v.pair) continue;  // the one-orbit form again
+            OrbitBuild b;
+            const int rc = v.pair ? build_pair_args(plan, esize, b) : build_orbit_args(plan, esize, v, b);
+            std::printf("%s | orbit %s rc=%d | %016llx\n", head.c_str(), v.pair ? "pair" : "one", rc, (unsigned long long)digest_args(rc, b.a, b.rows));
+            if (rc) continue;
+            if (v.pair) {
+                ++form_counts["orbit pair"];
+            } else {
+                ++form_counts[v.ng == 2 ? "orbit ng=2" : "orbit ng=4"];
+                ++form_counts[v.own0 ? "orbit own0=1" : "orbit own0=0"];
+                if (v.V == 1 && esize < 16) ++form_counts["orbit V=1"];
+            }
+        }
+    }
+}
+
 // the TILED work list of the problem when one more option is set (empty: no list, or another family)
 static std::vector<uint32_t> list_with(const smr_problem& p, i64 Options::*field, i64 value) {
     const Options saved = options();
@@ -189,6 +262,7 @@ static void plan_all(const std::string& id, const smr_problem& p, int var = ONE)
         const int rc = make_plan(&p, plan);
         if (rc) std::printf("%s opt=%s rc=%d\n", id.c_str(), os.name, rc);
         else std::printf("%s opt=%s | %s | %016llx\n", id.c_str(), os.name, plan.desc.c_str(), (unsigned long long)digest(plan));
+        if (!rc) args_lines("args " + id + " opt=" + os.name, plan);
         ++lines;
         ++var_lines[var];
         const OrbitPlan& o = plan.orbit;
@@ -700,6 +774,11 @@ int main() {
     };
     for (int i = 0; i < C_COUNT; ++i) report(cname[i], counts[i]);
     for (int v = ONE; v <= STEPPED; ++v) report(var_name[v], var_lines[v]);
+    for (const char* form : form_need) {
+        const long n = form_counts[form];
+        std::fprintf(stderr, "  args %s: %ld%s\n", form, n, n < form_min ? "  -- TOO FEW: the corpus no longer reaches this form of the argument builders" : "");
+        if (n < form_min) rc = 1;
+    }
     std::fprintf(stderr, "%ld group lines, %ld accepted or refused against the recipe's word\n", glines, gwrong);
     if (gwrong) rc = 1;
     for (int i = 0; i < S_COUNT; ++i) {
