@@ -300,6 +300,10 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
             Range r{0, 0, i, k == 0};
             operand_span(c, k, c.base[k], r.lo, r.hi);
             (r.write ? wr : rd).emplace_back(r.lo, r.hi);
+            // a contraction accumulates into its destination unless the initop replaces the old value: the footprint then says
+            // that it is read (like footprint() in smr_api.cpp for every reduction), so that a recorded group acquires what the
+            // sequence wrote there
+            if (r.write && contraction && c.initop != SMR_INIT_ZERO && c.initop != SMR_INIT_CONST) rd.emplace_back(r.lo, r.hi);
             if (!independent) ranges.push_back(r);
         }
         // a map member takes its workgroups here; a contraction's depend on the tile, which contract_finish picks for the whole group

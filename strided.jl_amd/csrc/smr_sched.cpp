@@ -185,8 +185,16 @@ void order_packets(const std::vector<SchedExec>& ex, const SchedKnobs& knobs, co
     const int nq = out.nq;
     const std::vector<int>&comp = out.comp, &cslices = cs.slices, &cqueue = cs.queue;
     // 5. packets + ordering inside each queue: a launch that conflicts with none of the launches since the queue's last ordered one
-    //    goes out without the barrier bit.  The decisions are those of the SECOND of two simulated replays (steady state: the first
-    //    launch of a replay is judged against the tail of the previous replay on the same queue).
+    //    (its window) goes out without the barrier bit.  A replay follows the previous one in the queue, so the window of a replay's
+    //    first launches is the tail of the previous replay UNDER THE BITS CHOSEN.  Two steps:
+    //    (a) a starting decision: the bits of the second of two simulated replays.  The first simulated replay opens with a forced
+    //        barrier, so its last barrier can stand later than the chosen bits put it, and the window (a) judges the head of the
+    //        list against can be smaller than the real one;
+    //    (b) the closure: two replays are walked with the bits held fixed and the true window kept (the executions since the last set
+    //        bit, over the replay boundary: once the first replay has been walked the window is the one of every later replay).  A free
+    //        launch that conflicts with its window gets the bit and the walk starts again, until a whole walk changes nothing.  Every
+    //        round sets a bit, so there are at most as many rounds as executions; bits are only added, so a decision of (a) that was
+    //        sound stays as it was.
     // which executions read something the sequence writes (their packets acquire; everything else reads only data that is constant
     // for the whole replay and was made visible by the first packet's system-scope acquire)
     out.acquire.assign(ni, 0);
@@ -194,38 +202,66 @@ void order_packets(const std::vector<SchedExec>& ex, const SchedKnobs& knobs, co
     for (size_t i = 0; i < ni; ++i)
         for (size_t j = 0; j < ni && !raw[i]; ++j)
             if (overlaps(ex[j].wr, ex[i].rd)) raw[i] = 1;
+    auto conflict = [&](size_t a, size_t b) {
+        return overlaps(ex[a].rd, ex[b].wr) || overlaps(ex[a].wr, ex[b].wr) || overlaps(ex[a].wr, ex[b].rd);
+    };
     out.queues.resize(nq);
     for (int k = 0; k < nq; ++k) {
-        Spans wrd, wwr;
-        for (int pass = 0; pass < 2; ++pass)
-            for (size_t i = 0; i < ni; ++i) {
-                const int c = comp[i];
-                if (k < cqueue[c] || k >= cqueue[c] + cslices[c]) continue;
-                const int ns = cslices[c], s2 = k - cqueue[c];
-                bool free_ = !(wrd.empty() && wwr.empty()) && !knobs.all_ordered;
-                if (free_) free_ = !overlaps(wrd, ex[i].wr) && !overlaps(wwr, ex[i].wr) && !overlaps(wwr, ex[i].rd);
-                if (!free_) {
-                    wrd.clear();
-                    wwr.clear();
+        std::vector<size_t> mine;  // the executions of this queue, in recorded order
+        for (size_t i = 0; i < ni; ++i)
+            if (k >= cqueue[comp[i]] && k < cqueue[comp[i]] + cslices[comp[i]]) mine.push_back(i);
+        const size_t nm = mine.size();
+        std::vector<char> free_(nm, 0);
+        {  // (a)
+            Spans wrd, wwr;
+            for (int pass = 0; pass < 2; ++pass)
+                for (size_t p = 0; p < nm; ++p) {
+                    const SchedExec& r = ex[mine[p]];
+                    bool f = !(wrd.empty() && wwr.empty()) && !knobs.all_ordered;
+                    if (f) f = !overlaps(wrd, r.wr) && !overlaps(wwr, r.wr) && !overlaps(wwr, r.rd);
+                    if (!f) {
+                        wrd.clear();
+                        wwr.clear();
+                    }
+                    wrd.insert(wrd.end(), r.rd.begin(), r.rd.end());
+                    wwr.insert(wwr.end(), r.wr.begin(), r.wr.end());
+                    free_[p] = f;
                 }
-                wrd.insert(wrd.end(), ex[i].rd.begin(), ex[i].rd.end());
-                wwr.insert(wwr.end(), ex[i].wr.begin(), ex[i].wr.end());
-                if (pass == 0) continue;
-                for (int j = 0; j < ex[i].nlaunch; ++j) {
-                    unsigned lo = 0, hi = j == 0 ? ex[i].grid : 0;
-                    if (ns > 1) slice_range(ex[i].grid, ns, s2, lo, hi);
-                    if (j == 0 && hi <= lo) continue;  // an empty slice (tiny grid)
-                    SchedEntry e;
-                    e.exec = (int)i;
-                    e.launch = j;
-                    e.slice = s2;
-                    e.lo = lo;
-                    e.hi = hi;
-                    e.barrier = j > 0 || !free_;  // later launches of one execution (folding passes) depend on the first
-                    e.acquire = j > 0 || raw[i] != 0;  // ... and read its partials
-                    out.queues[k].push_back(e);
-                }
+        }
+        for (bool changed = true; changed;) {  // (b)
+            changed = false;
+            std::vector<size_t> window;
+            for (size_t t = 0; t < 2 * nm && !changed; ++t) {
+                const size_t p = t % nm;
+                if (free_[p])
+                    for (size_t w : window)
+                        if (conflict(mine[w], mine[p])) {
+                            free_[p] = 0;
+                            changed = true;
+                            break;
+                        }
+                if (!free_[p] || ex[mine[p]].nlaunch > 1) window.clear();  // (a later launch of p always carries the bit)
+                window.push_back(p);
             }
+        }
+        for (size_t p = 0; p < nm; ++p) {
+            const size_t i = mine[p];
+            const int ns = cslices[comp[i]], s2 = k - cqueue[comp[i]];
+            for (int j = 0; j < ex[i].nlaunch; ++j) {
+                unsigned lo = 0, hi = j == 0 ? ex[i].grid : 0;
+                if (ns > 1) slice_range(ex[i].grid, ns, s2, lo, hi);
+                if (j == 0 && hi <= lo) continue;  // an empty slice (tiny grid)
+                SchedEntry e;
+                e.exec = (int)i;
+                e.launch = j;
+                e.slice = s2;
+                e.lo = lo;
+                e.hi = hi;
+                e.barrier = j > 0 || !free_[p];  // later launches of one execution (folding passes) depend on the first
+                e.acquire = j > 0 || raw[i] != 0;  // ... and read its partials
+                out.queues[k].push_back(e);
+            }
+        }
     }
 }
 }  // namespace
