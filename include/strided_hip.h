@@ -358,7 +358,7 @@ int smr_debug_kernarg_layout(const void* elf, size_t bytes, const char* symbol, 
 int smr_debug_canon_prog(const smr_problem* problem, uint8_t* code, int cap, int* nwraps, int* compute_class, int32_t* orig);
 /* Test hook, host-only: the replay scheduler of recorded sequences (csrc/smr_sched.cpp) on `nexec` synthetic executions.  Per
    execution i: nspans[2i], nspans[2i+1] = how many byte ranges it reads / writes; `spans` holds them all in that order as [lo, hi)
-   pairs; launches[5i..] = number of launches, grid of the first, first launch sliceable?, every launch self-released?, same_as (index
+   pairs; launches[5i..] = number of launches, grid of the first, first launch sliceable? (bit 1 set: a two-launch execution whose second launch folds the whole first one, SchedExec::fold_after), every launch self-released?, same_as (index
    of the first execution with the same plan and base pointers).  knobs = max_queues, slices, all_ordered, self_release_max_total,
    number of (component, slices) pairs in comp_slices.  Results: per_exec[4i..] = component, acquire, first queue, slices;
    totals[0..3] = components, sliced components, queues, cache_resident; *footprint = bytes of the union of all ranges;
@@ -406,7 +406,8 @@ int smr_plan_prepare(smr_plan* plan);
  * than 256 workgroups and a long reduced range); N >= 2 = N slices (clamped to the chunks) wherever a CONTRACT plan is made.
  * Option "contract_tile" (default 0 = the planner's rule; 16, 32 or 64; anything else: SMR_EINVAL) forces the tile of
  * single-call CONTRACT plans, split or not; a forced tile that does not fit "max_lds_bytes" refuses the family for the problem.
- * Contraction groups read neither option.                                                                             */
+ * Contraction groups read neither option: their tile is "group_contract_tile" and their split form "group_contract_split"
+ * (SPLIT CONTRACTION GROUPS below), whose slices are cut by the same arithmetic.                                         */
 int smr_plan_describe(const smr_plan* plan, char* buf, size_t buflen);
 /* Algorithmic bytes of one execution: every distinct operand footprint counted once
  * (SURVEY.md section 8d).                                                                 */
@@ -489,7 +490,8 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  *
  * CONTRACTION GROUPS.  When member 0 is a reduction the group is K outer-product reductions -- the generic mul! box
  * dest[i, j, rest] = op(initop(dest), op over k, q of f(in1[i, k, ..], in2[j, k, ..])) -- run as ONE launch of the grouped form of the
- * CONTRACT kernel (csrc/smr_k_gcontract.hip: LDS- and register-tiled, no partials, no scratch, no second launch).  Every member must
+ * CONTRACT kernel (csrc/smr_k_gcontract.hip: LDS- and register-tiled; no partials, no scratch and no second launch unless option
+ * "group_contract_split" splits a member, see SPLIT CONTRACTION GROUPS below).  Every member must
  * then be a reduction of that shape, whatever option "contract" says and whatever its size: once canonicalised it has exactly two
  * distinct inputs and no bit copy, at least two kept dims and one reduced dim, both inputs vary along the inner reduced dim, input 1
  * varies along a kept dim along which input 2 does not and the other way round, and neither input lies on the destination's buffer.
@@ -510,7 +512,44 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * smr_group_describe reads "family=group kind=contract members=K grid=G tile=<16|32> k=<chunk of the reduced dim> lds=<bytes>
  * f=<mul2|prog> op=<+|*|min|max|&||> jit=<0|1> bytes=<algorithmic bytes>[ independent=asserted]"; smr_group_layout reports form 2
  * for every member.  prepare, execute, destroy and smr_seq_add_group work as for map groups (a recorded contraction group is one
- * packet per replay and can be cut into block ranges).                                                                           */
+ * packet per replay and can be cut into block ranges).
+ *
+ * SPLIT CONTRACTION GROUPS.  Option "group_contract_split" (default 0; smr_group_create reads it for contraction groups only, like
+ * "group_contract_tile") cuts long reduced ranges over workgroups: a few blocks with small open legs and a very long contracted leg
+ * otherwise get a handful of workgroups.  0: never -- plans, describe(), layout() and launches are those of a library without the
+ * option.  N >= 2: every member's walk over its Q * nkc chunks (nkc = ceil(K / k)) is cut into N slices by the single call's
+ * arithmetic: N clamped to the chunks, cps = ceil(chunks / S), S = ceil(chunks / cps), no slice empty; a member left with one slice
+ * is an unsplit member.  1: the group rule -- only for a group whose unsplit plan has fewer than 256 workgroups; "contract_split"'s
+ * rule (slices of >= 2 chunks, <= 64 slices, the partials' round trip <= half the bytes the member's inputs move) bounds every
+ * member's slices, the tile is the largest allowed one on which the members' tiles * bounds reach 256 (else the one that allows the
+ * most), and with G the unsplit grid on it every member gets clamp(ceil(512 / G), 1, its bound) slices; a group in which no member
+ * can take two slices is not split.  Negative values and values above 2^31 - 1 are SMR_EINVAL in smr_set_option; a forced N whose
+ * slices need more than 2^31 - 1 workgroups is SMR_EINVAL and one whose partials exceed 2^31 bytes over the group SMR_EUNSUPPORTED
+ * (naming the limit) in smr_group_create; under the rule such a group simply is not split.
+ * A group with a split member is TWO launches.  Main launch: member i has tiles_i * S_i workgroups, the slice the slow digit; a
+ * workgroup of a split member (S_i >= 2) accumulates its slice from the neutral element and stores its register block -- compute-
+ * class values, no conversion, no conj, no initop; ragged tiles store all their lanes -- to the group's partials; a workgroup of an
+ * unsplit member (S_i == 1) finishes its outputs in this launch as in an unsplit group (a thousand small blocks next to two long
+ * ones do not go through the partials).  Fold launch: (tile / 16)^2 workgroups per tile of the split members only, one lane per
+ * output folds P_0 .. P_{S-1} in slice order and applies the member's own initop argument; it does not call f (natively compiled
+ * also when f is runtime-compiled).  ACCUMULATION ORDER of a split member: dest = op(initop(old), op(... op(P_0, P_1) ..., P_{S-1})),
+ * P_s sequential from the neutral element over slice s.  A member with S_i >= 2 is bit-identical to smr_mapreduce on that member
+ * alone under "contract" = 2, "contract_tile" = the group's tile and "contract_split" = S_i; a member with S_i == 1 is bit-identical
+ * to the single call under "contract" = 2, as in an unsplit group.
+ * The partials are owned by the group: smr_group_prepare or the first execution allocates them (sum over split members of tiles_i *
+ * S_i * tile^2 * compute-class element size), smr_group_destroy frees them after draining the device.  ONE buffer per group: two
+ * executions of one group in flight on different streams would share it -- that is the caller's problem, as for a split plan.  A run
+ * writes every partial it reads: nothing depends on what an earlier run left there.
+ * smr_group_describe appends " split=<members split> kparts=<max S_i> fold=second-launch fold_grid=<F> scratch=<bytes>" after
+ * "bytes=..." (before " independent=asserted") when at least one member is split; grid= is the main launch's grid.
+ * smr_group_layout stays at 4 values per member, "workgroups" being tiles_i * S_i.  smr_group_split_layout: per member 4 values --
+ * S_i, cps_i, first fold workgroup, fold workgroups; returns 4 * count and writes min(that, cap) values; returns 0 for map groups
+ * and groups without a split member.  smr_seq_add_group records a split group as its two launches inside ONE item (smr_seq_info still
+ * counts one item and one group): the fold carries the barrier bit and acquires, like the second launch of a split CONTRACT plan;
+ * the footprint other items are compared against stays the members' operands (the partials are private to the group).  Under
+ * "slices" = n (smr_seq_set; never automatically) the main launch of a split group that is a component of its own is cut into n
+ * block ranges of at least 64 workgroups each, like an unsplit group -- but the ranges go back to back onto the item's ONE queue and
+ * the fold follows them with the barrier bit, so it runs after all of them (no order across queues exists): n + 1 packets.       */
 typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
 #define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
@@ -521,6 +560,7 @@ int smr_group_describe(const smr_group* g, char* buf, size_t buflen);
 /* Sum of the members' algorithmic bytes (smr_plan_algorithmic_bytes). */
 int64_t smr_group_algorithmic_bytes(const smr_group* g);
 int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap);
+int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap);
 int smr_group_destroy(smr_group* g);
 
 /* Runtime compilation.  An `f` without a natively compiled functor is specialised the way
@@ -627,7 +667,8 @@ int smr_mapreduce_sharded_ex(const smr_problem* problem, uint32_t local_ops);
  *   Sharding: "allreduce_f64" (0; 1: Float32 / ComplexF32 sums cross the ranks as Float64).
  *   Groups: "group_max_bytes" (16 MiB: largest member, in algorithmic bytes, that a front end still defers into a group; read by the
  *     front ends only: setting it keeps the plan cache); "group_contract_tile" (0: the rule; 16 / 32 force the tile of contraction
- *     groups created afterwards: tests and measurements).
+ *     groups created afterwards: tests and measurements); "group_contract_split" (0: never; 1: the group rule; N >= 2: N slices
+ *     per member of contraction groups created afterwards; negative or above 2^31 - 1: SMR_EINVAL; keeps the plan cache).
  *   Debug builds with device-side wall-clock stamps (csrc/smr_device.h): "stamp_base" / "stamp_cap" /
  *     "stamp_used"; read-only "stamp_build".
  *   Read-only counters: "launches" (kernel launches the library issued, through HIP or directly),

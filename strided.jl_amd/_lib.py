@@ -82,7 +82,7 @@ EXPORTS = [
     "smr_comm_destroy", "smr_mapreduce_sharded", "smr_mapreduce_sharded_ex", "smr_shard", "smr_shard_ex", "smr_init_reduction", "smr_set_option",
     "smr_get_option", "smr_overlap_begin", "smr_overlap_end", "smr_overlap_fence", "smr_stream_create", "smr_stream_destroy",
     "smr_seq_create", "smr_seq_add", "smr_seq_add_group", "smr_seq_run", "smr_seq_wait", "smr_seq_info", "smr_seq_components", "smr_seq_fences", "smr_seq_set", "smr_seq_destroy", "smr_debug_kernarg_layout", "smr_debug_canon_prog", "smr_debug_seq_schedule",
-    "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_destroy",
+    "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_split_layout", "smr_group_destroy",
 ]
 
 
@@ -197,6 +197,8 @@ def load():
     lib.smr_group_algorithmic_bytes.restype = C.c_int64
     lib.smr_group_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_size_t]
     lib.smr_group_layout.restype = C.c_int64
+    lib.smr_group_split_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_size_t]
+    lib.smr_group_split_layout.restype = C.c_int64
     lib.smr_group_destroy.argtypes = [C.c_void_p]
     if lib.smr_abi_version() != 1:
         raise ImportError("libstrided_hip.so ABI version mismatch; rebuild")
@@ -214,6 +216,9 @@ def check(rc: int):
 
 
 def set_option(name: str, value: int):
+    """smr_set_option: the names are listed in include/strided_hip.h.  "group_contract_split" (0 = never, the default; 1 = the group
+    rule; N >= 2 = N slices per member; negative: SMR_EINVAL) is read by Group() for contraction groups only, like
+    "group_contract_tile": members with a long reduced range are cut into slices, folded by the group's second launch."""
     check(load().smr_set_option(name.encode(), int(value)))
 
 
@@ -477,7 +482,11 @@ class Group:
     A group whose member 0 is a reduction is a CONTRACTION group: every member is an outer-product reduction (the generic mul_
     box) with the f, op and initop kind of member 0 and a beta of its own; one launch of the grouped CONTRACT kernel, each member
     bit-identical to the single call under option "contract" = 2.  `member_scalars` is refused for it.  Option
-    "group_contract_tile" (0 = the rule, 16, 32) forces its tile.  See include/strided_hip.h."""
+    "group_contract_tile" (0 = the rule, 16, 32) forces its tile.  Option "group_contract_split" (0 = never, the default; 1 = the
+    group rule; N >= 2 = N slices per member, clamped to its chunks) cuts long reduced ranges over workgroups: the group is then
+    TWO launches through partials it owns (one buffer per group: do not run one group on two streams at once), and a split member
+    is bit-identical to the single call under "contract" = 2, "contract_tile" = the group's tile, "contract_split" = its slices.
+    See include/strided_hip.h."""
 
     def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False):
         self._lib = load()
@@ -508,6 +517,15 @@ class Group:
         n = int(self._lib.smr_group_layout(self._h, None, 0))
         buf = (C.c_int64 * max(1, n))()
         self._lib.smr_group_layout(self._h, buf, n)
+        v = list(buf)[:n]
+        return [tuple(v[i:i + 4]) for i in range(0, n, 4)]
+
+    def split_layout(self):
+        """Per member (slices S, chunks per slice, first fold workgroup, fold workgroups) of a contraction group with at least one
+        split member (option "group_contract_split"); [] for map groups and unsplit groups."""
+        n = int(self._lib.smr_group_split_layout(self._h, None, 0))
+        buf = (C.c_int64 * max(1, n))()
+        self._lib.smr_group_split_layout(self._h, buf, n)
         v = list(buf)[:n]
         return [tuple(v[i:i + 4]) for i in range(0, n, 4)]
 

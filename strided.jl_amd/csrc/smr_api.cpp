@@ -1026,6 +1026,11 @@ int smr_set_option(const char* name, int64_t value) {
         group_contract_tile() = value;
         return SMR_OK;
     }
+    if (n == "group_contract_split") {  // read by smr_group_create only, for contraction groups: no plan depends on it
+        if (value < 0 || value > 0x7fffffffLL) return set_error(SMR_EINVAL, "group_contract_split must be 0 (never), 1 (the group rule) or the number of slices to force per member");
+        group_contract_split() = value;
+        return SMR_OK;
+    }
     if (n == "contract_split" && value < 0) return set_error(SMR_EINVAL, "contract_split must be 0 (never), 1 (the rule) or the number of slices to force");
     if (n == "contract_tile" && value != 0 && value != 16 && value != 32 && value != 64) return set_error(SMR_EINVAL, "contract_tile must be 0 (the rule), 16, 32 or 64");
     if (i64 Options::*f = option_field(n)) o.*f = value;
@@ -1053,6 +1058,7 @@ int64_t smr_get_option(const char* name) {
     if (n == "stamp_build") return SMR_STAMP;
     if (n == "group_max_bytes") return group_max_bytes();
     if (n == "group_contract_tile") return group_contract_tile();
+    if (n == "group_contract_split") return group_contract_split();
     // read-only counters
     if (n == "launches") return g_launches.load();
     if (n == "jit_compiles") return jit_stats().compiles;

@@ -324,6 +324,33 @@ SMR_DEV void contract_by_op(A& a, const OpTab& ops, int redop, const F& f, T* ld
 }
 
 #ifndef SMR_JIT
+// The split form's arithmetic, shared by the single call's planner (smr_plan_contract.cpp) and the group planner
+// (smr_plan_group.cpp).  The constants are those of contract_split_rule, where the rows they were measured on are quoted.
+constexpr i64 CONTRACT_SPLIT_MIN_CPS = 2, CONTRACT_SPLIT_MAX_S = 64, CONTRACT_SPLIT_TARGET = 512;
+
+// Cuts a walk of `nchunks` chunks into at most `want` slices: clamped to the chunks, then cps = ceil(nchunks / S) and
+// S = ceil(nchunks / cps), so no slice is empty.  Returns S and sets `cps`; 1 (and cps = nchunks): the walk is not cut.
+inline i64 contract_slices(i64 nchunks, i64 want, i64& cps) {
+    i64 S = want < nchunks ? want : nchunks;
+    cps = nchunks;
+    if (S < 2) return 1;
+    const i64 per = (nchunks + S - 1) / S;
+    S = (nchunks + per - 1) / per;
+    if (S < 2) return 1;
+    cps = per;
+    return S;
+}
+
+// The most slices the rule allows a problem of `tiles` output tiles of edge `tile`: slices of at least MIN_CPS chunks, at most MAX_S
+// of them, and the partials' round trip (2 * tiles * tile^2 * es per slice) at most half the bytes the inputs move, (mi + nj) * K * Q * es
+inline i64 contract_split_smax(int es, i64 mi, i64 nj, i64 K, i64 Q, i64 nchunks, i64 tiles, i64 tile) {
+    const long double in_bytes = (long double)(mi + nj) * (long double)K * (long double)Q * es;
+    const long double per_slice = 2.0L * (long double)tiles * (long double)(tile * tile) * es;
+    i64 smax = nchunks / CONTRACT_SPLIT_MIN_CPS < CONTRACT_SPLIT_MAX_S ? nchunks / CONTRACT_SPLIT_MIN_CPS : CONTRACT_SPLIT_MAX_S;
+    const i64 by_bytes = (i64)(in_bytes / 2 / per_slice);
+    return smax < by_bytes ? smax : by_bytes;
+}
+
 // The tile-dependent part of the geometry: tiles along di / dj and chunks per outer reduced index, for elements of `es` bytes and
 // RB = rb.  Returns the problem's workgroups, nti * ntj * (the other kept extents), as plan_contract counts them.
 template <class A>

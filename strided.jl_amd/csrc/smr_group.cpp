@@ -1,8 +1,11 @@
 // smr_group.cpp -- grouped launches (include/strided_hip.h: smr_group_*): the C ABI and the launch path of a planned group.
 // smr_group_create checks its arguments and has the planner (smr_plan_group.cpp: plan_group) fill a GroupPlan; the device tables
 // (members, workgroup prefix sums, per-member scalars) are uploaded by smr_group_prepare or the first execution, and
-// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip).
+// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip) -- a contraction
+// group with split members (option "group_contract_split") as two, through partials the group owns.
+#include <algorithm>
 #include <cstdio>
+#include <iterator>
 #include <new>
 
 #include "smr_direct.h"
@@ -23,7 +26,8 @@ namespace {
 // the launcher of the group's kind in the object of compute class CT (a bit copy, never a contraction, goes through Float32's)
 template <int CT>
 int launch_group_in(const GroupPlan& g, hipStream_t s) {
-    return g.kind == GROUP_CONTRACT ? launch_group_contract_ct<CT>(g, s) : launch_group_ct<CT>(g, s);
+    if (g.kind == GROUP_CONTRACT) return g.contract.nsplit ? launch_group_contract_split_ct<CT>(g, s) : launch_group_contract_ct<CT>(g, s);
+    return launch_group_ct<CT>(g, s);
 }
 
 int launch_group(const GroupPlan& g, hipStream_t s) {
@@ -42,7 +46,18 @@ int ensure_tables(const GroupPlan& g) {
     const auto upload = [](void** dst, std::pair<const void*, size_t> t, const char* what) { return *dst ? SMR_OK : upload_table(dst, t.first, t.second, what); };
     if (int rc = upload(&g.d_members, g.member_table(), "group members")) return rc;
     if (int rc = upload(&g.d_first, GroupPlan::bytes_of(g.first_wg), "group workgroup ranges")) return rc;
-    return g.map.varc ? upload(&g.map.d_consts, GroupPlan::bytes_of(g.map.consts), "group member scalars") : SMR_OK;
+    if (g.map.varc)
+        if (int rc = upload(&g.map.d_consts, GroupPlan::bytes_of(g.map.consts), "group member scalars")) return rc;
+    if (g.contract.nsplit) {  // the split form's tables and the group's partials: one buffer per group, every element of which a run
+                              // writes (main launch) before it reads it (fold): nothing an earlier run left there is ever read
+        if (int rc = upload(&g.contract.d_split, GroupPlan::bytes_of(g.contract.split), "group slices")) return rc;
+        if (int rc = upload(&g.contract.d_fold_first, GroupPlan::bytes_of(g.contract.fold_first), "group fold ranges")) return rc;
+        if (!g.contract.d_partials) {
+            const hipError_t e = hipMalloc(&g.contract.d_partials, g.contract.scratch_bytes);
+            if (e != hipSuccess) return hip_error(e, "hipMalloc(group partials)");
+        }
+    }
+    return SMR_OK;
 }
 
 }  // namespace
@@ -126,10 +141,23 @@ int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap) {
     return (int64_t)(4 * n);
 }
 
+int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap) {
+    if (!g || !g->plan.contract.nsplit) return 0;
+    const GroupContractPlan& cp = g->plan.contract;
+    const size_t n = cp.split.size();
+    if (out)
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t v[4] = {cp.split[i].S, cp.split[i].cps, cp.fold_first[i], (int64_t)cp.fold_first[i + 1] - (int64_t)cp.fold_first[i]};
+            for (size_t j = 0; j < 4; ++j)
+                if (4 * i + j < cap) out[4 * i + j] = v[j];
+        }
+    return (int64_t)(4 * n);
+}
+
 int smr_group_destroy(smr_group* g) {
     if (!g) return SMR_OK;
-    void* const tables[] = {g->plan.d_members, g->plan.d_first, g->plan.map.d_consts};
-    if (tables[0] || tables[1] || tables[2]) {
+    void* const tables[] = {g->plan.d_members, g->plan.d_first, g->plan.map.d_consts, g->plan.contract.d_split, g->plan.contract.d_fold_first, g->plan.contract.d_partials};
+    if (std::any_of(std::begin(tables), std::end(tables), [](void* t) { return t != nullptr; })) {
         (void)eager_fence_if_active();
         (void)hipDeviceSynchronize();  // a queued launch may still read the tables
         for (void* t : tables)

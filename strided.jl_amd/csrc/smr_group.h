@@ -44,15 +44,27 @@ struct GroupContractMemberD {
     i64 nti, ntj, K, Q, nkc;
 };
 
+// The split form of a contraction group (option "group_contract_split"; smr_k_gcontract.hip): how member i's chunk walk is cut, one
+// entry per member in a table of its own next to the member table.  S == 1: the member is not split and runs the unsplit body.
+struct GroupSplitD {
+    i64 part_off;                // first element of the member's partials in the group's buffer (compute-class elements)
+    i64 cps;                     // chunks per slice
+    uint32_t S;                  // slices
+    uint32_t tiles;              // output tiles: the member's workgroups in the main launch are tiles * S, the slice the slow digit
+};
+
 // The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
 // space they are fetched by scalar loads into scalar registers, not once per lane.
 typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
 typedef const GroupContractMemberD __attribute__((address_space(4))) GroupContractMemberC;
+typedef const GroupSplitD __attribute__((address_space(4))) GroupSplitC;
 typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
 typedef const double __attribute__((address_space(4))) GroupConstC;
 
 // The member of workgroup `b` of the group: the last one whose first workgroup is <= b (first_wg[]: count + 1 prefix sums of the
-// members' workgroups; every member has at least one).
+// members' workgroups; every member has at least one in the main launch.  The fold launch of a split contraction group searches
+// its own prefix sums, in which unsplit members have none: equal neighbouring entries.  The loop keeps first_wg[lo] <= b <
+// first_wg[hi], so it ends on the one member whose range is not empty and holds b).
 SMR_DEV int group_member_of(GroupWordC* first_wg, int count, uint32_t b) {
     int lo = 0, hi = count;
     while (hi - lo > 1) {
@@ -85,6 +97,14 @@ struct GroupMapPlan {  // GROUP_MAP only
 struct GroupContractPlan {  // GROUP_CONTRACT only
     std::vector<GroupContractMemberD> members;
     int rb = 1;  // one tile size (16 * rb) for the whole launch
+    // the split form (option "group_contract_split"): empty / 0 unless at least one member is split
+    std::vector<GroupSplitD> split;        // one entry per member
+    std::vector<uint32_t> fold_first;      // count + 1 prefix sums of the members' workgroups in the fold launch (rb^2 per tile of a split member)
+    int nsplit = 0, max_s = 0;             // members with S >= 2, the largest S
+    size_t scratch_bytes = 0;              // the group's partials: sum over split members of tiles * S * tile^2 * element size
+    mutable void* d_split = nullptr;       // device copies, and the partials buffer (one per group)
+    mutable void* d_fold_first = nullptr;
+    mutable void* d_partials = nullptr;
 };
 
 // A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
@@ -118,10 +138,12 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
 
 template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);           // smr_k_group.hip
 template <int CT> int launch_group_contract_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip
+template <int CT> int launch_group_contract_split_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip compiled with -DSMR_GCONTRACT_SPLIT
 
 int ensure_device();         // smr_api.cpp
 i64& group_max_bytes();      // option "group_max_bytes" (smr_group.cpp)
 i64& group_contract_tile();  // option "group_contract_tile": 0 = the planner's rule, 16 / 32 force the tile of contraction groups
+i64& group_contract_split(); // option "group_contract_split": 0 = never, 1 = the group rule, N >= 2 force N slices per member (smr_plan_group.cpp)
 
 // Bounding byte range [lo, hi) of operand k of a canonical problem: what footprint() (smr_api.cpp) and the group planner compare.
 inline void operand_span(const Canon& c, int k, const void* base, uintptr_t& lo_out, uintptr_t& hi_out) {

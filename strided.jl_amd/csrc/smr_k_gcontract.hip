@@ -16,7 +16,21 @@
 // ACCUMULATION ORDER: the single call's.  One lane owns each output, starting from the neutral element, q ascending and inside it k
 // ascending, the init-ed old destination combined last -- whatever the tile.  A member's result is bit-identical to the single
 // call's on that member alone.  No partials, no scratch, one launch.
-// Compiled once per compute type (-DSMR_CT=n).
+//
+// SPLIT FORM (option "group_contract_split", off by default; smr_plan_group.cpp: contract_group_rule): a few members with small open
+// legs and a very long reduced range.  Member i's chunk walk is cut into S_i slices of cps_i chunks by the single call's arithmetic
+// (smr_contract.h: contract_slices) and the member has tiles_i * S_i workgroups in the main launch, the slice the slow digit as in
+// contract_split_body.  A workgroup of a split member (S_i >= 2) runs the tile body over its slice from the neutral element and
+// stores its register block -- compute-class values, no conversion, no conj, no initop; ragged tiles store all their lanes -- to the
+// group's partials at part_off_i + (tile * S_i + slice) * RB^2 * 256; a workgroup of an unsplit member (S_i == 1) runs the body above
+// and finishes its outputs in this launch.  The branch is on the member: wave-uniform.  k_group_contract_fold, the grouped form of
+// k_contract_fold, then runs RB^2 workgroups per tile of the split members only (a second prefix table, searched by the same
+// group_member_of), one lane per output: P_0 .. P_{S-1} folded in slice order, the result through the epilogue with the member's beta.
+// ACCUMULATION ORDER of a split member: the split single call's, dest = op(initop(old), op(... op(P_0, P_1) ..., P_{S-1})) -- bit-
+// identical to the single call on that member under contract = 2, contract_tile = the group's tile, contract_split = S_i.
+// Compiled once per compute type (-DSMR_CT=n), and a second time with -DSMR_GCONTRACT_SPLIT: the split form's two kernels and their
+// entry point in objects of their own, so that k_group_contract's code objects are those of the library before the split form
+// (kernels added to a translation unit change the register allocation of the ones it held: profiles/contract_split.txt).
 #include "smr_contract.h"
 #include "smr_group.h"
 
@@ -46,6 +60,8 @@ SMR_DEV void group_contract_body(const GroupContractArgs a, F f) {
     GroupWordC* const first_wg = (GroupWordC*)a.first_wg;
     const int lo = group_member_of(first_wg, a.count, b);
     GroupContractMemberC& m = ((GroupContractMemberC*)a.members)[lo];
+    // (not group_contract_optab below: this body is left textually as it was, so that k_group_contract's code objects stay the ones
+    // of the library before the split form)
     OpTab t;
 #pragma unroll
     for (int k = 0; k < MAXM; ++k) {
@@ -62,7 +78,57 @@ SMR_DEV void group_contract_body(const GroupContractArgs a, F f) {
     contract_by_op<T, F, MIXED, RB, false>(m, t, a.redop, f, lds, (i64)(b - first_wg[lo]), 0, m.Q * m.nkc, (T*)nullptr);
 }
 
+// the split form's arguments: the unsplit ones first (wg0 keeps its kernarg offset), the tables of the split form, the partials
+struct GroupContractSplitArgs {
+    GroupContractArgs g;
+    const GroupSplitD* split;      // count entries
+    const uint32_t* fold_first;    // count + 1 prefix sums of the fold launch's workgroups
+    void* partials;
+};
+
+// the operand table of member `m` in registers
+SMR_DEV OpTab group_contract_optab(GroupContractMemberC& m, const GroupContractArgs& a) {
+    OpTab t;
+#pragma unroll
+    for (int k = 0; k < MAXM; ++k) {
+        t.base[k] = nullptr;
+        t.dtype[k] = 0;
+        t.conj[k] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t.base[k] = m.base[k];
+        t.dtype[k] = a.dtype[k];
+        t.conj[k] = a.conj[k];
+    }
+    return t;
+}
+
+// The split form's main launch: workgroup w of member i is (tile = w % tiles_i, slice = w / tiles_i) when S_i >= 2, tile w otherwise.
+template <class T, class F, bool MIXED, int RB>
+SMR_DEV void group_contract_split_body(const GroupContractSplitArgs a, F f) {
+    typedef CGeom<T, RB> G;
+    __shared__ __attribute__((aligned(16))) T lds[2 * 2 * G::TK * G::LD];
+    const uint32_t b = blockIdx.x + a.g.wg0;
+    GroupWordC* const first_wg = (GroupWordC*)a.g.first_wg;
+    const int lo = group_member_of(first_wg, a.g.count, b);
+    GroupContractMemberC& m = ((GroupContractMemberC*)a.g.members)[lo];
+    GroupSplitC& sp = ((GroupSplitC*)a.split)[lo];
+    const OpTab t = group_contract_optab(m, a.g);
+    const i64 w = (i64)(b - first_wg[lo]), nchunks = m.Q * m.nkc;
+    const i64 S = (i64)sp.S;
+    if (S < 2) {  // (wave-uniform: sp is the member's)
+        contract_by_op<T, F, MIXED, RB, false>(m, t, a.g.redop, f, lds, w, 0, nchunks, (T*)nullptr);
+        return;
+    }
+    const i64 tiles = (i64)sp.tiles, sl = w / tiles, tile = w - sl * tiles;
+    const i64 t_lo = sl * sp.cps, t_hi = t_lo + sp.cps < nchunks ? t_lo + sp.cps : nchunks;
+    T* sink = (T*)a.partials + sp.part_off + (tile * S + sl) * (i64)(RB * RB * 256);
+    contract_by_op<T, F, MIXED, RB, true>(m, t, a.g.redop, f, lds, tile, t_lo, t_hi, sink);
+}
+
 #ifndef SMR_JIT
+#ifndef SMR_GCONTRACT_SPLIT
 template <class T, class F, bool MIXED, int RB>
 __global__ void __launch_bounds__(256) k_group_contract(GroupContractArgs a, F f) {
     group_contract_body<T, F, MIXED, RB>(a, f);
@@ -108,6 +174,113 @@ int launch_group_contract_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
     if (c.fkind == FK_MUL2) return go_gc<T, FMul2<T>, false>(g, s, FMul2<T>{});
     return with_prog<T>(c, [&](auto f) { return go_gc<T, decltype(f), false>(g, s, f); });
 }
+#else  // SMR_GCONTRACT_SPLIT
+template <class T, class F, bool MIXED, int RB>
+__global__ void __launch_bounds__(256) k_group_contract_split(GroupContractSplitArgs a, F f) {
+    group_contract_split_body<T, F, MIXED, RB>(a, f);
+}
+
+// The split form's second launch, the grouped form of k_contract_fold: workgroup w of split member i is (register = w % RB^2, tile =
+// w / RB^2); one lane per (tile, register, lane) of the main launch folds that output's S_i partials in slice order, acc = P_0; acc =
+// op(acc, P_s) for s = 1 .. S_i - 1, and puts the result through the epilogue with the member's own beta; lanes past the end of a
+// ragged tile drop theirs.  It does not call f.  Eight partials are loaded (index clamped, never guarded) before the first is used.
+template <class T, bool MIXED, int RB>
+__global__ void __launch_bounds__(256) k_group_contract_fold(GroupContractSplitArgs a) {
+    typedef CGeom<T, RB> G;
+    const uint32_t b0 = blockIdx.x;
+    GroupWordC* const fold_first = (GroupWordC*)a.fold_first;
+    const int lo = group_member_of(fold_first, a.g.count, b0);
+    GroupContractMemberC& g = ((GroupContractMemberC*)a.g.members)[lo];
+    GroupSplitC& sp = ((GroupSplitC*)a.split)[lo];
+    const OpTab t = group_contract_optab(g, a.g);
+    i64 b = (i64)(b0 - fold_first[lo]);
+    const int reg = (int)(b % (RB * RB));
+    b /= RB * RB;
+    const int kparts = (int)sp.S;
+    const T* p = (const T*)a.partials + sp.part_off + b * kparts * (i64)(RB * RB * 256) + reg * 256 + (int)threadIdx.x;
+    const i64 bi = b % g.nti;
+    b /= g.nti;
+    const i64 bj = b % g.ntj;
+    b /= g.ntj;
+    i64 off0 = 0;
+#pragma nounroll
+    for (int n = 0; n < g.nrd; ++n) {
+        const int d = g.rdim[n];
+        const i64 x = b / g.dims[d], cd = b - x * g.dims[d];
+        b = x;
+        off0 += cd * g.strides[0][d];
+    }
+    const int li = (int)threadIdx.x & (CONTRACT_LANES - 1), lj = (int)threadIdx.x >> 4;
+    const i64 i = bi * G::TILE + G::idx(li, reg / RB), j = bj * G::TILE + G::idx(lj, reg % RB);
+    if (i >= g.dims[g.di] || j >= g.dims[g.dj]) return;
+    constexpr i64 SL = RB * RB * 256;  // elements between the slices of one tile
+    const int last = kparts - 1;
+    T acc = p[0];
+    for (int s0 = 1; s0 <= last; s0 += 8) {
+        T x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = p[(i64)(s0 + e < last ? s0 + e : last) * SL];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const T v = red_apply<T>(a.g.redop, acc, x[e]);
+            if (s0 + e <= last) acc = v;
+        }
+    }
+    contract_epilogue<T, MIXED>(g, t, off0 + i * g.strides[0][g.di] + j * g.strides[0][g.dj], acc);
+}
+
+// the two launches of the split form: the members' (tile, slice) workgroups, then the fold (native: it does not call f)
+template <class T, class F, bool MIXED, int RB>
+static int launch_gcs(const GroupPlan& g, const GroupContractSplitArgs& a, hipStream_t s, F f) {
+    const unsigned grid = g.first_wg.back(), fold = g.contract.fold_first.back();
+    // a contiguous block range of the main launch is still self-contained (a workgroup writes its own outputs or its own partials):
+    // a recorded sequence cuts it under "slices" and puts the fold behind all ranges on the same queue (smr_sched.cpp, step 3c)
+    mark_sliceable(1, (unsigned)(offsetof(GroupContractSplitArgs, g) + offsetof(GroupContractArgs, wg0)), 0);
+    int rc;
+    if constexpr (is_jit<F>::value)
+        rc = launch_jit<T>(g.c, s, "gcontract", "smr::GroupContractSplitArgs", "group_contract_split_body", "", grid, 256, 0, a, MIXED, RB);
+    else
+        rc = launch_native(nullptr, 0, "k_group_contract_split", [&] { SMR_LAUNCH((k_group_contract_split<T, F, MIXED, RB>), dim3(grid), dim3(256), 0, s, a, f); });
+    if (rc || jit_no_launch()) return rc;
+    SMR_LAUNCH((k_group_contract_fold<T, MIXED, RB>), dim3(fold), dim3(256), 0, s, a);
+    return check_launch("k_group_contract_fold");
+}
+
+template <class T, class F, bool MIXED>
+static int go_gcs(const GroupPlan& g, hipStream_t s, F f) {
+    const Canon& c = g.c;
+    const GroupContractPlan& cp = g.contract;
+    // (a dry run compiles without a device: no tables and no partials yet, and nothing is launched)
+    if (!jit_dry_run() && (!g.d_members || !g.d_first || !cp.d_split || !cp.d_fold_first || !cp.d_partials))
+        return set_error(SMR_EINVAL, "split contraction group without its tables or its partials buffer");
+    GroupContractSplitArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.g.members = (const GroupContractMemberD*)g.d_members;
+    a.g.first_wg = (const uint32_t*)g.d_first;
+    a.g.count = (int32_t)cp.members.size();
+    a.g.wg0 = 0;
+    a.g.redop = c.redop;
+    for (int k = 0; k < 3; ++k) {
+        a.g.dtype[k] = c.dtype[k];
+        a.g.conj[k] = c.conj[k];
+    }
+    a.split = (const GroupSplitD*)cp.d_split;
+    a.fold_first = (const uint32_t*)cp.d_fold_first;
+    a.partials = cp.d_partials;
+    if (cp.rb == 2) return launch_gcs<T, F, MIXED, 2>(g, a, s, f);
+    if (cp.rb == 1) return launch_gcs<T, F, MIXED, 1>(g, a, s, f);
+    return set_error(SMR_EINVAL, "contraction group: no kernel for this tile");
+}
+
+template <>
+int launch_group_contract_split_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
+    typedef ct_type<SMR_CT>::type T;
+    const Canon& c = g.c;
+    if (c.mixed) return with_prog<T>(c, [&](auto f) { return go_gcs<T, decltype(f), true>(g, s, f); });
+    if (c.fkind == FK_MUL2) return go_gcs<T, FMul2<T>, false>(g, s, FMul2<T>{});
+    return with_prog<T>(c, [&](auto f) { return go_gcs<T, decltype(f), false>(g, s, f); });
+}
+#endif  // SMR_GCONTRACT_SPLIT
 #endif  // !SMR_JIT
 
 }  // namespace smr

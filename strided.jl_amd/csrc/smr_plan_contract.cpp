@@ -6,6 +6,7 @@
 // element of in2 m times, so REDUCE_PART (one use per load) runs it at a few per cent of the vector ALUs; this family stages a
 // TI x TK tile of in1 and a TJ x TK tile of in2 in LDS once per chunk and keeps an RB x RB block of outputs per lane in registers
 // (RB = 4, 2 or 1: 64 x 64, 32 x 32 or 16 x 16 tiles, by the number of workgroups they give).
+#include "smr_contract.h"
 #include "smr_plan.h"
 
 namespace smr {
@@ -72,11 +73,8 @@ static i64 contract_nchunks(const Canon& c, const ContractPlan& cp) {
 // Cuts the chunk walk of `cp` (its tile set) into at most `want` slices: clamped to the chunks, then cps = ceil(nchunks / S) and
 // S = ceil(nchunks / cps), so no slice is empty.  One slice, partials beyond 2^31 bytes or a grid beyond 2^31 - 1: left unsplit.
 static void contract_cut(const Canon& c, ContractPlan& cp, i64 want) {
-    const i64 nchunks = contract_nchunks(c, cp);
-    i64 S = std::min(want, nchunks);
-    if (S < 2) return;
-    const i64 cps = (nchunks + S - 1) / S;
-    S = (nchunks + cps - 1) / cps;
+    i64 cps = 0;
+    const i64 S = contract_slices(contract_nchunks(c, cp), want, cps);
     if (S < 2) return;
     const long double bytes = (long double)cp.grid * (long double)S * (long double)(cp.ti * cp.tj) * (long double)dtype_size(c.ct);
     if (bytes > 2147483648.0L || (long double)cp.grid * (long double)S > 2147483647.0L) return;
@@ -108,19 +106,16 @@ static void contract_cut(const Canon& c, ContractPlan& cp, i64 want) {
 //   the larger tile first: (64, 64, 65536) Float32 32 x 32 with 256 workgroups (c) 41.1 against 16 x 16 with 1024 workgroups 55.6
 //     (Float64 80.3 against 87.8; ComplexF64 the other way round, 162.6 against 133.1: the choice is not type-dependent here).
 static bool contract_split_rule(const Canon& c, ContractPlan& cp, const int* rbs, int nrb, i64 rest) {
-    constexpr i64 MIN_CPS = 2, MAX_S = 64, TARGET = 512;
+    // (the constants and the three bounds live in smr_contract.h: the group planner reads the same rule over a whole group)
+    constexpr i64 TARGET = CONTRACT_SPLIT_TARGET;
     const int es = dtype_size(c.ct);
     const i64 K = c.dims[c.NK], Q = c.total / c.nout / K;
-    const long double in_bytes = (long double)(c.dims[cp.di] + c.dims[cp.dj]) * (long double)K * (long double)Q * es;
     int best_rb = 0;
     i64 best_s = 0, best_wgs = 0;
     for (int n = 0; n < nrb; ++n) {
         ContractPlan t = cp;
         contract_set_plan_tile(c, t, rbs[n], rest);
-        const i64 nchunks = contract_nchunks(c, t);
-        const long double per_slice = 2.0L * (long double)t.grid * (long double)(t.ti * t.tj) * es;  // round trip of one slice's partials
-        i64 smax = std::min<i64>(MAX_S, nchunks / MIN_CPS);
-        smax = std::min<i64>(smax, (i64)(in_bytes / 2 / per_slice));
+        const i64 smax = contract_split_smax(es, c.dims[cp.di], c.dims[cp.dj], K, Q, contract_nchunks(c, t), t.grid, t.ti);
         if (smax < 2) continue;
         const i64 thr = rbs[n] == 4 ? 512 : 256;
         if (t.grid * smax >= thr) {

@@ -15,6 +15,7 @@
 namespace smr {
 
 i64& group_contract_tile() { static i64 v = 0; return v; }
+i64& group_contract_split() { static i64 v = 0; return v; }
 
 namespace {
 
@@ -219,6 +220,112 @@ void contract_member(GroupContractMemberD& m, const Canon& c, int di, int dj) {
     contract_fill(m, c, di, dj, contract_vec_of(c, di, dj, nullptr), 1);
 }
 
+// Every member's tiles, slices and workgroups on tile 16 * rb with want[i] slices asked for member i (the single call's slice
+// arithmetic, smr_contract.h: contract_slices; a member left with one slice is an unsplit member), and -- when at least one member
+// is split -- the tables of the split form: per member S, cps, tiles and the offset of its partials, and the fold launch's prefix sums
+// (rb^2 workgroups per tile of a split member, none for the others).  With no member split the plan is exactly the unsplit one.
+int contract_layout(GroupPlan& g, int es, int rb, const std::vector<i64>& want) {
+    GroupContractPlan& cp = g.contract;
+    const size_t count = cp.members.size();
+    const i64 tile2 = (i64)(CONTRACT_LANES * rb) * (CONTRACT_LANES * rb);
+    cp.rb = rb;
+    cp.split.assign(count, GroupSplitD{0, 0, 1, 0});
+    cp.fold_first.assign(count + 1, 0);
+    cp.nsplit = cp.max_s = 0;
+    g.first_wg.assign(count + 1, 0);
+    long double elems = 0;
+    i64 fold = 0;
+    for (size_t i = 0; i < count; ++i) {
+        GroupContractMemberD& m = cp.members[i];
+        const i64 tiles = contract_set_tile(m, es, rb);
+        GroupSplitD& sp = cp.split[i];
+        i64 cps = 0;
+        const i64 S = tiles > 0x7fffffffLL ? 1 : contract_slices(m.Q * m.nkc, want[i], cps);
+        if (S >= 2 && (i64)g.first_wg[i] + tiles * S > 0x7fffffffLL)
+            return set_error(SMR_EINVAL, member_tag((int)i) + ": group_contract_split: the slices need more than 2^31 - 1 workgroups");
+        if (int rc = assign_workgroups(g, (int)i, tiles * S)) return rc;
+        sp.S = (uint32_t)S;
+        sp.cps = cps;
+        sp.tiles = (uint32_t)tiles;
+        if (S >= 2) {
+            sp.part_off = (i64)elems;
+            elems += (long double)tiles * (long double)S * (long double)tile2;
+            fold += tiles * rb * rb;
+            if (elems * es > 2147483648.0L || fold > 0x7fffffffLL)
+                return set_error(SMR_EUNSUPPORTED, member_tag((int)i) + ": group_contract_split: the group's partials would exceed the limit of 2^31 bytes");
+            ++cp.nsplit;
+            cp.max_s = std::max(cp.max_s, (int)S);
+        }
+        cp.fold_first[i + 1] = (uint32_t)fold;
+    }
+    if (cp.nsplit == 0) {
+        std::vector<GroupSplitD>().swap(cp.split);
+        std::vector<uint32_t>().swap(cp.fold_first);
+    }
+    cp.scratch_bytes = (size_t)(elems * es);
+    return SMR_OK;
+}
+
+// group_contract_split = 1: the single call's contract_split_rule (smr_plan_contract.cpp; the constants and the three bounds on a
+// member's slices are shared with it, smr_contract.h) read over the whole group.  Only for a group whose unsplit plan, on the tile
+// `rb` the unsplit rule chose, has fewer than 256 workgroups.  Of the tiles allowed (32 then 16, those whose LDS fits `cap`; cap == 0:
+// the tile is forced, only `rb`) the largest on which the members' tiles * smax_i sum to at least 256, else the tile that allows the
+// most workgroups; smax_i < 2 counts as one slice, and a tile on which no member can take two slices is no candidate.  With G the
+// unsplit grid on that tile every member gets S_i = clamp(ceil(512 / G), 1, smax_i) slices.  False: the group is not split.
+// The constants were measured for single calls (profiles/contract_split.txt).  Measured for groups with
+// tools/group_contract_split_cases.py (profiles/group_contract_split.txt, MI355X; us per execution of the whole group, the unsplit
+// group -> the rule's group; the unsplit group's run-to-run spread is 0.1 - 1 us):
+//   every row the rule splits wins: 4 x (32, 32, 4096) Float64 118.66 -> 17.01 (32 x 32 tiles, 64 slices, 256 workgroups); 16 x (32,
+//     32, 4096) Float64 121.40 -> 21.56 (32 x 32, 32 slices, 512 workgroups); 16 x (16, 16, 65536) Float32 1083.66 -> 114.32 (32 x 32,
+//     32 slices).  No measured row that it splits loses, so no row is excluded and the constants stay the single call's;
+//   the larger tile first: 16 x (32, 32, 4096), 32 slices on 32 x 32 tiles 21.01 against 32 slices on 16 x 16 tiles 29.64;
+//   the gate (fewer than 256 unsplit workgroups) is conservative: the rows it leaves alone all have a forced form that wins -- 64 x
+//     (32, 32, 4096) Float64 122.99 -> 42.75 (S32 / 32 x 32), 16 x (64, 64, 4096) ComplexF64 328.14 -> 89.30, the group of 1000 x (32, 32,
+//     32) + 2 x (32, 32, 16384) 1047.25 -> 40.50 (S64 / 32 x 32), 64 x (64, 64, 4096) Float32 with exactly 256 workgroups 117.82 -> 89.64
+//     (S8 / 32 x 32).  A gate on the longest member's walk instead of the grid: not designed, not measured.
+bool contract_group_rule(const std::vector<GroupContractMemberD>& members, int es, i64 cap, int& rb, std::vector<i64>& want) {
+    std::vector<GroupContractMemberD> ms = members;  // (contract_set_tile writes the tile-dependent fields)
+    std::vector<i64> smax(ms.size());
+    i64 G = 0;  // the unsplit grid on the tile surveyed last
+    // every member's most slices on tile 16 * r; returns the sum of tiles * smax, 0 when no member can take two slices
+    auto survey = [&](int r) {
+        i64 W = 0;
+        bool any = false;
+        G = 0;
+        for (size_t i = 0; i < ms.size(); ++i) {
+            GroupContractMemberD& m = ms[i];
+            const i64 tiles = contract_set_tile(m, es, r);
+            smax[i] = std::max<i64>(1, contract_split_smax(es, m.dims[m.di], m.dims[m.dj], m.K, m.Q, m.Q * m.nkc, tiles, CONTRACT_LANES * r));
+            any = any || smax[i] >= 2;
+            G += tiles;
+            W += tiles * smax[i];
+        }
+        return any ? W : (i64)0;
+    };
+    (void)survey(rb);
+    if (G >= 256) return false;
+    int best = 0;
+    i64 best_w = 0;
+    for (int r = 2; r >= 1; r >>= 1) {
+        if (cap ? (i64)contract_lds(es, r) > cap : r != rb) continue;
+        const i64 W = survey(r);
+        if (W >= 256) {
+            best = r;
+            break;
+        }
+        if (W > best_w) {
+            best_w = W;
+            best = r;
+        }
+    }
+    if (!best) return false;
+    (void)survey(best);
+    const i64 s = (CONTRACT_SPLIT_TARGET + G - 1) / G;
+    for (size_t i = 0; i < ms.size(); ++i) want[i] = std::max<i64>(1, std::min(s, smax[i]));
+    rb = best;
+    return true;
+}
+
 // the group's tile, then every member's tiles and workgroups
 int contract_finish(GroupPlan& g) {
     i64 wgs32 = 0, outputs = 0;  // over the group: workgroups on 32 x 32 tiles, destination elements
@@ -241,10 +348,18 @@ int contract_finish(GroupPlan& g) {
     const i64 cap = std::min<i64>(options().max_lds_bytes, 65536);
     while (rb >= 1 && (i64)contract_lds(es, rb) > cap) rb >>= 1;
     if (rb < 1) return set_error(SMR_EUNSUPPORTED, "smr_group_create: the 16 x 16 tile of a contraction group does not fit max_lds_bytes");
-    g.contract.rb = rb;
-    for (size_t i = 0; i < g.contract.members.size(); ++i)
-        if (int rc = assign_workgroups(g, (int)i, contract_set_tile(g.contract.members[i], es, rb))) return rc;
-    return SMR_OK;
+    // the split form (opt-in: another accumulation order for the members it splits): forced slices on the tile chosen above, or the
+    // group rule, which picks tile and slices together
+    const i64 split = group_contract_split();
+    std::vector<i64> want(g.contract.members.size(), split >= 2 ? split : 1);  // slices asked for, per member
+    if (split == 1) {
+        const int rb0 = rb;
+        if (contract_group_rule(g.contract.members, es, force ? 0 : cap, rb, want) && contract_layout(g, es, rb, want) == SMR_OK) return SMR_OK;
+        rb = rb0;  // not split, or its partials or its grid are beyond the limits: the unsplit plan
+        (void)set_error(SMR_OK, std::string());  // (a limit's message is not this call's)
+        want.assign(want.size(), 1);
+    }
+    return contract_layout(g, es, rb, want);
 }
 
 void contract_describe(GroupPlan& g, uint32_t flags) {
@@ -253,11 +368,15 @@ void contract_describe(GroupPlan& g, uint32_t flags) {
     const bool native = !g.c.mixed && g.c.fkind == FK_MUL2;
     const int es = dtype_size(g.c.ct), rb = g.contract.rb;
     g.jit = options().jit && !native;
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "family=group kind=contract members=%zu grid=%u tile=%d k=%d lds=%zu f=%s op=%s jit=%d bytes=%lld%s", g.rank.size(), g.first_wg.back(),
+    char buf[256], split[160] = "";
+    // the split form: members split, the largest S, the fold launch's grid and the group's partials (grid= is the main launch's)
+    if (g.contract.nsplit)
+        std::snprintf(split, sizeof split, " split=%d kparts=%d fold=second-launch fold_grid=%u scratch=%zu", g.contract.nsplit, g.contract.max_s,
+                      g.contract.fold_first.back(), g.contract.scratch_bytes);
+    std::snprintf(buf, sizeof buf, "family=group kind=contract members=%zu grid=%u tile=%d k=%d lds=%zu f=%s op=%s jit=%d bytes=%lld", g.rank.size(), g.first_wg.back(),
                   CONTRACT_LANES * rb, contract_tk(es, rb), contract_lds(es, rb), native ? "mul2" : "prog", g.c.redop >= 0 && g.c.redop < 7 ? ops[g.c.redop] : "?",
-                  g.jit ? 1 : 0, (long long)g.algbytes, independent_tag(flags));
-    g.desc = buf;
+                  g.jit ? 1 : 0, (long long)g.algbytes);
+    g.desc = std::string(buf) + split + independent_tag(flags);
 }
 
 }  // namespace

@@ -72,6 +72,7 @@ namespace {
 // what schedule() knows about the dependency components: first execution, bytes touched (every view counted), slices, first queue
 struct Comps {
     std::vector<int> first, slices, queue;
+    std::vector<int> ranges;  // block ranges of a `fold_after` component on its ONE queue (1: not cut); such a component has slices == 1
     std::vector<size_t> bytes;
 };
 
@@ -142,6 +143,21 @@ int choose_slices(const std::vector<SchedExec>& ex, const SchedKnobs& knobs, con
                     cslices[c] = want[c];
                     ++nsliced;
                 }
+        // 3c. a component that is ONE two-launch execution whose second launch folds what the whole first one wrote (`fold_after`:
+        //     a split contraction group) is cut only when "slices" asks for it, and on its own queue: the ranges back to back, the
+        //     fold behind them with the barrier bit.  It takes no further queue, so it does not count against maxq.
+        for (int c = 0; c < ncomp; ++c) {
+            auto it = knobs.comp_slices.find(c);
+            const int ns = it != knobs.comp_slices.end() ? it->second : std::max(1, knobs.slices);
+            const SchedExec& r = ex[cfirst[c]];
+            bool ok = ns > 1 && r.fold_after && r.nlaunch == 2 && r.sliceable && r.grid >= (unsigned)(64 * ns);
+            for (size_t i = 0; i < ni && ok; ++i)
+                if (comp[i] == c && (int)i != cfirst[c]) ok = ex[i].same_as == r.same_as && ex[i].fold_after && ex[i].nlaunch == 2 && ex[i].grid == r.grid;
+            if (ok) {
+                cs.ranges[c] = ns;
+                ++nsliced;
+            }
+        }
     }
     return nsliced;
 }
@@ -246,6 +262,30 @@ void order_packets(const std::vector<SchedExec>& ex, const SchedKnobs& knobs, co
         }
         for (size_t p = 0; p < nm; ++p) {
             const size_t i = mine[p];
+            if (cs.ranges[comp[i]] > 1) {  // a cut `fold_after` execution: its ranges, then the fold, all on this queue
+                const int nr = cs.ranges[comp[i]];
+                bool first_range = true;
+                for (int s3 = 0; s3 < nr; ++s3) {
+                    SchedEntry e;
+                    e.exec = (int)i;
+                    e.launch = 0;
+                    e.slice = s3;
+                    slice_range(ex[i].grid, nr, s3, e.lo, e.hi);
+                    if (e.hi <= e.lo) continue;
+                    e.barrier = first_range ? !free_[p] : knobs.all_ordered;
+                    e.acquire = raw[i] != 0;
+                    first_range = false;
+                    out.queues[k].push_back(e);
+                }
+                SchedEntry e;
+                e.exec = (int)i;
+                e.launch = 1;
+                e.slice = 0;
+                e.lo = e.hi = 0;
+                e.barrier = e.acquire = true;
+                out.queues[k].push_back(e);
+                continue;
+            }
             const int ns = cslices[comp[i]], s2 = k - cqueue[comp[i]];
             for (int j = 0; j < ex[i].nlaunch; ++j) {
                 unsigned lo = 0, hi = j == 0 ? ex[i].grid : 0;
@@ -297,6 +337,7 @@ Schedule schedule(const std::vector<SchedExec>& ex, const SchedKnobs& knobs) {
         cs.bytes.assign(out.ncomp, 0);
         cs.slices.assign(out.ncomp, 1);
         cs.queue.assign(out.ncomp, 0);
+        cs.ranges.assign(out.ncomp, 1);
         for (size_t i = 0; i < ni; ++i) {
             cs.bytes[out.comp[i]] += bytes[i];
             if (cs.first[out.comp[i]] < 0) cs.first[out.comp[i]] = (int)i;
@@ -307,9 +348,14 @@ Schedule schedule(const std::vector<SchedExec>& ex, const SchedKnobs& knobs) {
     out.nq = assign_queues(maxq, cs);
     out.queue.resize(ni);
     out.nslices.resize(ni);
+    out.same_queue.assign(ni, 0);
     for (size_t i = 0; i < ni; ++i) {
         out.queue[i] = cs.queue[out.comp[i]];
         out.nslices[i] = cs.slices[out.comp[i]];
+        if (cs.ranges[out.comp[i]] > 1) {
+            out.nslices[i] = cs.ranges[out.comp[i]];
+            out.same_queue[i] = 1;
+        }
     }
     order_packets(ex, knobs, cs, out);
     return out;

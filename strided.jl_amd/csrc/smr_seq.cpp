@@ -164,6 +164,8 @@ int seq_record(smr_seq* q, std::vector<Rec>& recs, std::vector<SchedExec>& ex) {
         ex[i].sliceable = l0.slice_kind != 0;
         ex[i].all_self = true;
         for (const RecLaunch& l : recs[i].launches) ex[i].all_self = ex[i].all_self && l.self_released;
+        // a split contraction group: the partials' launch (sliceable) and the fold, which needs all of it
+        ex[i].fold_after = q->items[i].group != nullptr && ex[i].nlaunch == 2 && ex[i].sliceable;
     }
     return SMR_OK;
 }
@@ -197,7 +199,7 @@ int seq_kernargs(smr_seq* q, std::vector<Rec>& recs, const Schedule& sc) {
             const int ns = sc.nslices[i];
             for (int s2 = 0; s2 < ns; ++s2) {
                 unsigned lo = 0, hi = l.grid;
-                if (ns > 1) slice_range(l.grid, ns, s2, lo, hi);
+                if (ns > 1 && l.slice_kind != 0) slice_range(l.grid, ns, s2, lo, hi);  // (a launch that is not cut -- a fold behind a cut launch -- keeps its grid in every block)
                 unsigned char* b = host.data() + recs[i].offs[j] + (size_t)s2 * recs[i].blocksize(j);
                 // the hidden arguments carry this slice's block count
                 fill_kernarg_image(recs[i].refs[j], l, hi - lo, b, recs[i].blocksize(j));
@@ -288,7 +290,7 @@ int seq_build(smr_seq* q) {
         for (const SchedEntry& e : sc.queues[k]) {
             const Rec& r = recs[e.exec];
             const RecLaunch& l = r.launches[e.launch];
-            const unsigned nblocks = sc.nslices[e.exec] > 1 ? e.hi - e.lo : l.grid;
+            const unsigned nblocks = (sc.nslices[e.exec] > 1 && e.launch == 0) ? e.hi - e.lo : l.grid;  // (only a first launch is ever cut)
             if (nblocks == 0) continue;  // an empty launch
             SeqPacket sp;
             std::memset(&sp, 0, sizeof sp);
@@ -594,6 +596,7 @@ int smr_debug_seq_schedule(int nexec, const int32_t* nspans, const int64_t* span
         ex[i].nlaunch = l[0];
         ex[i].grid = (unsigned)l[1];
         ex[i].sliceable = l[2] != 0;
+        ex[i].fold_after = (l[2] & 2) != 0;  // (bit 1: a two-launch execution whose second launch folds the whole first one)
         ex[i].all_self = l[3] != 0;
         ex[i].same_as = l[4];
     }

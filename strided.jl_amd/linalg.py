@@ -20,6 +20,11 @@ Many small products (the blocks of a block-sparse contraction) share ONE launch 
 `with S.group(contract=True):` -- calls of `mul_` on matrices with the same alpha and the same kind of
 beta (0, 1, or anything else; the value is per call) are deferred and run as a contraction group
 (csrc/smr_k_gcontract.hip), each result bit-identical to the single call under "contract" = 2.
+`S.set_option("group_contract_split", 0 | 1 | N)` (default 0: never) is "contract_split" for those groups: a few blocks with small
+open legs and a very long contracted leg (an environment or projection step) get slices of that leg as workgroups of the one
+launch, and a second launch folds them in slice order (1 = the group rule, N >= 2 = N slices per member, clamped to its chunks).
+A split member is bit-identical to the single call under "contract" = 2, "contract_tile" = the group's tile and
+"contract_split" = its slices; the partials belong to the group (one buffer: not on two streams at once).
 """
 from __future__ import annotations
 

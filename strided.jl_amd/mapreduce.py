@@ -323,7 +323,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, forced contraction tile); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, (forced contraction tile, group_contract_split) or 0 for maps); least recently used first
 
 
 def _byte_range(a):
@@ -423,7 +423,10 @@ class group:
     of the grouped CONTRACT kernel (csrc/smr_k_gcontract.hip).  Their bucket key also holds the reduction's op, the kind of initop
     (zero / none / scale / const / ...: beta = 0, 1 and any other beta are three kinds) and the values of f's captured scalars (alpha)
     -- those always, whatever `member_scalars` says: a contraction group has one f.  beta itself is per member.  Each result is
-    bit-identical to the single call's under option "contract" = 2.  Without `contract=True` a reduction flushes and runs as usual.
+    bit-identical to the single call's under option "contract" = 2.  Option "group_contract_split" (0 never, 1 the group rule, N >= 2
+    slices per member) is read when a bucket is built, like "group_contract_tile": a bucket with split members is TWO launches (the
+    members' slices into partials the group owns, then the fold), and a split member is bit-identical to the single call under
+    "contract" = 2, "contract_tile" = the group's tile, "contract_split" = its slices.  Without `contract=True` a reduction flushes and runs as usual.
     `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
 
     MAX_PENDING = 4096
@@ -519,14 +522,14 @@ class group:
             self._launch(members, members[0].stream)
 
     def _launch(self, calls, stream):
-        # a bucket of contractions: the library is not passed member_scalars, and plans under the forced tile, if any
+        # a bucket of contractions: the library is not passed member_scalars, and plans under the forced tile and the split option
         if calls[0].op is not None:
-            scalars, tile = False, L.get_option("group_contract_tile")
+            scalars, plan_opts = False, (L.get_option("group_contract_tile"), L.get_option("group_contract_split"))
         else:
-            scalars, tile = self.member_scalars, 0
+            scalars, plan_opts = self.member_scalars, 0
         key = None
         if all(c.key is not None for c in calls):
-            key = (tuple(c.key for c in calls), self.independent, scalars, stream, tile)
+            key = (tuple(c.key for c in calls), self.independent, scalars, stream, plan_opts)
         grp = None
         if key is not None:
             try:

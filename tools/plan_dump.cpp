@@ -15,6 +15,8 @@
 // Before the groups, a section "split <id> ..." plans the generic product box with "contract_split" / "contract_tile" set: both outcomes
 // of the rule, every tile, forced slices, slices clamped to the chunks, a forced tile refused (`sneed`).  The sections before it plan
 // with both options at their defaults.
+// Behind the groups, a section "gsplit <id> ..." plans contraction groups under option "group_contract_split": the group rule's outcomes
+// (split, a forced tile, a mixed group, groups left alone), forced slices on both tiles, slices clamped to the chunks, and the option at 0.
 // Behind every TILED and ORBIT plan line come the launch arguments the family's pure builder makes for it (smr_plan_tiled_args.cpp,
 // smr_plan_orbit_args.cpp): "args <id> opt=<set> | <form> | <digest>" over the builder's status, the argument struct's bytes (pointers
 // null) and its tables -- TILED: the variant tiled_variant() names, struct and lane rows; ORBIT: "variant" lines with orbit_variant()'s
@@ -411,6 +413,48 @@ static void plan_one_group(const std::string& id, const std::vector<smr_problem>
     }
 }
 
+// Split contraction groups (option "group_contract_split"): "gsplit <id> | describe() | digest", the digest also over the tables of the
+// split form (per member S, cps, tiles and the partials' offset; the fold launch's prefix sums) and the scratch size.  Rows of their
+// own behind the group corpus: with the option at 0 every line above is the one of a tree without the option.
+static void plan_split_group(const std::string& id, const std::vector<smr_problem>& ms, i64 split, i64 tile = 0) {
+    const i64 saved_tile = group_contract_tile(), saved_split = group_contract_split();
+    group_contract_tile() = tile;
+    group_contract_split() = split;
+    GroupPlan g;
+    const int rc = plan_group(ms.data(), (int)ms.size(), 0, g);
+    group_contract_tile() = saved_tile;
+    group_contract_split() = saved_split;
+    if (rc) {
+        std::printf("gsplit %s | rc=%d | %s\n", id.c_str(), rc, last_error.c_str());
+        return;
+    }
+    Fnv f;
+    f.v(digest(g));
+    f.v(g.contract.split.size()); f.bytes(g.contract.split.data(), g.contract.split.size() * sizeof(GroupSplitD));
+    f.vec(g.contract.fold_first); f.v(g.contract.nsplit); f.v(g.contract.max_s); f.v(g.contract.scratch_bytes);
+    std::printf("gsplit %s | %s | %016llx\n", id.c_str(), g.desc.c_str(), (unsigned long long)f.h);
+}
+
+static void split_group_corpus() {
+    typedef std::vector<smr_problem> Ms;
+    Ms longs, mixed, small, full;
+    for (int i = 0; i < 16; ++i) longs.push_back(gmm(i, 32, 32, 4096));
+    for (int i = 0; i < 10; ++i) mixed.push_back(gmm(i, 32, 32, 32));
+    for (int i = 10; i < 12; ++i) mixed.push_back(gmm(i, 32, 32, 16384));
+    mixed.push_back(gmul(12, {33, 31, 3, 65, 3}, 3));   // ragged tiles, a batch dim, two reduced dims
+    for (int i = 0; i < 300; ++i) small.push_back(gmm(i, 32, 32, 32));
+    for (int i = 0; i < 64; ++i) full.push_back(gmm(i, 64, 64, 4096, SMR_F32));
+    plan_split_group("rule/16x(32,32,4096)", longs, 1);                 // the rule splits: 32 x 32 tiles, 32 slices each
+    plan_split_group("rule/16x(32,32,4096)/t16", longs, 1, 16);        // ... a forced tile stays
+    plan_split_group("rule/mixed", mixed, 1);                           // only the long members are split
+    plan_split_group("rule/300x(32,32,32)", small, 1);                  // left alone: 256 workgroups and more
+    plan_split_group("rule/64x(64,64,4096)f32", full, 1);               // left alone: 256 workgroups and more
+    plan_split_group("forced3/mixed/t16", mixed, 3, 16);
+    plan_split_group("forced64/mixed/t32", mixed, 64, 32);
+    plan_split_group("forced1000/16x(32,32,4096)", longs, 1000);        // clamped to the chunks
+    plan_split_group("off/mixed", mixed, 0);                            // the unsplit plan
+}
+
 static void group_corpus() {
     const uint32_t IND = SMR_GROUP_INDEPENDENT, OWN = SMR_GROUP_MEMBER_SCALARS;
     typedef std::vector<smr_problem> Ms;
@@ -763,6 +807,7 @@ int main() {
         }
     split_corpus();
     group_corpus();
+    split_group_corpus();
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     std::fprintf(stderr, "%ld lines:", lines);
     for (int f = 1; f < 9; ++f) std::fprintf(stderr, " %s=%ld", fam[f], fam_lines[f]);
