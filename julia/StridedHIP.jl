@@ -155,6 +155,9 @@ function emit!(p::Prog, x::Number)
     return typeof(x)
 end
 round32!(p::Prog, T) = (p.wide && T in NARROW && push!(p.code, OP_ROUND32, 0x00); T)
+# + - * / min max convert their arguments BEFORE operating (Float32[1] .+ Int32[16777217] == 16777216): an Int32 / UInt32 / Int64 / UInt64
+# argument of a Float32 / ComplexF32 operation gets its ROUND32 right behind its own code, which ends at p.code[at]
+roundarg!(p::Prog, f, at, Ta, T) = (p.wide && T in NARROW && Ta in (Int32, UInt32, Int64, UInt64) && f in (+, -, *, /, min, max) && splice!(p.code, at+1:at, (OP_ROUND32, 0x00)); nothing)
 valn(::Val{n}) where {n} = n
 function emit!(p::Prog, c::CaptureArgs)
     f, args = c.f, c.args
@@ -174,11 +177,12 @@ function emit!(p::Prog, c::CaptureArgs)
         T = emit!(p, args[1]); push!(p.code, UNARY_ALL[f], 0x00)
         return round32!(p, Base.promote_op(f, T))
     elseif haskey(BINARY_ALL, f) && (length(args) == 2 || f in (+, *, min, max))
-        T = emit!(p, args[1])                  # Julia's +(a,b,c,d) folds left
+        T = emit!(p, args[1]); at = length(p.code)   # Julia's +(a,b,c,d) folds left; `at`: where the left argument ends
         for a in args[2:end]
-            T = Base.promote_op(f, T, emit!(p, a))
+            Ta = emit!(p, a); Tn = Base.promote_op(f, T, Ta)
+            roundarg!(p, f, length(p.code), Ta, Tn); roundarg!(p, f, at, T, Tn); T = Tn   # (the right argument first: `at` stays valid)
             push!(p.code, BINARY_ALL[f], 0x00)
-            round32!(p, T)
+            round32!(p, T); at = length(p.code)
         end
         return T
     elseif f === ifelse && length(args) == 3

@@ -369,7 +369,11 @@ inline void store_as(void* base, i64 idx, int dt, T v) {
         case SMR_I32: ((int32_t*)base)[idx] = (int32_t)std::llrint((double)re); break;
         case SMR_U32: ((uint32_t*)base)[idx] = (uint32_t)std::llrint((double)re); break;
         case SMR_I64: ((int64_t*)base)[idx] = (int64_t)std::llrint((double)re); break;
-        case SMR_U64: ((uint64_t*)base)[idx] = (uint64_t)std::llrint((double)re); break;
+        case SMR_U64: {  // llrint saturates at 2^63: values of [2^63, 2^64) are integers already (spacing >= 2048), shifted down for the cast
+            double d = (double)re;
+            ((uint64_t*)base)[idx] = d >= 9223372036854775808.0 ? (uint64_t)(int64_t)(d - 9223372036854775808.0) + (1ull << 63) : (uint64_t)std::llrint(d);
+            break;
+        }
     }
     }
 }

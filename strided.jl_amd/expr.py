@@ -251,8 +251,10 @@ def node_dtype(n, arg_dtypes):
         strong = [t for t in ts[1:] if t is not None]
     if not strong:
         return None
-    r = np.result_type(*strong)
-    if n.op == "div" and not np.issubdtype(r, np.inexact):
+    # + - * / min max ifelse: both arguments are converted to Julia's promote_type (a float beats any integer: Float32 + Int64 is a
+    # Float32; Int32 + UInt32 is a UInt32) -- not NumPy's result_type, which widens until the type holds both
+    r = _jl_promote(*strong)
+    if n.op == "div" and r.kind not in "fc":
         r = np.dtype(np.float64)
     if r == np.bool_ and n.op in ("add", "sub", "mul"):
         r = np.dtype(np.int64)
@@ -277,6 +279,30 @@ def serialize(e: Expr, arg_dtypes=None, wide: bool = False):
         if node.op == "select":
             return False  # picks one of two already rounded values
         return node_dtype(node, arg_dtypes) in narrow
+
+    _F32_HOLDS_NOT = (np.dtype(np.int32), np.dtype(np.uint32), np.dtype(np.int64), np.dtype(np.uint64))
+
+    def narrow_parent(node) -> bool:
+        """Is `node` an operation Julia carries out in Float32 / ComplexF32 after converting its arguments (promotion), while the
+        call computes wider?"""
+        return wide and arg_dtypes is not None and isinstance(node, Call) and (node.op in ("add", "sub", "mul", "div", "min", "max")) \
+            and node_dtype(node, arg_dtypes) in narrow
+
+    def emit_arg(a, parent):
+        """An argument of `parent`.  Julia converts it to the operation's type BEFORE operating: an Int32 / UInt32 / Int64 / UInt64
+        value that Float32 does not hold is rounded there (`Float32[1] .+ Int32[16777217]` is 16777216, not the exact sum rounded
+        once), so a ROUND32 follows the argument; a weak integer literal is folded to Float32 on the host."""
+        if narrow_parent(parent):
+            if isinstance(a, Const):
+                integer = a.literal is not None if a.dtype is None else a.dtype in _F32_HOLDS_NOT
+                if integer and float(np.float32(a.value.real)) != a.value.real:
+                    code.extend((OPCODES["CONST"], const_index(complex(float(np.float32(a.value.real)), 0.0))))
+                    return
+            emit(a)
+            if not isinstance(a, Const) and node_dtype(a, arg_dtypes) in _F32_HOLDS_NOT:
+                code.extend((OPCODES["ROUND32"], 0))
+            return
+        emit(a)
 
     def const_index(v: complex) -> int:
         for i, c in enumerate(consts):
@@ -322,12 +348,14 @@ def serialize(e: Expr, arg_dtypes=None, wide: bool = False):
             else:
                 if len(node.args) < 2 or (len(node.args) > 2 and node.op not in _NARY_FOLD):
                     raise ValueError(f"{node.op} takes two arguments")
-                emit(node.args[0])
-                for a in node.args[1:]:
-                    emit(a)
-                    code.extend((OPCODES[_BINARY[node.op]], 0))
-                    if rounds(node):  # every step of a left fold has the fold's type
-                        code.extend((OPCODES["ROUND32"], 0))
+                if len(node.args) > 2:  # a left fold, typed step by step: +(i, j, a) is Float32(i + j) + a, (a32 + b32) + c64 rounds its first sum
+                    emit(Call(node.op, (Call(node.op, node.args[:-1]), node.args[-1])))
+                    return
+                emit_arg(node.args[0], node)
+                emit_arg(node.args[1], node)
+                code.extend((OPCODES[_BINARY[node.op]], 0))
+                if rounds(node):
+                    code.extend((OPCODES["ROUND32"], 0))
         else:
             raise TypeError(type(node))
 

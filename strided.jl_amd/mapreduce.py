@@ -119,6 +119,12 @@ _FPROG_CACHE: dict = {}
 _SCALARS = (int, float, complex, bool, np.generic, type(None))
 
 
+def _scalar_key(v):
+    """(type name, repr) of a captured scalar: `==` would merge 0.0 with -0.0 (and 1 with 1.0 and True), whose programs differ --
+    repr tells signed zeros apart, in both parts of a complex too."""
+    return (type(v).__name__, repr(v))
+
+
 def _code_names(code):
     """Global / attribute names read by a code object and by every code object nested in it."""
     names = set(code.co_names)
@@ -146,17 +152,18 @@ def _closure_key(f):
         from . import fn as _fn0
         if not all(isinstance(v, _SCALARS) or v is _fn0 for v in cells):
             return None
-        cells = tuple((type(v).__name__, "fn" if v is _fn0 else v) for v in cells)
+        cells = tuple(("module", "fn") if v is _fn0 else _scalar_key(v) for v in cells)
     defaults = f.__defaults__ or ()
     kwdefaults = tuple(sorted((f.__kwdefaults__ or {}).items()))
     if not all(isinstance(v, _SCALARS) for v in defaults) or not all(isinstance(v, _SCALARS) for _, v in kwdefaults):
         return None
+    kwdefaults = tuple((k, _scalar_key(v)) for k, v in kwdefaults)
     from . import fn as _fn
     g = f.__globals__
     for n in _code_names(code):
         if n in g and g[n] is not _fn:
             return None  # a module-level scalar, object or function the closure reads: may change between calls
-    return (code, cells, tuple((type(v).__name__, v) for v in defaults), kwdefaults)
+    return (code, cells, tuple(_scalar_key(v) for v in defaults), kwdefaults)
 
 
 def _serialized(f, M, dts):
@@ -666,10 +673,10 @@ def _fill_(out: StridedView, value):
 def _reduced_dtype(e, op, A):
     T = E.result_dtype(e, [A.dtype])
     if T == np.bool_ or (np.issubdtype(T, np.integer) and T.itemsize < 8):
-        # Base.add_sum / mul_prod widen Bool and small ints to Int (src/mapreduce.jl:62-64 via
-        # Base.mapreduce_first)
+        # Base.add_sum / mul_prod widen Bool and small signed ints to Int, small unsigned ints to UInt
+        # (src/mapreduce.jl:62-64 via Base.mapreduce_first)
         if _redop_code(op) in (L.SMR_RED_ADD, L.SMR_RED_MUL):
-            T = np.dtype(np.int64)
+            T = np.dtype(np.uint64) if T.kind == "u" else np.dtype(np.int64)
     if _redop_code(op) in (L.SMR_RED_AND, L.SMR_RED_OR):
         T = np.dtype(np.bool_)
     return T

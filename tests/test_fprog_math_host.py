@@ -119,6 +119,56 @@ def test_round32_follows_narrow_math_in_wide_calls():
     assert ser(lambda a: fn.tan(a), np.float32)[0] == [(OP["ARG"], 1), (OP["TAN"], 0)]  # a Float32 call: nothing to round
 
 
+def test_round32_follows_wide_integer_arguments_of_narrow_operations():
+    """+ - * / min max convert their arguments to the promoted type before they operate: an Int32 / UInt32 / Int64 / UInt64 argument of a
+    Float32 / ComplexF32 operation is rounded right behind the argument (Float32[1] .+ Int32[16777217] is 16777216), a weak integer
+    literal that Float32 does not hold is folded on the host.  Integers that Float32 holds (8 and 16 bits, Bool) and programs without such
+    arguments serialise as before."""
+    R, ARG, CONST = (OP["ROUND32"], 0), OP["ARG"], OP["CONST"]
+    for op, f in (("ADD", lambda a, b: a + b), ("SUB", lambda a, b: a - b), ("MUL", lambda a, b: a * b), ("DIV", lambda a, b: a / b),
+                  ("MIN", lambda a, b: fn.min(a, b)), ("MAX", lambda a, b: fn.max(a, b))):
+        for it in (np.int32, np.uint32, np.int64, np.uint64):
+            assert ser(f, np.float32, it)[0] == [(ARG, 1), (ARG, 2), R, (OP[op], 0), R], (op, it)
+            assert ser(f, it, np.float32)[0] == [(ARG, 1), R, (ARG, 2), (OP[op], 0), R], (op, it)
+        for it in (np.int8, np.uint8, np.int16, np.uint16, np.bool_):
+            assert ser(f, np.float32, it)[0] == [(ARG, 1), (ARG, 2), (OP[op], 0), R], (op, it)
+        assert ser(f, np.float64, np.int32)[0] == [(ARG, 1), (ARG, 2), (OP[op], 0)]      # a Float64 operation: Float64 holds every Int32
+    assert ser(lambda z, i: z * i, np.complex64, np.int32)[0] == [(ARG, 1), (ARG, 2), R, (OP["MUL"], 0), R]
+    # an integer-typed sub-expression as the argument: the Int32 sum is converted, its own arguments are not
+    assert ser(lambda i, j, a: (i + j) * a, np.int32, np.int32, np.float32)[0] == [(ARG, 1), (ARG, 2), (OP["ADD"], 0), R, (ARG, 3), (OP["MUL"], 0), R]
+    # an n-ary fold is typed step by step like Julia's +(a, b, c) = (a + b) + c: the Int32 sum is converted, not its terms; a Float32 step
+    # in front of a Float64 one is rounded; folds of one type serialise as before
+    assert ser(lambda i, j, a: fn.add(i, j, a), np.int32, np.int32, np.float32)[0] == [(ARG, 1), (ARG, 2), (OP["ADD"], 0), R, (ARG, 3), (OP["ADD"], 0), R]
+    assert ser(lambda a, b, c: fn.add(a, b, c), np.float32, np.float32, np.float64)[0] == [(ARG, 1), (ARG, 2), (OP["ADD"], 0), R, (ARG, 3), (OP["ADD"], 0)]
+    assert ser(lambda a, b, c, d: fn.max(a, b, c, d), *[np.float32] * 4, wide=True)[0][:-1] == \
+        [(ARG, 1), (ARG, 2), (OP["MAX"], 0), R, (ARG, 3), (OP["MAX"], 0), R, (ARG, 4), (OP["MAX"], 0), R]
+    assert ser(lambda a, b, c: fn.mul(a, b, c), *[np.float64] * 3)[0] == [(ARG, 1), (ARG, 2), (OP["MUL"], 0), (ARG, 3), (OP["MUL"], 0)]
+    # comparisons are mathematical, sqrt of an integer is a Float64: nothing is rounded
+    assert ser(lambda a, i: a < i, np.float32, np.int32)[0] == [(ARG, 1), (ARG, 2), (OP["LT"], 0)]
+    assert ser(lambda i, a: fn.sqrt(i) * a, np.int32, np.float32)[0] == [(ARG, 1), (OP["SQRT"], 0), (ARG, 2), (OP["MUL"], 0)]
+    # a weak integer literal above 2^24 beside a Float32 array in a wide call: folded to Float32(16777217) = 16777216
+    c, k = ser(lambda a: a + 16777217, np.float32, wide=True)
+    W_ = (OP["WIDEN"], 0)   # (only Float32 operands: the wide class is announced at the end)
+    assert c == [(ARG, 1), (CONST, 0), (OP["ADD"], 0), R, W_] and k == [16777216.0]
+    c, k = ser(lambda a: 16777219 * a, np.float32, wide=True)
+    assert c == [(CONST, 0), (ARG, 1), (OP["MUL"], 0), R, W_] and k == [16777220.0]
+    c, k = ser(lambda a: a + np.int32(16777217), np.float32)
+    assert c == [(ARG, 1), (CONST, 0), (OP["ADD"], 0), R, W_] and k == [16777216.0]
+    # ... a literal that Float32 holds, a Float64 operation and a Float32 call keep their bytes
+    assert ser(lambda a: a + 16777216, np.float32, wide=True) == ([(ARG, 1), (CONST, 0), (OP["ADD"], 0), R, W_], [16777216.0])
+    assert ser(lambda a: a + 16777217, np.float64) == ([(ARG, 1), (CONST, 0), (OP["ADD"], 0)], [16777217.0])
+    assert ser(lambda a: a + 16777217, np.float32, wide=False) == ([(ARG, 1), (CONST, 0), (OP["ADD"], 0)], [16777217.0])   # the Float32 class converts it
+    assert ser(lambda a: a < 16777217, np.float32, wide=True)[1] == [16777217.0]
+    # typing of the arithmetic operators follows Julia's promote_type, not NumPy's result_type
+    for f, ts, want in ((lambda a, b: a + b, (np.float32, np.int32), np.float32), (lambda a, b: a / b, (np.float32, np.int64), np.float32),
+                        (lambda a, b: a * b, (np.complex64, np.int32), np.complex64), (lambda a, b: a + b, (np.int32, np.uint32), np.uint32),
+                        (lambda a, b: a + b, (np.int8, np.uint8), np.uint8), (lambda a, b: a + b, (np.int64, np.uint64), np.uint64),
+                        (lambda a, b: a / b, (np.int32, np.int16), np.float64), (lambda a, b: fn.max(a, b), (np.int16, np.uint16), np.uint16)):
+        assert E.result_dtype(E.trace(f, 2), [np.dtype(t) for t in ts]) == np.dtype(want), ts
+    # the shim carries the same rule
+    assert "roundarg!(p, f, length(p.code), Ta, Tn); roundarg!(p, f, at, T, Tn)" in JL and "Ta in (Int32, UInt32, Int64, UInt64)" in JL
+
+
 # ---- typing (expected types: what Julia infers for the expression beside each row) ------------------------------------------------
 f32, f64, c64, c128 = np.float32, np.float64, np.complex64, np.complex128
 i8, i16, i32, i64, u8, u16, b = np.int8, np.int16, np.int32, np.int64, np.uint8, np.uint16, np.bool_

@@ -291,3 +291,46 @@ def test_stream_override_is_per_thread():
     finally:
         M._pop_stream()
     assert M._STREAM_OVERRIDE.stack == []
+
+
+def test_signed_zeros_captured_by_a_closure_are_different_functions(monkeypatch):
+    """`lambda x: x * c` with c = 0.0 and with c = -0.0 compared equal under `==`: the second call reused the first one's program from
+    _FPROG_CACHE and, on the same operands, its whole smr_problem from _PROBLEM_CACHE.  Captured scalars, defaults and keyword defaults
+    are keyed by type and repr, the parts of a complex included."""
+    import importlib
+    MR = importlib.import_module("strided_jl_amd.mapreduce")
+    a = S.StridedView(np.zeros((8, 8), order="F"))
+    b = a.similar()
+
+    def closure(c):
+        return lambda x: x * c
+
+    def default(c):
+        return lambda x, c=c: x * c
+
+    def kwdefault(c):
+        return lambda x, *, c=c: x * c
+
+    pairs = [(0.0, -0.0), (complex(0.0, 0.0), complex(0.0, -0.0)), (complex(0.0, 1.0), complex(-0.0, 1.0)), (np.float32(0.0), np.float32(-0.0)), (1, 1.0), (1, True)]
+    for make in (closure, default, kwdefault):
+        for p, q in pairs:
+            kp, kq = MR._closure_key(make(p)), MR._closure_key(make(q))
+            assert kp is not None and kq is not None and kp != kq, (make.__name__, p, q)
+            assert MR._closure_key(make(p)) == kp   # (and the same value is the same key)
+    # the program cache
+    MR._FPROG_CACHE.clear()
+    consts = []
+    for c in (0.0, -0.0, 0.0):
+        p, keep = S.build_problem(closure(c), None, None, a.size, (b, a), stream=0)
+        consts.append(p.fconsts[0])
+    assert [bool(np.signbit(v)) for v in consts] == [False, True, False] and len(MR._FPROG_CACHE) == 2
+    # the problem cache: the same operands, the second call builds a new problem with its own constant
+    launched = []
+    monkeypatch.setattr(type(a), "on_device", property(lambda self: True))
+    monkeypatch.setattr(MR, "_SMR_MAPREDUCE", lambda ref: launched.append(ref._obj.fconsts[0]) or 0)
+    MR._PROBLEM_CACHE.clear()
+    for c in (0.0, -0.0, 0.0, -0.0):
+        MR._mapreduce_fuse_(closure(c), None, None, a.size, (b, a))
+    assert [bool(np.signbit(v)) for v in launched] == [False, True, False, True], launched
+    assert len(MR._PROBLEM_CACHE) == 2
+    MR._PROBLEM_CACHE.clear()
