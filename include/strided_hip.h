@@ -549,10 +549,47 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * the footprint other items are compared against stays the members' operands (the partials are private to the group).  Under
  * "slices" = n (smr_seq_set; never automatically) the main launch of a split group that is a component of its own is cut into n
  * block ranges of at least 64 workgroups each, like an unsplit group -- but the ranges go back to back onto the item's ONE queue and
- * the fold follows them with the barrier bit, so it runs after all of them (no order across queues exists): n + 1 packets.       */
+ * the fold follows them with the barrier bit, so it runs after all of them (no order across queues exists): n + 1 packets.
+ *
+ * REDUCTION GROUPS.  With SMR_GROUP_REDUCE the group is K COMPLETE reductions -- a norm, an inner product, max |x| per block:
+ * dest = op(initop(dest), op over the whole box of f(in1, in2, ...)) with a destination of ONE element -- run as ONE launch of
+ * csrc/smr_k_greduce.hip.  Without the flag nothing changes: a reduction as member 0 still opens a contraction group.  Every member
+ * must be a reduction (redop != SMR_RED_NONE) whose destination, once canonicalised, is one element, with 1 .. SMR_MAXM - 1 distinct
+ * inputs and at most 2^31 - 1 box elements; a map, or a reduction that keeps a dim of extent > 1, gets SMR_EUNSUPPORTED naming the
+ * member, with "complete" in the message.  Members agree with member 0 exactly as contraction members do (compute class, whether
+ * operand types are converted, the number of distinct operands, dtype and conj flag per operand position, the f-program including
+ * its constants, redop, the initop CODE); initarg (beta), rank, extents, strides, pointers and offsets are the member's own.
+ * SMR_GROUP_REDUCE | SMR_GROUP_MEMBER_SCALARS is SMR_EUNSUPPORTED; SMR_GROUP_INDEPENDENT combines as usual.  The independence check,
+ * the count limits, the footprints, prepare / execute / destroy / describe / layout and smr_seq_add_group work as for the other
+ * kinds; the destination counts as READ in the footprint unless the initop code is ZERO or CONST.
+ * Member i gets W_i = min(ceil(total_i / 4096), 64) workgroups of 256 lanes -- what a single call takes under option
+ * "reduce_blocks" = 64 -- and the body the single call would take: the vector body (16-byte loads) when no operand type is converted,
+ * a 16-byte vector holds more than one element of the compute class, the canonical rank is 1, total_i is a multiple of the vector
+ * and at least 4096, and every input is broadcast or unit-stride from a 16-byte aligned address (the base pointers are fixed at
+ * creation, so alignment is decided there); the strided body otherwise.
+ * ACCUMULATION ORDER: that of the single call's complete-reduction kernel on a grid of W_i workgroups -- four accumulators per
+ * lane (vector body: a wave reads 4 consecutive 1-KiB rows per iteration; strided body: a grid stride of W_i * 256 with 4 elements
+ * in flight), the pairwise tree over the four, the wave butterfly, four wave sums through LDS.  W_i == 1: lane 0 applies the initop
+ * with the member's beta, redop, and stores.  W_i > 1: every workgroup publishes its partial write-through into the member's run of
+ * W_i slots, arrives at the member's counter, and the workgroup that arrives last folds the slots in slot order and stores -- inside
+ * the same launch; nobody waits or polls.  GUARANTEE: member i's result is bit-identical to smr_mapreduce on that member alone under
+ * option "reduce_blocks" = 64 whenever that call runs family REDUCE_ALL (the default of 2048 differs from 64 only above 64 * 4096
+ * elements).  A single call hands a complete reduction of canonical rank > 1 whose inputs run along dim 0 (a sub-box) to the ROW form
+ * of REDUCE_PART instead, which accumulates in another order; a group runs such a member on the strided body above.
+ * The partials (compute-class elements, a contiguous run of W_i slots per member with W_i > 1) and the arrival counters (one per
+ * such member) are owned by the group: smr_group_prepare or the first execution allocates them and ZEROES the counters, the last
+ * arriver leaves its counter at zero for the next run, smr_group_destroy frees both after draining the device.  Two executions of
+ * one group in flight at once share them: that is the caller's problem, as for split plans and split contraction groups.
+ * smr_group_describe reads "family=group kind=reduce members=K grid=G vec=<members on the vector body> strided=<on the strided body>
+ * f=<ident|abs2|mul2|prog> op=<+|*|min|max|&||> jit=<0|1> partials=<members with W > 1> scratch=<bytes> bytes=<algorithmic bytes>
+ * [ independent=asserted]"; smr_group_layout reports form 3 (strided) or 4 (vector), the first workgroup, W_i and the canonical rank.
+ * The launch is NOT sliceable -- the fold needs all of a member's workgroups in one launch: a recorded reduction group is one
+ * packet per replay and stays whole under "slices" = n.  Option "nt_load" selects non-temporal loads in the vector body as in a
+ * single call; it does not change values.                                                                                   */
 typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
 #define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
+#define SMR_GROUP_REDUCE 8u /* a reduction group: every member a complete reduction (REDUCTION GROUPS above; bit 4 is not a flag) */
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out);
 int smr_group_prepare(smr_group* g);
 int smr_group_execute(smr_group* g, void* stream);

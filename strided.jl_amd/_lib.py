@@ -470,6 +470,7 @@ class Plan:
 
 SMR_GROUP_INDEPENDENT = 1
 SMR_GROUP_MEMBER_SCALARS = 2
+SMR_GROUP_REDUCE = 8
 
 
 class Group:
@@ -486,9 +487,14 @@ class Group:
     group rule; N >= 2 = N slices per member, clamped to its chunks) cuts long reduced ranges over workgroups: the group is then
     TWO launches through partials it owns (one buffer per group: do not run one group on two streams at once), and a split member
     is bit-identical to the single call under "contract" = 2, "contract_tile" = the group's tile, "contract_split" = its slices.
+    `reduce=True` passes SMR_GROUP_REDUCE: a REDUCTION group, every member a complete reduction (its destination is one element:
+    a norm, an inner product, max |x| per block) with the f, op and initop kind of member 0 and a beta of its own; one launch, member
+    i on min(ceil(total_i / 4096), 64) workgroups, its partials folded inside the launch through scratch the group owns (do not run
+    one group on two streams at once).  Each member is bit-identical to the single call under option "reduce_blocks" = 64 where that
+    call runs family REDUCE_ALL.  `member_scalars` is refused for it.
     See include/strided_hip.h."""
 
-    def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False):
+    def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False, reduce: bool = False):
         self._lib = load()
         self._h = C.c_void_p()
         self.count = len(problems)
@@ -496,7 +502,7 @@ class Group:
         for i, p in enumerate(problems):
             C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(smr_problem))
         self._keep = (arr, problems, keepalive)
-        flags = (SMR_GROUP_INDEPENDENT if independent else 0) | (SMR_GROUP_MEMBER_SCALARS if member_scalars else 0)
+        flags = (SMR_GROUP_INDEPENDENT if independent else 0) | (SMR_GROUP_MEMBER_SCALARS if member_scalars else 0) | (SMR_GROUP_REDUCE if reduce else 0)
         check(self._lib.smr_group_create(arr, self.count, flags, C.byref(self._h)))
 
     def execute(self, stream: int | None = None):
@@ -513,7 +519,7 @@ class Group:
 
     def layout(self):
         """Per member (form, first workgroup, workgroups, canonical rank); form 0 = linear, 1 = transposing, 2 = a member of a
-        contraction group."""
+        contraction group, 3 / 4 = a member of a reduction group on the strided / the vector body."""
         n = int(self._lib.smr_group_layout(self._h, None, 0))
         buf = (C.c_int64 * max(1, n))()
         self._lib.smr_group_layout(self._h, buf, n)

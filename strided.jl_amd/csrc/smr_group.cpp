@@ -1,8 +1,9 @@
 // smr_group.cpp -- grouped launches (include/strided_hip.h: smr_group_*): the C ABI and the launch path of a planned group.
 // smr_group_create checks its arguments and has the planner (smr_plan_group.cpp: plan_group) fill a GroupPlan; the device tables
 // (members, workgroup prefix sums, per-member scalars) are uploaded by smr_group_prepare or the first execution, and
-// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip) -- a contraction
-// group with split members (option "group_contract_split") as two, through partials the group owns.
+// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip, smr_k_greduce.hip)
+// -- a contraction group with split members (option "group_contract_split") as two, through partials the group owns.  A reduction
+// group (SMR_GROUP_REDUCE) owns partials and arrival counters too, and folds them inside its one launch.
 #include <algorithm>
 #include <cstdio>
 #include <iterator>
@@ -26,6 +27,7 @@ namespace {
 // the launcher of the group's kind in the object of compute class CT (a bit copy, never a contraction, goes through Float32's)
 template <int CT>
 int launch_group_in(const GroupPlan& g, hipStream_t s) {
+    if (g.kind == GROUP_REDUCE) return launch_group_reduce_ct<CT>(g, s);
     if (g.kind == GROUP_CONTRACT) return g.contract.nsplit ? launch_group_contract_split_ct<CT>(g, s) : launch_group_contract_ct<CT>(g, s);
     return launch_group_ct<CT>(g, s);
 }
@@ -55,6 +57,18 @@ int ensure_tables(const GroupPlan& g) {
         if (!g.contract.d_partials) {
             const hipError_t e = hipMalloc(&g.contract.d_partials, g.contract.scratch_bytes);
             if (e != hipSuccess) return hip_error(e, "hipMalloc(group partials)");
+        }
+    }
+    if (g.reduce.npartials) {  // a run of slots and an arrival counter for every member with more than one workgroup.  A run writes a
+                               // slot before it reads it; the counters must be ZERO before the first launch (the workgroup that
+                               // arrives last leaves its counter at zero for the next one)
+        if (!g.reduce.d_partials) {
+            const hipError_t e = hipMalloc(&g.reduce.d_partials, (size_t)g.reduce.slots * (size_t)dtype_size(g.c.ct));
+            if (e != hipSuccess) return hip_error(e, "hipMalloc(group partials)");
+        }
+        if (!g.reduce.d_counters) {
+            const std::vector<unsigned> zeros((size_t)g.reduce.npartials, 0u);
+            if (int rc = upload(&g.reduce.d_counters, GroupPlan::bytes_of(zeros), "group arrival counters")) return rc;
         }
     }
     return SMR_OK;
@@ -87,7 +101,7 @@ extern "C" {
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
     if (!members || !out) return set_error(SMR_EINVAL, "smr_group_create: null argument");
     if (count < 1 || count > 65535) return set_error(SMR_EINVAL, "smr_group_create: count must be 1..65535");
-    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
+    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS | SMR_GROUP_REDUCE)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
     smr_group* h = new (std::nothrow) smr_group();
     if (!h) return set_error(SMR_ENOMEM, "out of host memory");
     if (int rc = plan_group(members, count, flags, h->plan)) {
@@ -156,7 +170,8 @@ int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap) {
 
 int smr_group_destroy(smr_group* g) {
     if (!g) return SMR_OK;
-    void* const tables[] = {g->plan.d_members, g->plan.d_first, g->plan.map.d_consts, g->plan.contract.d_split, g->plan.contract.d_fold_first, g->plan.contract.d_partials};
+    void* const tables[] = {g->plan.d_members, g->plan.d_first, g->plan.map.d_consts, g->plan.contract.d_split, g->plan.contract.d_fold_first, g->plan.contract.d_partials,
+                            g->plan.reduce.d_partials,   g->plan.reduce.d_counters};
     if (std::any_of(std::begin(tables), std::end(tables), [](void* t) { return t != nullptr; })) {
         (void)eager_fence_if_active();
         (void)hipDeviceSynchronize();  // a queued launch may still read the tables

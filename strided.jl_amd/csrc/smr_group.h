@@ -53,11 +53,28 @@ struct GroupSplitD {
     uint32_t tiles;              // output tiles: the member's workgroups in the main launch are tiles * S, the slice the slow digit
 };
 
+// One member of a REDUCTION group (SMR_GROUP_REDUCE; smr_k_greduce.hip): a complete reduction as a single call of FAM_REDUCE_ALL
+// carries it in its arguments.  Everything in it is wave-uniform.  beta (the initop's argument) is the member's own; redop and the
+// initop code are those of member 0.  The member's workgroups W are first_wg[i + 1] - first_wg[i].
+struct GroupReduceMemberD {
+    void* base[MAXM];            // operand addresses, element offsets folded in ([0]: the one destination element)
+    i64 strides[MAXM][MAXN];     // canonical strides (elements)
+    i64 dims[MAXN];              // canonical dims
+    i64 total;                   // box elements (at most 2^31 - 1)
+    i64 part_off;                // W > 1: the member's first slot in the group's partials (compute-class elements) ...
+    double beta[2];
+    int32_t counter;             // ... and its arrival counter
+    int32_t N;                   // canonical rank
+    int32_t form;                // GROUP_FORM_REDUCE_STRIDED or GROUP_FORM_REDUCE_VECTOR
+    int32_t pad;
+};
+
 // The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
 // space they are fetched by scalar loads into scalar registers, not once per lane.
 typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
 typedef const GroupContractMemberD __attribute__((address_space(4))) GroupContractMemberC;
 typedef const GroupSplitD __attribute__((address_space(4))) GroupSplitC;
+typedef const GroupReduceMemberD __attribute__((address_space(4))) GroupReduceMemberC;
 typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
 typedef const double __attribute__((address_space(4))) GroupConstC;
 
@@ -75,14 +92,20 @@ SMR_DEV int group_member_of(GroupWordC* first_wg, int count, uint32_t b) {
     return lo;
 }
 
+// what smr_group_layout reports per member: the body a map member runs (GroupMemberD::form), that it is a contraction, or the body
+// a member of a reduction group runs (GroupReduceMemberD::form)
+enum GroupForm { GROUP_FORM_LINEAR = 0, GROUP_FORM_TRANSPOSING = 1, GROUP_FORM_CONTRACT = 2, GROUP_FORM_REDUCE_STRIDED = 3, GROUP_FORM_REDUCE_VECTOR = 4 };
+
 #ifndef SMR_JIT
 // every recognised functor has a natively compiled group kernel (a single call's functor code); any other f is a program, as in GENERIC
 constexpr unsigned GROUP_FMASK = 0xffffffffu;
 
+// a reduction group runs natively the functors a single complete reduction does (smr_k_reduce.hip), any other f as a program
+constexpr unsigned GROUP_REDUCE_FMASK = (1u << FK_IDENT) | (1u << FK_ABS2) | (1u << FK_MUL2);
+
 // the kind is member 0's: a reduction opens a contraction group (every member an outer-product reduction on FAM_CONTRACT's tile body)
-enum GroupKind { GROUP_MAP, GROUP_CONTRACT };
-// what smr_group_layout reports per member: the body a map member runs (GroupMemberD::form), or that it is a contraction
-enum GroupForm { GROUP_FORM_LINEAR = 0, GROUP_FORM_TRANSPOSING = 1, GROUP_FORM_CONTRACT = 2 };
+// -- unless SMR_GROUP_REDUCE asks for a reduction group (every member a complete reduction)
+enum GroupKind { GROUP_MAP, GROUP_CONTRACT, GROUP_REDUCE };
 
 struct GroupMapPlan {  // GROUP_MAP only
     std::vector<GroupMemberD> members;
@@ -107,6 +130,17 @@ struct GroupContractPlan {  // GROUP_CONTRACT only
     mutable void* d_partials = nullptr;
 };
 
+struct GroupReducePlan {  // GROUP_REDUCE only
+    std::vector<GroupReduceMemberD> members;
+    int nvec = 0, nstrided = 0;            // members on the vector / the strided body
+    int npartials = 0;                     // members with more than one workgroup: each has a run of slots and a counter
+    i64 slots = 0;                         // the group's partials, in compute-class elements (sum of W_i over those members)
+    size_t scratch_bytes = 0;              // ... in bytes, the counters included
+    long double max_in_bytes = 0;          // the largest member's first input (what the non-temporal-load rule looks at)
+    mutable void* d_partials = nullptr;    // one buffer per group, and the counters (zeroed when allocated; a run leaves them zero)
+    mutable void* d_counters = nullptr;
+};
+
 // A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
 // (the values of the program's constants too, unless `map.varc`).
 struct GroupPlan {
@@ -114,6 +148,7 @@ struct GroupPlan {
     GroupKind kind = GROUP_MAP;
     GroupMapPlan map;
     GroupContractPlan contract;
+    GroupReducePlan reduce;
     std::vector<uint32_t> first_wg;   // count + 1 prefix sums of the members' workgroups
     std::vector<int> rank;            // canonical rank per member (smr_group_layout)
     bool jit = false;                 // f runs as a runtime-compiled functor
@@ -129,8 +164,10 @@ struct GroupPlan {
 
     // a host table as bytes; the member table of the group's kind
     template <class E> static std::pair<const void*, size_t> bytes_of(const std::vector<E>& v) { return {v.data(), v.size() * sizeof(E)}; }
-    std::pair<const void*, size_t> member_table() const { return kind == GROUP_CONTRACT ? bytes_of(contract.members) : bytes_of(map.members); }
-    int form(size_t i) const { return kind == GROUP_CONTRACT ? GROUP_FORM_CONTRACT : map.members[i].form; }
+    std::pair<const void*, size_t> member_table() const {
+        return kind == GROUP_CONTRACT ? bytes_of(contract.members) : (kind == GROUP_REDUCE ? bytes_of(reduce.members) : bytes_of(map.members));
+    }
+    int form(size_t i) const { return kind == GROUP_CONTRACT ? GROUP_FORM_CONTRACT : (kind == GROUP_REDUCE ? reduce.members[i].form : map.members[i].form); }
 };
 
 // smr_plan_group.cpp: plans members[0..count) (count >= 1, known flags) into a fresh `g`.  Host arithmetic only, no HIP runtime call
@@ -139,6 +176,7 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
 template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);           // smr_k_group.hip
 template <int CT> int launch_group_contract_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip
 template <int CT> int launch_group_contract_split_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip compiled with -DSMR_GCONTRACT_SPLIT
+template <int CT> int launch_group_reduce_ct(const GroupPlan&, hipStream_t);    // smr_k_greduce.hip
 
 int ensure_device();         // smr_api.cpp
 i64& group_max_bytes();      // option "group_max_bytes" (smr_group.cpp)

@@ -787,7 +787,9 @@ __global__ void __launch_bounds__(256) k_reduce_part_final(RedArgs a) {
     }
 }
 
-#ifndef SMR_JIT
+// (SMR_REDUCE_DEVICE_ONLY: smr_k_greduce.hip includes this file for the device functions above -- the one-launch fold's protocol, the
+// epilogue, the wave butterfly -- and compiles none of the kernels and launchers below)
+#if !defined(SMR_JIT) && !defined(SMR_REDUCE_DEVICE_ONLY)
 template <class T, class F, bool MIXED, int V>
 __global__ void __launch_bounds__(256) k_reduce_all(RedArgs a, F f) {
     reduce_all_body<T, F, MIXED, V>(a, f);
@@ -972,6 +974,6 @@ int launch_reduce_part_ct<SMR_CT>(const Plan& plan, void* const* bases, hipStrea
     const unsigned mask = fbit(FK_IDENT) | fbit(FK_MUL2);
     return with_functor<T>(c, mask, [&](auto f) { return go_part<T, decltype(f), false>(plan, bases, s, f); });
 }
-#endif  // !SMR_JIT
+#endif  // !SMR_JIT && !SMR_REDUCE_DEVICE_ONLY
 
 }  // namespace smr

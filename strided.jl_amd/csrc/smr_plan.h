@@ -20,6 +20,13 @@ bool plan_flatb(const Canon& c, FlatBPlan& f);
 bool plan_flat2(const Canon& c, Flat2Plan& f);
 void plan_reduce_all(const Canon& c, ReducePlan& rp);              // smr_plan_reduce.cpp
 void plan_reduce_part(const Canon& c, ReducePlan& rp);
+// complete reductions, single calls and the members of a reduction group (smr_plan_group.cpp) alike:
+constexpr i64 REDUCE_ALL_PER_BLOCK = 256 * 16;  // box elements per workgroup before a second workgroup is taken; also the vector body's floor
+constexpr i64 REDUCE_FOLD_MAX = 64;             // most partials of ONE arrival counter folded inside the launch (its arrivals serialise)
+// does a complete reduction take the vector body?  Same-typed operands, a 16-byte vector of more than one element, canonical rank 1,
+// a whole number of vectors, at least REDUCE_ALL_PER_BLOCK elements, every input broadcast or unit-stride from a 16-byte aligned
+// address (`bases`: the call's base pointers, nullptr: the plan's)
+bool reduce_all_vector(const Canon& c, void* const* bases);
 bool plan_contract(const Canon& c, ContractPlan& cp);             // smr_plan_contract.cpp (shape rules + the "contract" option's gate)
 // predicates shared by the family planners (smr_plan.cpp)
 int elem_bytes(const Canon& c);                      // bytes per element as the kernels move them

@@ -4,13 +4,15 @@
 // values of f's constants are the member's own, a row of a third table) and given its descriptor; its operands' byte ranges are the
 // independence check's input and the footprint of a group recorded in a sequence.  What differs between the kinds are plain functions
 // called from that loop: a map member takes one of the kernel's two bodies and its workgroups at once, a contraction its workgroups
-// once the whole group has decided the tile.
+// once the whole group has decided the tile, a complete reduction (SMR_GROUP_REDUCE) its body, its workgroups and -- with more than
+// one -- its run of partial slots and its arrival counter.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 
 #include "smr_contract.h"
 #include "smr_group.h"
+#include "smr_plan.h"
 
 namespace smr {
 
@@ -39,7 +41,7 @@ std::string mismatch(const Canon& r, const Canon& c, bool own_scalars) {
         return own_scalars ? "has another f-program than member 0 (only the values of its constants may differ)" : "has another f (program or constants) than member 0";
     // recognition (smr_canon.cpp) looks at the program's structure, FK_EXPR5 also at a constant's value: one launch runs ONE functor
     if (own_scalars && c.fkind != r.fkind) return "is recognised as another functor than member 0";
-    if (r.redop != SMR_RED_NONE) {  // a contraction group: one op and one initop code as well; beta (initarg) is the member's own
+    if (r.redop != SMR_RED_NONE) {  // a contraction or a reduction group: one op and one initop code as well; beta (initarg) is the member's own
         if (c.redop != r.redop) return "reduces with another op than member 0";
         if (c.initop != r.initop) return "has another kind of initop than member 0 (only its argument, beta, may differ)";
     }
@@ -379,24 +381,87 @@ void contract_describe(GroupPlan& g, uint32_t flags) {
     g.desc = std::string(buf) + split + independent_tag(flags);
 }
 
+// ---- reduction groups ------------------------------------------------------------------------------------------------------------
+// member i, a complete reduction: W = min(ceil(total / REDUCE_ALL_PER_BLOCK), REDUCE_FOLD_MAX) workgroups -- what plan_reduce_all gives a
+// single call under "reduce_blocks" = REDUCE_FOLD_MAX, the most partials one arrival counter folds inside a launch -- and the body the
+// single call would take (reduce_all_vector; the base pointers are fixed, so alignment is decided here).  A member with W > 1 gets the
+// next W slots of the group's partials and the next counter.
+int reduce_admit(int i, const Canon& c) {
+    if (c.nout != 1 || c.NK != 0)
+        return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is not a complete reduction: it keeps a dim of extent > 1 (" + std::to_string((long long)c.nout) +
+                                               " destination elements); a reduction group (SMR_GROUP_REDUCE) holds complete reductions only");
+    if (c.M < 2) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " has no input: a complete reduction in a group reads 1 .. SMR_MAXM - 1 distinct inputs");
+    return SMR_OK;
+}
+
+int reduce_member(GroupPlan& g, int i, const Canon& c) {
+    GroupReducePlan& rp = g.reduce;
+    GroupReduceMemberD& m = rp.members[(size_t)i];
+    std::memset(&m, 0, sizeof m);
+    for (int k = 0; k < c.M; ++k) {
+        m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+        for (int d = 0; d < c.N; ++d) m.strides[k][d] = c.strides[k][d];
+    }
+    for (int d = 0; d < MAXN; ++d) m.dims[d] = d < c.N ? c.dims[d] : 1;
+    m.total = c.total;
+    m.N = c.N;
+    m.beta[0] = c.initarg[0];
+    m.beta[1] = c.initarg[1];
+    const bool vec = reduce_all_vector(c, nullptr);
+    m.form = vec ? GROUP_FORM_REDUCE_VECTOR : GROUP_FORM_REDUCE_STRIDED;
+    (vec ? rp.nvec : rp.nstrided) += 1;
+    const i64 W = std::max<i64>(1, std::min<i64>((c.total + REDUCE_ALL_PER_BLOCK - 1) / REDUCE_ALL_PER_BLOCK, REDUCE_FOLD_MAX));
+    if (W > 1) {
+        m.part_off = rp.slots;
+        m.counter = rp.npartials;
+        rp.slots += W;
+        rp.npartials += 1;
+    }
+    rp.max_in_bytes = std::max(rp.max_in_bytes, (long double)c.total * c.esize[1]);
+    return assign_workgroups(g, i, W);
+}
+
+void reduce_describe(GroupPlan& g, uint32_t flags) {
+    static const char* names[FK_COUNT] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
+    static const char* ops[] = {"none", "+", "*", "min", "max", "&", "|"};
+    const Canon& c = g.c;
+    GroupReducePlan& rp = g.reduce;
+    // launch_group_reduce_ct(): a functor of the mask when the operand types are the compute class's, every other f a program
+    const int fk = (!c.mixed && (GROUP_REDUCE_FMASK & fbit(c.fkind))) ? c.fkind : FK_PROG;
+    g.jit = options().jit && fk == FK_PROG;
+    rp.scratch_bytes = (size_t)rp.slots * (size_t)dtype_size(c.ct) + (size_t)rp.npartials * sizeof(unsigned);
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "family=group kind=reduce members=%zu grid=%u vec=%d strided=%d f=%s op=%s jit=%d partials=%d scratch=%zu bytes=%lld%s", g.rank.size(),
+                  g.first_wg.back(), rp.nvec, rp.nstrided, names[fk], c.redop >= 0 && c.redop < 7 ? ops[c.redop] : "?", g.jit ? 1 : 0, rp.npartials, rp.scratch_bytes,
+                  (long long)g.algbytes, independent_tag(flags));
+    g.desc = buf;
+}
+
 }  // namespace
 
 int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g) {
     const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0, independent = (flags & SMR_GROUP_INDEPENDENT) != 0;
-    const bool contraction = members[0].redop != SMR_RED_NONE;  // the kind is member 0's
+    const bool reduce = (flags & SMR_GROUP_REDUCE) != 0;        // a reduction group: every member a complete reduction
+    const bool contraction = !reduce && members[0].redop != SMR_RED_NONE;  // else the kind is member 0's
+    if (reduce && own_scalars)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a reduction group (SMR_GROUP_REDUCE): per-member constants of f are not supported there");
     if (contraction && own_scalars)
         return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a contraction group (member 0 is a reduction): per-member constants of f are not supported there");
-    g.kind = contraction ? GROUP_CONTRACT : GROUP_MAP;
+    g.kind = reduce ? GROUP_REDUCE : (contraction ? GROUP_CONTRACT : GROUP_MAP);
     g.first_wg.assign((size_t)count + 1, 0);
     g.rank.resize((size_t)count);
-    if (contraction) g.contract.members.resize((size_t)count);
+    if (reduce) g.reduce.members.resize((size_t)count);
+    else if (contraction) g.contract.members.resize((size_t)count);
     else g.map.members.resize((size_t)count);
     std::vector<Range> ranges;
     Spans rd, wr;
     for (int i = 0; i < count; ++i) {
         const smr_problem& p = members[i];
-        // admit: a map group holds maps only, a contraction group reductions of the contraction shape only
-        if ((p.redop != SMR_RED_NONE) != contraction)
+        // admit: a map group holds maps only, a contraction group reductions of the contraction shape only, a reduction group
+        // complete reductions only
+        if (reduce && p.redop == SMR_RED_NONE)
+            return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a map; a reduction group (SMR_GROUP_REDUCE) holds complete reductions only");
+        if (!reduce && (p.redop != SMR_RED_NONE) != contraction)
             return set_error(SMR_EUNSUPPORTED, member_tag(i) + (contraction ? " is a map; a contraction group (member 0 is a reduction) holds contractions only"
                                                                              : " is a reduction; a group holds maps only"));
         Canon ci;
@@ -406,6 +471,8 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
         if (contraction && !contract_shape(c, di, dj))
             return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction, but not of the contraction shape: two inputs that vary along different kept dims of "
                                                                 "extent > 1 and both along a reduced dim, neither on the destination's buffer; a group holds maps only, or such contractions only");
+        if (reduce)
+            if (int rc = reduce_admit(i, c)) return rc;
         if (i > 0) {
             const std::string why = mismatch(g.c, c, own_scalars);
             if (!why.empty()) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
@@ -419,22 +486,26 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
             Range r{0, 0, i, k == 0};
             operand_span(c, k, c.base[k], r.lo, r.hi);
             (r.write ? wr : rd).emplace_back(r.lo, r.hi);
-            // a contraction accumulates into its destination unless the initop replaces the old value: the footprint then says
+            // a contraction or a complete reduction accumulates into its destination unless the initop replaces the old value: the footprint then says
             // that it is read (like footprint() in smr_api.cpp for every reduction), so that a recorded group acquires what the
             // sequence wrote there
-            if (r.write && contraction && c.initop != SMR_INIT_ZERO && c.initop != SMR_INIT_CONST) rd.emplace_back(r.lo, r.hi);
+            if (r.write && (contraction || reduce) && c.initop != SMR_INIT_ZERO && c.initop != SMR_INIT_CONST) rd.emplace_back(r.lo, r.hi);
             if (!independent) ranges.push_back(r);
         }
         // a map member takes its workgroups here; a contraction's depend on the tile, which contract_finish picks for the whole group
-        if (contraction) contract_member(g.contract.members[(size_t)i], c, di, dj);
+        if (reduce) {
+            if (int rc = reduce_member(g, i, c)) return rc;
+        } else if (contraction) contract_member(g.contract.members[(size_t)i], c, di, dj);
         else if (int rc = map_member(g, i, c, own_scalars)) return rc;
     }
-    if (!contraction) map_finish(g.map, count);
-    else if (int rc = contract_finish(g)) return rc;
+    if (g.kind == GROUP_MAP) map_finish(g.map, count);
+    if (g.kind == GROUP_CONTRACT)
+        if (int rc = contract_finish(g)) return rc;  // (a reduction group decides nothing over the whole group)
     if (int rc = independent ? SMR_OK : check_independent(ranges)) return rc;
     g.rd = merged(std::move(rd));
     g.wr = merged(std::move(wr));
-    if (contraction) contract_describe(g, flags);
+    if (reduce) reduce_describe(g, flags);
+    else if (contraction) contract_describe(g, flags);
     else map_describe(g, flags);
     return SMR_OK;
 }

@@ -4,7 +4,7 @@
 namespace smr {
 
 void plan_reduce_all(const Canon& c, ReducePlan& rp) {
-    const i64 per_block = 256 * 16;
+    const i64 per_block = REDUCE_ALL_PER_BLOCK;
     i64 nb = (c.total + per_block - 1) / per_block;
     nb = std::max<i64>(1, std::min<i64>(nb, std::max<i64>(1, options().reduce_blocks)));
     rp.nparts = (int)nb;
@@ -197,14 +197,29 @@ void plan_reduce_part(const Canon& c, ReducePlan& rp) {
     if (rp.nparts > 1) rp.scratch_bytes = (size_t)c.nout * (size_t)rp.nparts * s.es;  // chunk partials
 }
 
+// operand k's element-offset base (as make_optab computes it) is 16-byte aligned
+static bool aligned16(const Canon& c, void* const* bases, int k) {
+    const uintptr_t b = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]);
+    return b % 16 == 0;
+}
+
+bool reduce_all_vector(const Canon& c, void* const* bases) {
+    const int es = dtype_size(c.ct);
+    const int vmax = es >= 16 ? 1 : 16 / es;
+    // one fused dim, every input unit stride / broadcast, 16-B aligned
+    bool vec = !c.mixed && vmax > 1 && c.N == 1 && (c.total % vmax == 0) && c.total >= REDUCE_ALL_PER_BLOCK;
+    for (int k = 1; k < c.M && vec; ++k) {
+        if (c.strides[k][0] == 0) continue;
+        if (c.strides[k][0] != 1) vec = false;
+        if (!aligned16(c, bases, k)) vec = false;
+    }
+    return vec;
+}
+
 RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch) {
     const Canon& c = plan.c;
     RedLaunch r;
     const int es = dtype_size(c.ct);
-    auto aligned16 = [&](int k) {  // operand k's element-offset base (as make_optab computes it) is 16-byte aligned
-        const uintptr_t b = (uintptr_t)(bases ? bases[c.orig[k]] : c.base[k]) + (uintptr_t)(c.offsets[k] * (i64)c.esize[k]);
-        return b % 16 == 0;
-    };
     const i64 rs = options().reduce_single;
     if (plan.family == FAM_REDUCE_ALL) {
         int blocks = plan.red.nparts;
@@ -212,17 +227,9 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
         r.nparts = blocks;
         // up to 64 partials are folded inside the launch (1 MiB: 4.9 -> 4.1 us; tools/reduce_all_sweep.py) -- the arrivals of ONE
         // counter serialise, so larger reductions keep the second launch (8 MiB with 256 workgroups: 6.6 vs 5.4 us)
-        const bool single = blocks > 1 && rs > 0 && blocks <= std::max<i64>(rs, 64);
+        const bool single = blocks > 1 && rs > 0 && blocks <= std::max<i64>(rs, REDUCE_FOLD_MAX);
         r.fold = blocks == 1 ? RED_FOLD_EPILOGUE : (single ? RED_FOLD_IN_LAUNCH : RED_FOLD_SECOND_LAUNCH);
-        // vector path: one fused dim, every input unit stride / broadcast, 16-B aligned
-        const int vmax = es >= 16 ? 1 : 16 / es;
-        bool vec = !c.mixed && vmax > 1 && c.N == 1 && (c.total % vmax == 0) && c.total >= 4096;
-        for (int k = 1; k < c.M && vec; ++k) {
-            if (c.strides[k][0] == 0) continue;
-            if (c.strides[k][0] != 1) vec = false;
-            if (!aligned16(k)) vec = false;
-        }
-        r.vec = vec ? vmax : 1;
+        r.vec = reduce_all_vector(c, bases) ? 16 / es : 1;
         return r;
     }
     if (plan.family != FAM_REDUCE_PART) return r;
@@ -238,7 +245,7 @@ RedLaunch reduce_launch(const Plan& plan, void* const* bases, bool have_scratch)
         bool vec = vmax > 1 && (c.dims[vax] % vmax == 0);
         for (int k = 1; k < c.M && vec; ++k) {
             if (c.strides[k][vax] != 1) continue;
-            if (!aligned16(k)) vec = false;
+            if (!aligned16(c, bases, k)) vec = false;
             for (int d = 0; d < c.N; ++d)
                 if (d != vax && (c.strides[k][d] % vmax)) vec = false;
         }

@@ -285,6 +285,8 @@ def _mapreduce_fuse_(f, op, initop, dims, arrays):
             return arrays[0]
         if op is not None and g.contract and g.defer(f, dims, arrays, op, initop):  # a contraction: S.group(contract=True)
             return arrays[0]
+        if op is not None and g.reduce and g.defer(f, dims, arrays, op, initop, complete=True):  # a complete reduction: S.group(reduce=True)
+            return arrays[0]
         g.flush()
     if _SMR_MAPREDUCE is None:
         _SMR_MAPREDUCE = L.load().smr_mapreduce
@@ -330,7 +332,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, (forced contraction tile, group_contract_split) or 0 for maps); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, the kind: (forced contraction tile, group_contract_split), "reduce", or 0 for maps); least recently used first
 
 
 def _byte_range(a):
@@ -403,12 +405,21 @@ def _contract_shaped(dims, arrays) -> bool:
     return _member_bytes(arrays) <= L.get_option("group_max_bytes")
 
 
+def _complete_reduction(dims, arrays) -> bool:
+    """Is the call a member of a reduction group: its destination has one element (stride 0 or extent 1 along every dim), and its
+    algorithmic bytes are within option "group_max_bytes"?"""
+    dest = arrays[0]
+    if any(n != 1 and st != 0 for n, st in zip(dims, dest.strides)):
+        return False
+    return _member_bytes(arrays) <= L.get_option("group_max_bytes")
+
+
 class _Deferred:
-    __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key", "op", "initop")
+    __slots__ = ("f", "dims", "arrays", "stream", "bucket", "wr", "rd", "key", "op", "initop", "kind")
 
 
 class group:
-    """`with S.group(independent=False, member_scalars=False, contract=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    """`with S.group(independent=False, member_scalars=False, contract=False, reduce=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
     `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
@@ -434,14 +445,22 @@ class group:
     slices per member) is read when a bucket is built, like "group_contract_tile": a bucket with split members is TWO launches (the
     members' slices into partials the group owns, then the fold), and a split member is bit-identical to the single call under
     "contract" = 2, "contract_tile" = the group's tile, "contract_split" = its slices.  Without `contract=True` a reduction flushes and runs as usual.
+    `reduce=True` (reduction groups): COMPLETE reductions -- `mapreducedim_(f, op, out1, A, B...)` / `_mapreducedim_` with an initop
+    into a destination of ONE element, such as element i of a K-vector reshaped to all-ones dims -- within "group_max_bytes" are
+    deferred as well, and every bucket of them becomes ONE launch of csrc/smr_k_greduce.hip (L.Group(reduce=True)).  The contraction
+    test comes first when `contract=True` is also set.  Their bucket key also holds ("reduce", the op, the kind of initop) and the
+    values of f's captured scalars (always: a reduction group has one f); beta is per member.  Each result is bit-identical to the
+    single call's under option "reduce_blocks" = 64 where that call runs family REDUCE_ALL (include/strided_hip.h).
+    `S.mapreduce(f, op, A)` without `dims` returns a host scalar: like every host read it still flushes, and is never deferred.
     `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
 
     MAX_PENDING = 4096
 
-    def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False):
+    def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False, reduce: bool = False):
         self.independent = bool(independent)
         self.member_scalars = bool(member_scalars)
         self.contract = bool(contract)
+        self.reduce = bool(reduce)
         self.pending = []
         self.groups = []
         self.singles = 0
@@ -479,21 +498,23 @@ class group:
                     return True
         return False
 
-    def defer(self, f, dims, arrays, op=None, initop=None) -> bool:
-        """Takes one map call (destination first), or with `op` one reduction of the contraction shape.  False: the call is not
+    def defer(self, f, dims, arrays, op=None, initop=None, complete=False) -> bool:
+        """Takes one map call (destination first), or with `op` one reduction of the contraction shape -- with `complete` one
+        complete reduction (a reduction group's member) instead.  False: the call is not
         eligible (too large, too many operands, a reduction of another shape) -- the caller flushes and runs it through the normal
         path."""
         arrays = tuple(arrays)
         if len(arrays) < 2 or len(arrays) > L.SMR_MAXM or len(dims) > L.SMR_MAXN:
             return False
         if op is not None:
-            if not _contract_shaped(dims, arrays):
+            if not (_complete_reduction(dims, arrays) if complete else _contract_shaped(dims, arrays)):
                 return False
         elif _member_bytes(arrays) > L.get_option("group_max_bytes"):
             return False
         c = _Deferred()
         c.f, c.dims, c.arrays = f, tuple(int(d) for d in dims), arrays
         c.op, c.initop = op, initop
+        c.kind = "map" if op is None else ("reduce" if complete else "contract")
         c.stream = _current_stream()
         dts = tuple(np.dtype(a.dtype) for a in arrays)
         code, consts = _serialized(f, len(arrays), dts)
@@ -508,7 +529,8 @@ class group:
         else:
             ck = tuple(consts)
         # a bucket of contractions also has one op and one kind of initop; beta is the member's
-        tail = () if op is None else ("contract", _redop_code(op), _initop_code(initop)[0])
+        # (so has a bucket of complete reductions)
+        tail = () if op is None else (c.kind, _redop_code(op), _initop_code(initop)[0])
         c.bucket = (bytes(code), ck, tuple(d.str for d in dts), len(arrays), tuple(a.op for a in arrays), same, c.stream) + tail
         c.wr = _byte_range(arrays[0])  # (a reduction also reads its destination: a write range conflicts with everything a read does)
         c.rd = [_byte_range(a) for a in arrays[1:]]
@@ -530,7 +552,10 @@ class group:
 
     def _launch(self, calls, stream):
         # a bucket of contractions: the library is not passed member_scalars, and plans under the forced tile and the split option
-        if calls[0].op is not None:
+        reduce = calls[0].kind == "reduce"
+        if reduce:  # a bucket of complete reductions: no member_scalars either; nothing an option decides at creation
+            scalars, plan_opts = False, "reduce"
+        elif calls[0].op is not None:
             scalars, plan_opts = False, (L.get_option("group_contract_tile"), L.get_option("group_contract_split"))
         else:
             scalars, plan_opts = self.member_scalars, 0
@@ -547,7 +572,8 @@ class group:
             built = [build_problem(c.f, c.op, c.initop, c.dims, c.arrays, stream=stream) for c in calls]
             try:
                 # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
-                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=scalars)
+                grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=scalars,
+                              **({"reduce": True} if reduce else {}))   # (the other kinds are created exactly as before)
             except L.UnsupportedOnDevice:
                 for c in calls:
                     self._single(c)
@@ -704,7 +730,9 @@ def _mapreduce(f, op, A: StridedView, init=None):
 
 
 def mapreduce(f, op, A: StridedView, dims=None, init=None):
-    """`Base.mapreduce(f, op, A::StridedView; dims=:, init)` (src/mapreduce.jl:16-30)."""
+    """`Base.mapreduce(f, op, A::StridedView; dims=:, init)` (src/mapreduce.jl:16-30).  Without `dims` the result is a host scalar:
+    inside `with S.group(reduce=True):` that read flushes what is pending like every host read, so such a call is never grouped with
+    others (use `mapreducedim_` into the elements of a device vector for that)."""
     if dims is None:
         return _mapreduce(f, op, A, init)
     if isinstance(dims, int):
