@@ -499,7 +499,9 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * "contraction" in the message.  Every member must agree with member 0 in compute class, in whether operand types are converted,
  * in dtype and conj flag per operand position, in the f-program including its constants, in redop and in the initop CODE; initarg
  * (beta) is the member's own, and so are rank, extents, strides, pointers, offsets and batch / outer reduced dims.
- * SMR_GROUP_MEMBER_SCALARS with a contraction group is SMR_EUNSUPPORTED (per-member constants of f: not supported there).  The
+ * SMR_GROUP_MEMBER_SCALARS with a contraction group is SMR_EUNSUPPORTED (per-member constants of f: not supported there).  A
+ * contraction group takes them under a flag of its own, SMR_GROUP_CONTRACT_SCALARS: see PER-MEMBER CONSTANTS OF A CONTRACTION GROUP
+ * below.  The
  * independence check (the destination's range is a write range, which covers the read of the old destination), the footprints, the
  * 2^31 - 1 workgroup limit and the count limits are those of map groups.
  * One tile size per group: 32 x 32 outputs per workgroup when the group then still has >= 256 workgroups and those tiles are at
@@ -551,6 +553,27 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * block ranges of at least 64 workgroups each, like an unsplit group -- but the ranges go back to back onto the item's ONE queue and
  * the fold follows them with the barrier bit, so it runs after all of them (no order across queues exists): n + 1 packets.
  *
+ * PER-MEMBER CONSTANTS OF A CONTRACTION GROUP.  SMR_GROUP_CONTRACT_SCALARS (contraction groups only; combines with
+ * SMR_GROUP_INDEPENDENT) lets the VALUES of f's constants differ from member to member: mul!(C_blk, A_blk, B_blk, alpha_blk, beta_blk)
+ * with a coefficient per block, f = x * y * alpha, is one group.  The members still agree with member 0 in everything listed above, in
+ * the program's length, every (opcode, immediate) pair and the number of constants; a member whose constants put it into another
+ * compute class is refused like any member of another class.  With SMR_GROUP_REDUCE, on a map group (member 0 is a map) or together
+ * with SMR_GROUP_MEMBER_SCALARS the flag is SMR_EUNSUPPORTED, the message naming it.  Every member keeps the constants of its own
+ * canonicalisation in a third device table, one row of W doubles per member (2 * the number of constants, (re, im) pairs), which
+ * smr_group_prepare or the first execution uploads and smr_group_destroy frees after draining the device.  A workgroup reads the row
+ * of ITS MEMBER -- not of its tile or slice: every tile and every slice of a member reads the same row -- by scalar loads, before
+ * any data load.  When all rows are bit-equal (-0.0 differs from 0.0) the plan is the one planned without the flag, with no table.
+ * Nothing else in the plan depends on the flag: tile rule, slices ("group_contract_split"), workgroups, layout and footprint are those
+ * of the same members without it.  The program `arg1 arg2 MUL const MUL` -- the mul! form -- on operands of the compute class runs a
+ * natively compiled functor in such a group (f=mul2scale, (a * b) * alpha with the f-program's own multiply: bit-equal to the
+ * program); every other f with constants, and every group that converts operand types, is runtime-compiled or interpreted, and the
+ * runtime-compiled text depends on the structure of f only: one code object for every table of constants.
+ * GUARANTEE: member i is bit-identical to smr_mapreduce on that member alone, with its own constants, under "contract" = 2 (a split
+ * member: also "contract_tile" = the group's tile and "contract_split" = S_i).  smr_group_describe appends " scalars=member" (a table)
+ * or " scalars=shared" (the rows were equal) at the very end, and reads f=mul2scale jit=0 for the recognised product of a
+ * scalars=member group.  A recorded scalars=member group is one packet per replay (two in one item when split) and is cut into block
+ * ranges under "slices" like any contraction group: the kernel finds its member, and with it its row, from its index in the group.
+ *
  * REDUCTION GROUPS.  With SMR_GROUP_REDUCE the group is K COMPLETE reductions -- a norm, an inner product, max |x| per block:
  * dest = op(initop(dest), op over the whole box of f(in1, in2, ...)) with a destination of ONE element -- run as ONE launch of
  * csrc/smr_k_greduce.hip.  Without the flag nothing changes: a reduction as member 0 still opens a contraction group.  Every member
@@ -590,6 +613,7 @@ typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
 #define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
 #define SMR_GROUP_REDUCE 8u /* a reduction group: every member a complete reduction (REDUCTION GROUPS above; bit 4 is not a flag) */
+#define SMR_GROUP_CONTRACT_SCALARS 64u /* a contraction group whose members have constants of f of their own (bits 4, 16 and 32 are not flags) */
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out);
 int smr_group_prepare(smr_group* g);
 int smr_group_execute(smr_group* g, void* stream);

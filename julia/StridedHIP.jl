@@ -17,7 +17,7 @@ using Base.Broadcast: Broadcasted, DefaultArrayStyle
 import Strided: _mapreduce_fuse!
 
 const lib = get(ENV, "STRIDED_HIP_LIB", "libstrided_hip.so")
-const MAXN, MAXM = 8, 8
+const MAXN, MAXM = 8, 8; const GROUP_CONTRACT_SCALARS = UInt32(64)  # (smr_group_create flag: an α per block of a mul! sweep, f = x*y*α; the group entry points are not bound yet)
 
 # Calls are ORDERED on the library's stream and return as soon as they are queued (round 4; rounds 1-3 ended every funnel call
 # with a stream synchronisation, which costs more than a 3 us kernel).  That is indistinguishable from the reference's synchronous

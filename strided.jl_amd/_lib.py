@@ -471,6 +471,7 @@ class Plan:
 SMR_GROUP_INDEPENDENT = 1
 SMR_GROUP_MEMBER_SCALARS = 2
 SMR_GROUP_REDUCE = 8
+SMR_GROUP_CONTRACT_SCALARS = 64
 
 
 class Group:
@@ -482,7 +483,11 @@ class Group:
     the number of constants and the compute class they lead to must still be those of member 0.
     A group whose member 0 is a reduction is a CONTRACTION group: every member is an outer-product reduction (the generic mul_
     box) with the f, op and initop kind of member 0 and a beta of its own; one launch of the grouped CONTRACT kernel, each member
-    bit-identical to the single call under option "contract" = 2.  `member_scalars` is refused for it.  Option
+    bit-identical to the single call under option "contract" = 2.  `member_scalars` is refused for it; `contract_scalars=True` passes
+    SMR_GROUP_CONTRACT_SCALARS instead (contraction groups only; refused with `member_scalars`, with `reduce` and for maps): the values of
+    f's constants -- the alpha of `mul_(C, A, B, alpha, beta)` -- may differ from member to member, each member bit-identical to the
+    single call with its own constants; describe() then ends in " scalars=member" (a row of constants per member; f=mul2scale for
+    x * y * alpha) or " scalars=shared" (they were equal: the plan without the flag).  Option
     "group_contract_tile" (0 = the rule, 16, 32) forces its tile.  Option "group_contract_split" (0 = never, the default; 1 = the
     group rule; N >= 2 = N slices per member, clamped to its chunks) cuts long reduced ranges over workgroups: the group is then
     TWO launches through partials it owns (one buffer per group: do not run one group on two streams at once), and a split member
@@ -494,7 +499,8 @@ class Group:
     call runs family REDUCE_ALL.  `member_scalars` is refused for it.
     See include/strided_hip.h."""
 
-    def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False, reduce: bool = False):
+    def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False, reduce: bool = False,
+                 contract_scalars: bool = False):
         self._lib = load()
         self._h = C.c_void_p()
         self.count = len(problems)
@@ -503,6 +509,7 @@ class Group:
             C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(smr_problem))
         self._keep = (arr, problems, keepalive)
         flags = (SMR_GROUP_INDEPENDENT if independent else 0) | (SMR_GROUP_MEMBER_SCALARS if member_scalars else 0) | (SMR_GROUP_REDUCE if reduce else 0)
+        flags |= SMR_GROUP_CONTRACT_SCALARS if contract_scalars else 0
         check(self._lib.smr_group_create(arr, self.count, flags, C.byref(self._h)))
 
     def execute(self, stream: int | None = None):

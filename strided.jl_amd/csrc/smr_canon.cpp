@@ -296,6 +296,15 @@ static void recognise(Canon& c) {
     }
 }
 
+bool prog_is_mul2scale(const Canon& c) {
+    const ProgD& p = c.prog;
+    auto op = [&](int i) { return (int)p.code[2 * i]; };
+    auto im = [&](int i) { return (int)p.code[2 * i + 1]; };
+    auto isarg = [&](int i, int k) { return op(i) == SMR_OP_ARG && im(i) == k; };
+    return p.len == 5 && c.M - 1 == 2 && p.nconst == 1 && isarg(0, 1) && isarg(1, 2) && op(2) == SMR_OP_MUL && op(3) == SMR_OP_CONST && im(3) == 0 &&
+           op(4) == SMR_OP_MUL;
+}
+
 // ---- canonicalisation ---------------------------------------------------------------------------
 int canonicalise(const smr_problem* p0, Canon& c) {
     if (!p0) return set_error(SMR_EINVAL, "null problem");

@@ -757,6 +757,14 @@ template <class T> struct FMul2 {
     static constexpr int NIN = 2;
     SMR_DEV T operator()(const T* a) const { return a[0] * a[1]; }
 };
+// the mul! form x * y * alpha of a contraction group with an alpha per member (smr_k_gcontract.hip): the program `arg1 arg2 MUL const
+// MUL` with the program's own multiply (complex, wrapping Int64), so that it is bit-equal to the program run as a program
+template <class T> struct FMul2Scale {
+    static constexpr int NIN = 2;
+    T c;
+    template <class P> SMR_DEV void set_consts(P k) { c = mk_const<T>(k, 0); }
+    SMR_DEV T operator()(const T* a) const { return mathx<T>::bin(SMR_OP_MUL, mathx<T>::bin(SMR_OP_MUL, a[0], a[1]), c); }
+};
 template <class T> struct FExpr5 {  // a*exp(c*a) + sin(a*a), real types only
     static constexpr int NIN = 1;
     T c;

@@ -28,6 +28,8 @@ namespace {
 template <int CT>
 int launch_group_in(const GroupPlan& g, hipStream_t s) {
     if (g.kind == GROUP_REDUCE) return launch_group_reduce_ct<CT>(g, s);
+    if (g.kind == GROUP_CONTRACT && g.contract.varc)  // per-member constants of f: the bodies that read the member's row
+        return g.contract.nsplit ? launch_group_contract_split_varc_ct<CT>(g, s) : launch_group_contract_varc_ct<CT>(g, s);
     if (g.kind == GROUP_CONTRACT) return g.contract.nsplit ? launch_group_contract_split_ct<CT>(g, s) : launch_group_contract_ct<CT>(g, s);
     return launch_group_ct<CT>(g, s);
 }
@@ -50,6 +52,8 @@ int ensure_tables(const GroupPlan& g) {
     if (int rc = upload(&g.d_first, GroupPlan::bytes_of(g.first_wg), "group workgroup ranges")) return rc;
     if (g.map.varc)
         if (int rc = upload(&g.map.d_consts, GroupPlan::bytes_of(g.map.consts), "group member scalars")) return rc;
+    if (g.contract.varc)
+        if (int rc = upload(&g.contract.d_consts, GroupPlan::bytes_of(g.contract.consts), "group member scalars")) return rc;
     if (g.contract.nsplit) {  // the split form's tables and the group's partials: one buffer per group, every element of which a run
                               // writes (main launch) before it reads it (fold): nothing an earlier run left there is ever read
         if (int rc = upload(&g.contract.d_split, GroupPlan::bytes_of(g.contract.split), "group slices")) return rc;
@@ -101,7 +105,7 @@ extern "C" {
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
     if (!members || !out) return set_error(SMR_EINVAL, "smr_group_create: null argument");
     if (count < 1 || count > 65535) return set_error(SMR_EINVAL, "smr_group_create: count must be 1..65535");
-    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS | SMR_GROUP_REDUCE)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
+    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS | SMR_GROUP_REDUCE | SMR_GROUP_CONTRACT_SCALARS)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
     smr_group* h = new (std::nothrow) smr_group();
     if (!h) return set_error(SMR_ENOMEM, "out of host memory");
     if (int rc = plan_group(members, count, flags, h->plan)) {
@@ -171,7 +175,7 @@ int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap) {
 int smr_group_destroy(smr_group* g) {
     if (!g) return SMR_OK;
     void* const tables[] = {g->plan.d_members, g->plan.d_first, g->plan.map.d_consts, g->plan.contract.d_split, g->plan.contract.d_fold_first, g->plan.contract.d_partials,
-                            g->plan.reduce.d_partials,   g->plan.reduce.d_counters};
+                            g->plan.contract.d_consts, g->plan.reduce.d_partials, g->plan.reduce.d_counters};
     if (std::any_of(std::begin(tables), std::end(tables), [](void* t) { return t != nullptr; })) {
         (void)eager_fence_if_active();
         (void)hipDeviceSynchronize();  // a queued launch may still read the tables

@@ -128,6 +128,13 @@ struct GroupContractPlan {  // GROUP_CONTRACT only
     mutable void* d_split = nullptr;       // device copies, and the partials buffer (one per group)
     mutable void* d_fold_first = nullptr;
     mutable void* d_partials = nullptr;
+    // per-member constants of f (SMR_GROUP_CONTRACT_SCALARS and constants that do differ), as in GroupMapPlan: row i holds member
+    // i's W doubles, ProgD::consts (W = 2 * nconst) -- for the recognised product x * y * alpha (`mul2scale`) the pair (re, im) of alpha
+    bool varc = false;
+    bool mul2scale = false;                // varc, unmixed and f is the mul! form: the natively compiled FMul2Scale
+    int W = 0;
+    std::vector<double> consts;
+    mutable void* d_consts = nullptr;      // device copy of `consts`
 };
 
 struct GroupReducePlan {  // GROUP_REDUCE only
@@ -142,7 +149,7 @@ struct GroupReducePlan {  // GROUP_REDUCE only
 };
 
 // A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
-// (the values of the program's constants too, unless `map.varc`).
+// (the values of the program's constants too, unless `map.varc` / `contract.varc`).
 struct GroupPlan {
     Canon c;
     GroupKind kind = GROUP_MAP;
@@ -176,6 +183,8 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
 template <int CT> int launch_group_ct(const GroupPlan&, hipStream_t);           // smr_k_group.hip
 template <int CT> int launch_group_contract_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip
 template <int CT> int launch_group_contract_split_ct(const GroupPlan&, hipStream_t);  // smr_k_gcontract.hip compiled with -DSMR_GCONTRACT_SPLIT
+template <int CT> int launch_group_contract_varc_ct(const GroupPlan&, hipStream_t);        // ... with -DSMR_GCONTRACT_VARC (contract.varc)
+template <int CT> int launch_group_contract_split_varc_ct(const GroupPlan&, hipStream_t);  // ... (contract.varc and a split member)
 template <int CT> int launch_group_reduce_ct(const GroupPlan&, hipStream_t);    // smr_k_greduce.hip
 
 int ensure_device();         // smr_api.cpp

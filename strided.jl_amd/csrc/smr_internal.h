@@ -417,6 +417,9 @@ Options& options();
 unsigned long long* stamp_next(size_t waves);
 
 int canonicalise(const smr_problem* p, Canon& c);  // smr_canon.cpp (with options())
+// is the canonical f the mul! form x * y * alpha (`arg1 arg2 MUL const MUL`, one constant)?  Not a kind of its own: Canon::fkind
+// stays FK_PROG and every single call runs it as a program; a contraction group with per-member constants runs it natively
+bool prog_is_mul2scale(const Canon& c);            // smr_canon.cpp
 int make_plan(const smr_problem* p, Plan& plan);  // smr_plan.cpp: selects the family and calls its planner
 void describe(Plan& plan);
 

@@ -31,6 +31,16 @@
 // Compiled once per compute type (-DSMR_CT=n), and a second time with -DSMR_GCONTRACT_SPLIT: the split form's two kernels and their
 // entry point in objects of their own, so that k_group_contract's code objects are those of the library before the split form
 // (kernels added to a translation unit change the register allocation of the ones it held: profiles/contract_split.txt).
+//
+// PER-MEMBER CONSTANTS OF f (SMR_GROUP_CONTRACT_SCALARS, GroupContractPlan::varc): an alpha per block.  A third table holds one row of
+// W doubles per member (ProgD::consts of the member's own canonicalisation); group_contract_varc_body / group_contract_split_varc_body
+// are the two bodies above plus one step: right after the member search the workgroup rebuilds f's constants from the row of its
+// MEMBER (set_consts, smr_device.h; wave-uniform index, constant address space: scalar loads) -- every tile and every slice of a
+// member reads the same row -- before any data load.  The fold launch does not call f and is the split form's kernel, as it is
+// (instantiated in these objects a second time).  Natively
+// compiled: the mul! form x * y * alpha (FMul2Scale); every other f with constants, and every mixed group, is a program whose
+// runtime-compiled text depends on f's structure only.  A third pass, -DSMR_GCONTRACT_VARC, compiles these kernels and their entry
+// points into objects of their own, for the reason given above.
 #include "smr_contract.h"
 #include "smr_group.h"
 
@@ -127,8 +137,215 @@ SMR_DEV void group_contract_split_body(const GroupContractSplitArgs a, F f) {
     contract_by_op<T, F, MIXED, RB, true>(m, t, a.g.redop, f, lds, tile, t_lo, t_hi, sink);
 }
 
+// per-member constants: the argument block behind the existing fields (wg0 keeps its kernarg offset), and the two bodies
+struct GroupConstsArgs {
+    int32_t W, pad;        // doubles per row of `consts`
+    const double* consts;  // count rows of f's constants, one per member
+};
+struct GroupContractVarcArgs {
+    GroupContractArgs g;
+    GroupConstsArgs k;
+};
+struct GroupContractSplitVarcArgs {
+    GroupContractSplitArgs s;
+    GroupConstsArgs k;
+};
+
+template <class T, class F, bool MIXED, int RB>
+SMR_DEV void group_contract_varc_body(const GroupContractVarcArgs a, F f) {
+    typedef CGeom<T, RB> G;
+    __shared__ __attribute__((aligned(16))) T lds[2 * 2 * G::TK * G::LD];
+    const uint32_t b = blockIdx.x + a.g.wg0;
+    GroupWordC* const first_wg = (GroupWordC*)a.g.first_wg;
+    const int lo = group_member_of(first_wg, a.g.count, b);
+    f.set_consts((GroupConstC*)a.k.consts + (i64)lo * a.k.W);  // the member's row: not the workgroup's, not the slice's
+    GroupContractMemberC& m = ((GroupContractMemberC*)a.g.members)[lo];
+    const OpTab t = group_contract_optab(m, a.g);
+    contract_by_op<T, F, MIXED, RB, false>(m, t, a.g.redop, f, lds, (i64)(b - first_wg[lo]), 0, m.Q * m.nkc, (T*)nullptr);
+}
+
+template <class T, class F, bool MIXED, int RB>
+SMR_DEV void group_contract_split_varc_body(const GroupContractSplitVarcArgs a, F f) {
+    typedef CGeom<T, RB> G;
+    __shared__ __attribute__((aligned(16))) T lds[2 * 2 * G::TK * G::LD];
+    const uint32_t b = blockIdx.x + a.s.g.wg0;
+    GroupWordC* const first_wg = (GroupWordC*)a.s.g.first_wg;
+    const int lo = group_member_of(first_wg, a.s.g.count, b);
+    f.set_consts((GroupConstC*)a.k.consts + (i64)lo * a.k.W);  // the member's row: not the workgroup's, not the slice's
+    GroupContractMemberC& m = ((GroupContractMemberC*)a.s.g.members)[lo];
+    GroupSplitC& sp = ((GroupSplitC*)a.s.split)[lo];
+    const OpTab t = group_contract_optab(m, a.s.g);
+    const i64 w = (i64)(b - first_wg[lo]), nchunks = m.Q * m.nkc;
+    const i64 S = (i64)sp.S;
+    if (S < 2) {  // (wave-uniform: sp is the member's)
+        contract_by_op<T, F, MIXED, RB, false>(m, t, a.s.g.redop, f, lds, w, 0, nchunks, (T*)nullptr);
+        return;
+    }
+    const i64 tiles = (i64)sp.tiles, sl = w / tiles, tile = w - sl * tiles;
+    const i64 t_lo = sl * sp.cps, t_hi = t_lo + sp.cps < nchunks ? t_lo + sp.cps : nchunks;
+    T* sink = (T*)a.s.partials + sp.part_off + (tile * S + sl) * (i64)(RB * RB * 256);
+    contract_by_op<T, F, MIXED, RB, true>(m, t, a.s.g.redop, f, lds, tile, t_lo, t_hi, sink);
+}
+
 #ifndef SMR_JIT
-#ifndef SMR_GCONTRACT_SPLIT
+#if defined(SMR_GCONTRACT_SPLIT) || defined(SMR_GCONTRACT_VARC)
+// The split form's second launch, the grouped form of k_contract_fold: workgroup w of split member i is (register = w % RB^2, tile =
+// w / RB^2); one lane per (tile, register, lane) of the main launch folds that output's S_i partials in slice order, acc = P_0; acc =
+// op(acc, P_s) for s = 1 .. S_i - 1, and puts the result through the epilogue with the member's own beta; lanes past the end of a
+// ragged tile drop theirs.  It does not call f.  Eight partials are loaded (index clamped, never guarded) before the first is used.
+template <class T, bool MIXED, int RB>
+__global__ void __launch_bounds__(256) k_group_contract_fold(GroupContractSplitArgs a) {
+    typedef CGeom<T, RB> G;
+    const uint32_t b0 = blockIdx.x;
+    GroupWordC* const fold_first = (GroupWordC*)a.fold_first;
+    const int lo = group_member_of(fold_first, a.g.count, b0);
+    GroupContractMemberC& g = ((GroupContractMemberC*)a.g.members)[lo];
+    GroupSplitC& sp = ((GroupSplitC*)a.split)[lo];
+    const OpTab t = group_contract_optab(g, a.g);
+    i64 b = (i64)(b0 - fold_first[lo]);
+    const int reg = (int)(b % (RB * RB));
+    b /= RB * RB;
+    const int kparts = (int)sp.S;
+    const T* p = (const T*)a.partials + sp.part_off + b * kparts * (i64)(RB * RB * 256) + reg * 256 + (int)threadIdx.x;
+    const i64 bi = b % g.nti;
+    b /= g.nti;
+    const i64 bj = b % g.ntj;
+    b /= g.ntj;
+    i64 off0 = 0;
+#pragma nounroll
+    for (int n = 0; n < g.nrd; ++n) {
+        const int d = g.rdim[n];
+        const i64 x = b / g.dims[d], cd = b - x * g.dims[d];
+        b = x;
+        off0 += cd * g.strides[0][d];
+    }
+    const int li = (int)threadIdx.x & (CONTRACT_LANES - 1), lj = (int)threadIdx.x >> 4;
+    const i64 i = bi * G::TILE + G::idx(li, reg / RB), j = bj * G::TILE + G::idx(lj, reg % RB);
+    if (i >= g.dims[g.di] || j >= g.dims[g.dj]) return;
+    constexpr i64 SL = RB * RB * 256;  // elements between the slices of one tile
+    const int last = kparts - 1;
+    T acc = p[0];
+    for (int s0 = 1; s0 <= last; s0 += 8) {
+        T x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = p[(i64)(s0 + e < last ? s0 + e : last) * SL];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const T v = red_apply<T>(a.g.redop, acc, x[e]);
+            if (s0 + e <= last) acc = v;
+        }
+    }
+    contract_epilogue<T, MIXED>(g, t, off0 + i * g.strides[0][g.di] + j * g.strides[0][g.dj], acc);
+}
+#endif
+
+#if defined(SMR_GCONTRACT_VARC)
+template <class T, class F, bool MIXED, int RB>
+__global__ void __launch_bounds__(256) k_group_contract_varc(GroupContractVarcArgs a, F f) {
+    group_contract_varc_body<T, F, MIXED, RB>(a, f);
+}
+
+template <class T, class F, bool MIXED, int RB>
+__global__ void __launch_bounds__(256) k_group_contract_split_varc(GroupContractSplitVarcArgs a, F f) {
+    group_contract_split_varc_body<T, F, MIXED, RB>(a, f);
+}
+
+// the unsplit arguments of a planned group (what go_gc / go_gcs fill), and its table of constants
+static void fill_gc(const GroupPlan& g, GroupContractArgs& a) {
+    const Canon& c = g.c;
+    std::memset(&a, 0, sizeof a);
+    a.members = (const GroupContractMemberD*)g.d_members;
+    a.first_wg = (const uint32_t*)g.d_first;
+    a.count = (int32_t)g.contract.members.size();
+    a.wg0 = 0;
+    a.redop = c.redop;
+    for (int k = 0; k < 3; ++k) {
+        a.dtype[k] = c.dtype[k];
+        a.conj[k] = c.conj[k];
+    }
+}
+static int fill_consts(const GroupPlan& g, GroupConstsArgs& k) {
+    const GroupContractPlan& cp = g.contract;
+    // (a dry run compiles without a device: no tables yet, and nothing is launched)
+    if (!cp.varc || cp.W < 1 || (!jit_dry_run() && !cp.d_consts)) return set_error(SMR_EINVAL, "contraction group: per-member constants planned without their table");
+    k.W = cp.W;
+    k.pad = 0;
+    k.consts = (const double*)cp.d_consts;
+    return SMR_OK;
+}
+
+template <class T, class F, bool MIXED, int RB>
+static int launch_gcv(const Canon& c, const GroupContractVarcArgs& a, unsigned grid, hipStream_t s, F f) {
+    // sliceable like k_group_contract: wg0 has the kernarg offset it has there, and the row is found from the member
+    mark_sliceable(1, (unsigned)(offsetof(GroupContractVarcArgs, g) + offsetof(GroupContractArgs, wg0)), 0);
+    if constexpr (is_jit<F>::value)  // the kernel argument kc holds member 0's constants and goes unused; the text depends on f's structure only
+        return launch_jit<T>(c, s, "gcontract", "smr::GroupContractVarcArgs", "group_contract_varc_body", "", grid, 256, 0, a, MIXED, RB);
+    else
+        return launch_native(nullptr, 0, "k_group_contract_varc", [&] { SMR_LAUNCH((k_group_contract_varc<T, F, MIXED, RB>), dim3(grid), dim3(256), 0, s, a, f); });
+}
+
+template <class T, class F, bool MIXED>
+static int go_gcv(const GroupPlan& g, hipStream_t s, F f) {
+    GroupContractVarcArgs a;
+    fill_gc(g, a.g);
+    if (int rc = fill_consts(g, a.k)) return rc;
+    const unsigned grid = g.first_wg.back();
+    if (g.contract.rb == 2) return launch_gcv<T, F, MIXED, 2>(g.c, a, grid, s, f);
+    if (g.contract.rb == 1) return launch_gcv<T, F, MIXED, 1>(g.c, a, grid, s, f);
+    return set_error(SMR_EINVAL, "contraction group: no kernel for this tile");
+}
+
+template <>
+int launch_group_contract_varc_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
+    typedef ct_type<SMR_CT>::type T;
+    const Canon& c = g.c;
+    if (c.mixed) return with_prog<T>(c, [&](auto f) { return go_gcv<T, decltype(f), true>(g, s, f); });
+    // natively compiled: the mul! form x * y * alpha (the planner recognised it); every other f is runtime-compiled or interpreted
+    if (g.contract.mul2scale) return go_gcv<T, FMul2Scale<T>, false>(g, s, FMul2Scale<T>{});
+    return with_prog<T>(c, [&](auto f) { return go_gcv<T, decltype(f), false>(g, s, f); });
+}
+
+// the two launches of the split form: the members' (tile, slice) workgroups with their rows, then the split form's fold as it is
+template <class T, class F, bool MIXED, int RB>
+static int launch_gcsv(const GroupPlan& g, const GroupContractSplitVarcArgs& a, hipStream_t s, F f) {
+    const unsigned grid = g.first_wg.back();
+    mark_sliceable(1, (unsigned)(offsetof(GroupContractSplitVarcArgs, s) + offsetof(GroupContractSplitArgs, g) + offsetof(GroupContractArgs, wg0)), 0);
+    int rc;
+    if constexpr (is_jit<F>::value)
+        rc = launch_jit<T>(g.c, s, "gcontract", "smr::GroupContractSplitVarcArgs", "group_contract_split_varc_body", "", grid, 256, 0, a, MIXED, RB);
+    else
+        rc = launch_native(nullptr, 0, "k_group_contract_split_varc", [&] { SMR_LAUNCH((k_group_contract_split_varc<T, F, MIXED, RB>), dim3(grid), dim3(256), 0, s, a, f); });
+    if (rc || jit_no_launch()) return rc;
+    SMR_LAUNCH((k_group_contract_fold<T, MIXED, RB>), dim3(g.contract.fold_first.back()), dim3(256), 0, s, a.s);
+    return check_launch("k_group_contract_fold");
+}
+
+template <class T, class F, bool MIXED>
+static int go_gcsv(const GroupPlan& g, hipStream_t s, F f) {
+    const GroupContractPlan& cp = g.contract;
+    if (!jit_dry_run() && (!g.d_members || !g.d_first || !cp.d_split || !cp.d_fold_first || !cp.d_partials))
+        return set_error(SMR_EINVAL, "split contraction group without its tables or its partials buffer");
+    GroupContractSplitVarcArgs a;
+    std::memset(&a, 0, sizeof a);
+    fill_gc(g, a.s.g);
+    a.s.split = (const GroupSplitD*)cp.d_split;
+    a.s.fold_first = (const uint32_t*)cp.d_fold_first;
+    a.s.partials = cp.d_partials;
+    if (int rc = fill_consts(g, a.k)) return rc;
+    if (cp.rb == 2) return launch_gcsv<T, F, MIXED, 2>(g, a, s, f);
+    if (cp.rb == 1) return launch_gcsv<T, F, MIXED, 1>(g, a, s, f);
+    return set_error(SMR_EINVAL, "contraction group: no kernel for this tile");
+}
+
+template <>
+int launch_group_contract_split_varc_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
+    typedef ct_type<SMR_CT>::type T;
+    const Canon& c = g.c;
+    if (c.mixed) return with_prog<T>(c, [&](auto f) { return go_gcsv<T, decltype(f), true>(g, s, f); });
+    if (g.contract.mul2scale) return go_gcsv<T, FMul2Scale<T>, false>(g, s, FMul2Scale<T>{});
+    return with_prog<T>(c, [&](auto f) { return go_gcsv<T, decltype(f), false>(g, s, f); });
+}
+#elif !defined(SMR_GCONTRACT_SPLIT)
 template <class T, class F, bool MIXED, int RB>
 __global__ void __launch_bounds__(256) k_group_contract(GroupContractArgs a, F f) {
     group_contract_body<T, F, MIXED, RB>(a, f);
@@ -178,55 +395,6 @@ int launch_group_contract_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
 template <class T, class F, bool MIXED, int RB>
 __global__ void __launch_bounds__(256) k_group_contract_split(GroupContractSplitArgs a, F f) {
     group_contract_split_body<T, F, MIXED, RB>(a, f);
-}
-
-// The split form's second launch, the grouped form of k_contract_fold: workgroup w of split member i is (register = w % RB^2, tile =
-// w / RB^2); one lane per (tile, register, lane) of the main launch folds that output's S_i partials in slice order, acc = P_0; acc =
-// op(acc, P_s) for s = 1 .. S_i - 1, and puts the result through the epilogue with the member's own beta; lanes past the end of a
-// ragged tile drop theirs.  It does not call f.  Eight partials are loaded (index clamped, never guarded) before the first is used.
-template <class T, bool MIXED, int RB>
-__global__ void __launch_bounds__(256) k_group_contract_fold(GroupContractSplitArgs a) {
-    typedef CGeom<T, RB> G;
-    const uint32_t b0 = blockIdx.x;
-    GroupWordC* const fold_first = (GroupWordC*)a.fold_first;
-    const int lo = group_member_of(fold_first, a.g.count, b0);
-    GroupContractMemberC& g = ((GroupContractMemberC*)a.g.members)[lo];
-    GroupSplitC& sp = ((GroupSplitC*)a.split)[lo];
-    const OpTab t = group_contract_optab(g, a.g);
-    i64 b = (i64)(b0 - fold_first[lo]);
-    const int reg = (int)(b % (RB * RB));
-    b /= RB * RB;
-    const int kparts = (int)sp.S;
-    const T* p = (const T*)a.partials + sp.part_off + b * kparts * (i64)(RB * RB * 256) + reg * 256 + (int)threadIdx.x;
-    const i64 bi = b % g.nti;
-    b /= g.nti;
-    const i64 bj = b % g.ntj;
-    b /= g.ntj;
-    i64 off0 = 0;
-#pragma nounroll
-    for (int n = 0; n < g.nrd; ++n) {
-        const int d = g.rdim[n];
-        const i64 x = b / g.dims[d], cd = b - x * g.dims[d];
-        b = x;
-        off0 += cd * g.strides[0][d];
-    }
-    const int li = (int)threadIdx.x & (CONTRACT_LANES - 1), lj = (int)threadIdx.x >> 4;
-    const i64 i = bi * G::TILE + G::idx(li, reg / RB), j = bj * G::TILE + G::idx(lj, reg % RB);
-    if (i >= g.dims[g.di] || j >= g.dims[g.dj]) return;
-    constexpr i64 SL = RB * RB * 256;  // elements between the slices of one tile
-    const int last = kparts - 1;
-    T acc = p[0];
-    for (int s0 = 1; s0 <= last; s0 += 8) {
-        T x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = p[(i64)(s0 + e < last ? s0 + e : last) * SL];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const T v = red_apply<T>(a.g.redop, acc, x[e]);
-            if (s0 + e <= last) acc = v;
-        }
-    }
-    contract_epilogue<T, MIXED>(g, t, off0 + i * g.strides[0][g.di] + j * g.strides[0][g.dj], acc);
 }
 
 // the two launches of the split form: the members' (tile, slice) workgroups, then the fold (native: it does not call f)
@@ -280,7 +448,7 @@ int launch_group_contract_split_ct<SMR_CT>(const GroupPlan& g, hipStream_t s) {
     if (c.fkind == FK_MUL2) return go_gcs<T, FMul2<T>, false>(g, s, FMul2<T>{});
     return with_prog<T>(c, [&](auto f) { return go_gcs<T, decltype(f), false>(g, s, f); });
 }
-#endif  // SMR_GCONTRACT_SPLIT
+#endif  // SMR_GCONTRACT_VARC / unsplit / SMR_GCONTRACT_SPLIT
 #endif  // !SMR_JIT
 
 }  // namespace smr

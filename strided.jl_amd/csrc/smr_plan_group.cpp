@@ -1,7 +1,8 @@
 // smr_plan_group.cpp -- the group planner (smr_group.h: plan_group).  Host arithmetic only, no HIP runtime call: like every planner
 // file it links into tools/plan_dump.cpp, which pins the device tables of a corpus of groups.  One loop over the members: each is
 // canonicalised like a single call, checked against member 0 (one kernel instantiation, one f; under SMR_GROUP_MEMBER_SCALARS the
-// values of f's constants are the member's own, a row of a third table) and given its descriptor; its operands' byte ranges are the
+// values of f's constants are the member's own, a row of a third table; a contraction group takes them under SMR_GROUP_CONTRACT_SCALARS)
+// and given its descriptor; its operands' byte ranges are the
 // independence check's input and the footprint of a group recorded in a sequence.  What differs between the kinds are plain functions
 // called from that loop: a map member takes one of the kernel's two bodies and its workgroups at once, a contraction its workgroups
 // once the whole group has decided the tile, a complete reduction (SMR_GROUP_REDUCE) its body, its workgroups and -- with more than
@@ -26,7 +27,8 @@ typedef std::vector<std::pair<uintptr_t, uintptr_t>> Spans;  // (smr_sched.h)
 std::string member_tag(int i) { return "smr_group_create: member " + std::to_string(i); }
 
 // does member `c` run the same kernel instantiation with the same functor as member 0 (`r`)?  Empty = yes, else what differs.
-// `own_scalars` (SMR_GROUP_MEMBER_SCALARS): the values of f's constants may differ, nothing else.
+// `own_scalars` (SMR_GROUP_MEMBER_SCALARS; SMR_GROUP_CONTRACT_SCALARS on a contraction group): the values of f's constants may differ,
+// nothing else.
 std::string mismatch(const Canon& r, const Canon& c, bool own_scalars) {
     if (c.bitcopy != r.bitcopy || (!c.bitcopy && c.ct != r.ct)) return "computes in another class than member 0";
     if (c.mixed != r.mixed) return "differs from member 0 in whether operand types are converted";
@@ -364,10 +366,31 @@ int contract_finish(GroupPlan& g) {
     return contract_layout(g, es, rb, want);
 }
 
+// SMR_GROUP_CONTRACT_SCALARS, member i: its row of the constant table, the constants of its own canonicalisation (ProgD::consts; for
+// the mul! form that is the pair (re, im) of alpha, which FMul2Scale reads like FScale reads Canon::fc)
+void contract_member_consts(GroupContractPlan& cp, int i, const Canon& c) {
+    if (i == 0) cp.W = 2 * c.prog.nconst;
+    cp.consts.insert(cp.consts.end(), c.prog.consts, c.prog.consts + cp.W);
+}
+
+// bit-equal rows, or none: the plan is the unflagged one, no table and today's f path (map_finish).  Otherwise the launch reads the
+// member's row; the mul! form on operands of the compute class then runs the natively compiled functor
+void contract_consts_finish(GroupPlan& g, int count) {
+    GroupContractPlan& cp = g.contract;
+    const size_t row = sizeof(double) * (size_t)cp.W;
+    for (int i = 1; i < count && !cp.varc; ++i) cp.varc = row && std::memcmp(cp.consts.data(), cp.consts.data() + (size_t)i * cp.W, row) != 0;
+    if (!cp.varc) {
+        std::vector<double>().swap(cp.consts);
+        cp.W = 0;
+    }
+    cp.mul2scale = cp.varc && !g.c.mixed && prog_is_mul2scale(g.c);
+}
+
 void contract_describe(GroupPlan& g, uint32_t flags) {
     static const char* ops[] = {"none", "+", "*", "min", "max", "&", "|"};
-    // launch_group_contract_ct(): the product of same-typed operands is native, every other f a program
-    const bool native = !g.c.mixed && g.c.fkind == FK_MUL2;
+    // launch_group_contract_ct(): the product of same-typed operands is native, every other f a program -- but for the mul! form
+    // in a group with a row of constants per member (launch_group_contract_varc_ct())
+    const bool native = !g.c.mixed && (g.c.fkind == FK_MUL2 || g.contract.mul2scale);
     const int es = dtype_size(g.c.ct), rb = g.contract.rb;
     g.jit = options().jit && !native;
     char buf[256], split[160] = "";
@@ -376,9 +399,10 @@ void contract_describe(GroupPlan& g, uint32_t flags) {
         std::snprintf(split, sizeof split, " split=%d kparts=%d fold=second-launch fold_grid=%u scratch=%zu", g.contract.nsplit, g.contract.max_s,
                       g.contract.fold_first.back(), g.contract.scratch_bytes);
     std::snprintf(buf, sizeof buf, "family=group kind=contract members=%zu grid=%u tile=%d k=%d lds=%zu f=%s op=%s jit=%d bytes=%lld", g.rank.size(), g.first_wg.back(),
-                  CONTRACT_LANES * rb, contract_tk(es, rb), contract_lds(es, rb), native ? "mul2" : "prog", g.c.redop >= 0 && g.c.redop < 7 ? ops[g.c.redop] : "?",
+                  CONTRACT_LANES * rb, contract_tk(es, rb), contract_lds(es, rb), g.contract.mul2scale ? "mul2scale" : (native ? "mul2" : "prog"), g.c.redop >= 0 && g.c.redop < 7 ? ops[g.c.redop] : "?",
                   g.jit ? 1 : 0, (long long)g.algbytes);
-    g.desc = std::string(buf) + split + independent_tag(flags);
+    g.desc = std::string(buf) + split + independent_tag(flags) +
+             ((flags & SMR_GROUP_CONTRACT_SCALARS) ? (g.contract.varc ? " scalars=member" : " scalars=shared") : "");
 }
 
 // ---- reduction groups ------------------------------------------------------------------------------------------------------------
@@ -440,9 +464,17 @@ void reduce_describe(GroupPlan& g, uint32_t flags) {
 }  // namespace
 
 int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g) {
+    const bool contract_scalars = (flags & SMR_GROUP_CONTRACT_SCALARS) != 0;
     const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0, independent = (flags & SMR_GROUP_INDEPENDENT) != 0;
     const bool reduce = (flags & SMR_GROUP_REDUCE) != 0;        // a reduction group: every member a complete reduction
     const bool contraction = !reduce && members[0].redop != SMR_RED_NONE;  // else the kind is member 0's
+    // (SMR_GROUP_CONTRACT_SCALARS first: its refusals name it, whatever else is set; the refusals of flag 2 keep their text)
+    if (contract_scalars && reduce)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_CONTRACT_SCALARS with a reduction group (SMR_GROUP_REDUCE): per-member constants of f are not supported there");
+    if (contract_scalars && !contraction)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_CONTRACT_SCALARS with a map group (member 0 is a map): the flag is for contraction groups, a map group takes SMR_GROUP_MEMBER_SCALARS");
+    if (contract_scalars && own_scalars)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_CONTRACT_SCALARS together with SMR_GROUP_MEMBER_SCALARS: a contraction group takes the former alone");
     if (reduce && own_scalars)
         return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a reduction group (SMR_GROUP_REDUCE): per-member constants of f are not supported there");
     if (contraction && own_scalars)
@@ -474,7 +506,7 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
         if (reduce)
             if (int rc = reduce_admit(i, c)) return rc;
         if (i > 0) {
-            const std::string why = mismatch(g.c, c, own_scalars);
+            const std::string why = mismatch(g.c, c, own_scalars || contract_scalars);
             if (!why.empty()) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
         }
         if (c.total > 0x7fffffffLL) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " has more than 2^31 - 1 box elements");
@@ -495,10 +527,14 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
         // a map member takes its workgroups here; a contraction's depend on the tile, which contract_finish picks for the whole group
         if (reduce) {
             if (int rc = reduce_member(g, i, c)) return rc;
-        } else if (contraction) contract_member(g.contract.members[(size_t)i], c, di, dj);
+        } else if (contraction) {
+            contract_member(g.contract.members[(size_t)i], c, di, dj);
+            if (contract_scalars) contract_member_consts(g.contract, i, c);
+        }
         else if (int rc = map_member(g, i, c, own_scalars)) return rc;
     }
     if (g.kind == GROUP_MAP) map_finish(g.map, count);
+    if (g.kind == GROUP_CONTRACT && contract_scalars) contract_consts_finish(g, count);
     if (g.kind == GROUP_CONTRACT)
         if (int rc = contract_finish(g)) return rc;  // (a reduction group decides nothing over the whole group)
     if (int rc = independent ? SMR_OK : check_independent(ranges)) return rc;

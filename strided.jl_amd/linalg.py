@@ -20,6 +20,10 @@ Many small products (the blocks of a block-sparse contraction) share ONE launch 
 `with S.group(contract=True):` -- calls of `mul_` on matrices with the same alpha and the same kind of
 beta (0, 1, or anything else; the value is per call) are deferred and run as a contraction group
 (csrc/smr_k_gcontract.hip), each result bit-identical to the single call under "contract" = 2.
+`with S.group(contract=True, contract_scalars=True):` also puts calls that differ in alpha into one launch -- a coefficient per
+block: the group keeps a row of f's constants per member (SMR_GROUP_CONTRACT_SCALARS, f=mul2scale natively compiled) and every block
+is still bit-identical to the single call with its own alpha.  alpha = 1 lowers to another f (x * y) and stays in a bucket of its
+own; alpha = 0 is a map.
 `S.set_option("group_contract_split", 0 | 1 | N)` (default 0: never) is "contract_split" for those groups: a few blocks with small
 open legs and a very long contracted leg (an environment or projection step) get slices of that leg as workgroups of the one
 launch, and a second launch folds them in slice order (1 = the group rule, N >= 2 = N slices per member, clamped to its chunks).

@@ -332,7 +332,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars, stream, the kind: (forced contraction tile, group_contract_split), "reduce", or 0 for maps); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars -- "contract_scalars" for a contraction bucket under that keyword --, stream, the kind: (forced contraction tile, group_contract_split), "reduce", or 0 for maps); least recently used first
 
 
 def _byte_range(a):
@@ -419,7 +419,7 @@ class _Deferred:
 
 
 class group:
-    """`with S.group(independent=False, member_scalars=False, contract=False, reduce=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    """`with S.group(independent=False, member_scalars=False, contract=False, reduce=False, contract_scalars=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
     `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
@@ -445,6 +445,11 @@ class group:
     slices per member) is read when a bucket is built, like "group_contract_tile": a bucket with split members is TWO launches (the
     members' slices into partials the group owns, then the fold), and a split member is bit-identical to the single call under
     "contract" = 2, "contract_tile" = the group's tile, "contract_split" = its slices.  Without `contract=True` a reduction flushes and runs as usual.
+    `contract_scalars=True` (needs `contract=True`; SMR_GROUP_CONTRACT_SCALARS): the VALUES of a contraction's captured scalars leave its
+    bucket key, which keeps what `member_scalars` keeps for maps (how many, any imaginary part, all integer-valued): `mul_(C_i, A_i, B_i,
+    alpha_i, beta_i)` with a coefficient per block is ONE launch (describe(): f=mul2scale scalars=member), each block bit-identical to
+    the single call with its own alpha under "contract" = 2.  alpha = 1 is another f (x * y) and stays in a bucket of its own, alpha = 0
+    is a map; maps and complete reductions bucket as without it.
     `reduce=True` (reduction groups): COMPLETE reductions -- `mapreducedim_(f, op, out1, A, B...)` / `_mapreducedim_` with an initop
     into a destination of ONE element, such as element i of a K-vector reshaped to all-ones dims -- within "group_max_bytes" are
     deferred as well, and every bucket of them becomes ONE launch of csrc/smr_k_greduce.hip (L.Group(reduce=True)).  The contraction
@@ -456,7 +461,11 @@ class group:
 
     MAX_PENDING = 4096
 
-    def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False, reduce: bool = False):
+    def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False, reduce: bool = False,
+                 contract_scalars: bool = False):
+        if contract_scalars and not contract:
+            raise ValueError("S.group(contract_scalars=True) needs contract=True: the flag is for contraction groups")
+        self.contract_scalars = bool(contract_scalars)
         self.independent = bool(independent)
         self.member_scalars = bool(member_scalars)
         self.contract = bool(contract)
@@ -524,7 +533,8 @@ class group:
         same = tuple(ops.index(o) for o in ops)
         # what the constants contribute.  A contraction group has one f: their values, whatever member_scalars says.  Under
         # member_scalars a map contributes only what they decide in canonicalise(): count, complex or not, integer class or not
-        if self.member_scalars and op is None:
+        # (contract_scalars: the same for a contraction, whose group then holds a row of constants per member)
+        if (self.member_scalars and op is None) or (self.contract_scalars and op is not None and not complete):
             ck = (len(consts), any(v.imag != 0 for v in consts), all(_integer_valued(v) for v in consts))
         else:
             ck = tuple(consts)
@@ -559,9 +569,11 @@ class group:
             scalars, plan_opts = False, (L.get_option("group_contract_tile"), L.get_option("group_contract_split"))
         else:
             scalars, plan_opts = self.member_scalars, 0
+        # contract_scalars: passed for contraction buckets only, and part of the cached group's key (in the slot of member_scalars)
+        cscalars = self.contract_scalars and not reduce and calls[0].op is not None
         key = None
         if all(c.key is not None for c in calls):
-            key = (tuple(c.key for c in calls), self.independent, scalars, stream, plan_opts)
+            key = (tuple(c.key for c in calls), self.independent, "contract_scalars" if cscalars else scalars, stream, plan_opts)
         grp = None
         if key is not None:
             try:
@@ -573,7 +585,7 @@ class group:
             try:
                 # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
                 grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=scalars,
-                              **({"reduce": True} if reduce else {}))   # (the other kinds are created exactly as before)
+                              **({"reduce": True} if reduce else ({"contract_scalars": True} if cscalars else {})))   # (the other kinds are created exactly as before)
             except L.UnsupportedOnDevice:
                 for c in calls:
                     self._single(c)

@@ -17,6 +17,8 @@
 // with both options at their defaults.
 // Behind the groups, a section "gsplit <id> ..." plans contraction groups under option "group_contract_split": the group rule's outcomes
 // (split, a forced tile, a mixed group, groups left alone), forced slices on both tiles, slices clamped to the chunks, and the option at 0.
+// Last, a section "gscalars <id> ..." plans contraction groups under SMR_GROUP_CONTRACT_SCALARS (f = x * y * alpha): equal constants (shared),
+// a row per member, and a row per member with split members; its digest also covers the table of constants.
 // Behind every TILED and ORBIT plan line come the launch arguments the family's pure builder makes for it (smr_plan_tiled_args.cpp,
 // smr_plan_orbit_args.cpp): "args <id> opt=<set> | <form> | <digest>" over the builder's status, the argument struct's bytes (pointers
 // null) and its tables -- TILED: the variant tiled_variant() names, struct and lane rows; ORBIT: "variant" lines with orbit_variant()'s
@@ -455,6 +457,45 @@ static void split_group_corpus() {
     plan_split_group("off/mixed", mixed, 0);                            // the unsplit plan
 }
 
+// Contraction groups with per-member constants of f (SMR_GROUP_CONTRACT_SCALARS): "gscalars <id> | describe() | digest", the digest also
+// over the table of constants (W, varc, whether the mul! form runs natively, every row) and, for a split group, the split form's tables.
+// Rows of their own behind the other corpora: every line above is the one of a tree without the flag.
+static void plan_scalars_group(const std::string& id, const std::vector<smr_problem>& ms, i64 split = 0, i64 tile = 0) {
+    const i64 saved_tile = group_contract_tile(), saved_split = group_contract_split();
+    group_contract_tile() = tile;
+    group_contract_split() = split;
+    GroupPlan g;
+    const int rc = plan_group(ms.data(), (int)ms.size(), SMR_GROUP_CONTRACT_SCALARS, g);
+    group_contract_tile() = saved_tile;
+    group_contract_split() = saved_split;
+    if (rc) {
+        std::printf("gscalars %s | rc=%d | %s\n", id.c_str(), rc, last_error.c_str());
+        return;
+    }
+    Fnv f;
+    f.v(digest(g));
+    f.v(g.contract.W); f.v((int)g.contract.varc); f.v((int)g.contract.mul2scale); f.vec(g.contract.consts);
+    f.v(g.contract.split.size()); f.bytes(g.contract.split.data(), g.contract.split.size() * sizeof(GroupSplitD));
+    f.vec(g.contract.fold_first); f.v(g.contract.nsplit); f.v(g.contract.max_s); f.v(g.contract.scratch_bytes);
+    std::printf("gscalars %s | %s | %016llx\n", id.c_str(), g.desc.c_str(), (unsigned long long)f.h);
+}
+
+static void scalars_group_corpus() {
+    typedef std::vector<smr_problem> Ms;
+    auto alpha = [](smr_problem p, double re) {
+        set_f(p, P_MULC, {re, 0});
+        return p;
+    };
+    Ms shared, member, split;
+    for (int i = 0; i < 12; ++i) shared.push_back(alpha(gmm(i, 20 + i, 24, 9), 2.0));
+    for (int i = 0; i < 12; ++i) member.push_back(alpha(gmm(i, 20 + i, 24, 9), 0.5 * (i + 2)));
+    for (int i = 0; i < 10; ++i) split.push_back(alpha(gmm(i, 32, 32, 32), 3.0 - i));
+    for (int i = 10; i < 12; ++i) split.push_back(alpha(gmm(i, 32, 32, 16384), -0.25 * i));
+    plan_scalars_group("shared", shared);               // equal constants: the unflagged plan, scalars=shared
+    plan_scalars_group("member", member);               // a row per member, f=mul2scale
+    plan_scalars_group("member+split", split, 3, 16);   // ... and the long members cut into slices
+}
+
 static void group_corpus() {
     const uint32_t IND = SMR_GROUP_INDEPENDENT, OWN = SMR_GROUP_MEMBER_SCALARS;
     typedef std::vector<smr_problem> Ms;
@@ -808,6 +849,7 @@ int main() {
     split_corpus();
     group_corpus();
     split_group_corpus();
+    scalars_group_corpus();
     static const char* fam[] = {"auto", "generic", "stream", "tiled", "reduce_all", "reduce_part", "orbit", "flat", "contract"};
     std::fprintf(stderr, "%ld lines:", lines);
     for (int f = 1; f < 9; ++f) std::fprintf(stderr, " %s=%ld", fam[f], fam_lines[f]);
