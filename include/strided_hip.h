@@ -608,12 +608,44 @@ int64_t smr_plan_flat_batched(const smr_plan* plan, int64_t* out, size_t cap);
  * [ independent=asserted]"; smr_group_layout reports form 3 (strided) or 4 (vector), the first workgroup, W_i and the canonical rank.
  * The launch is NOT sliceable -- the fold needs all of a member's workgroups in one launch: a recorded reduction group is one
  * packet per replay and stays whole under "slices" = n.  Option "nt_load" selects non-temporal loads in the vector body as in a
- * single call; it does not change values.                                                                                   */
+ * single call; it does not change values.
+ *
+ * PARTIAL REDUCTION GROUPS.  With SMR_GROUP_REDUCE | SMR_GROUP_REDUCE_PART the group is K reductions that may KEEP dims -- a
+ * matrix-vector product y[i] = sum_j A[i,j] * x[j], row or column norms, a partial trace, sum(A; dims=2) per block:
+ * dest[I] = op(initop(dest[I]), op over the reduced dims of f(in1, in2, ...)) with a destination that keeps any number of dims -- run
+ * as ONE launch of csrc/smr_k_greduce_part.hip.  SMR_GROUP_REDUCE_PART without SMR_GROUP_REDUCE is SMR_EUNSUPPORTED; without the flag
+ * every other combination plans, describes, launches and refuses exactly as before (flag 8 alone still refuses a kept dim with
+ * "complete").  It combines with SMR_GROUP_INDEPENDENT and is refused with SMR_GROUP_MEMBER_SCALARS and SMR_GROUP_CONTRACT_SCALARS as a
+ * reduction group refuses them.  Every member must be a reduction (redop != SMR_RED_NONE; a map gets SMR_EUNSUPPORTED naming the
+ * member) with 1 .. SMR_MAXM - 1 distinct inputs and at most 2^31 - 1 box elements; members agree with member 0 exactly as in a
+ * reduction group; beta, rank, extents, strides, pointers, offsets and WHICH dims are kept are the member's own.  Members with one
+ * destination element and members with no reduced dim at all (the accumulating map dest[I] = op(dest[I], f(...))) are accepted.  The
+ * independence check, the count limits, prepare / execute / destroy and smr_seq_add_group work as for the other kinds.  A member's
+ * destination range in the check and in the footprint is its whole bounding range, so destinations that interleave in memory (the
+ * columns of one matrix) need SMR_GROUP_INDEPENDENT; the destination counts as READ unless the initop code is ZERO or CONST.
+ * RULE: member i takes the general form of a single partial reduction with the reduced range in ONE piece: TR_i consecutive lanes (a
+ * power of two, 1 .. 256: what the single planner's general form gives that canonical problem) cooperate on one destination element, a
+ * workgroup of 256 lanes owns 256 / TR_i consecutive destination elements in canonical order, W_i = ceil(nout_i / (256 / TR_i)).  The
+ * group never splits a member's reduced range: no partials, no counters, no scratch -- long members are not what a group is for.
+ * ACCUMULATION ORDER: with red_i reduced elements per destination element in canonical order, lane rl = 0 .. TR_i - 1 of a destination
+ * element accumulates r = rl, rl + TR_i, rl + 2 TR_i, ... serially into one accumulator that starts at the op's neutral element; the
+ * TR_i accumulators are folded by the wave butterfly (xor 32, 16, ... 1 below min(TR_i, 64)) and, for TR_i > 64, lane 0 then adds the
+ * waves' values in ascending order through LDS; lane 0 applies the initop with the member's beta, the op, and stores.
+ * GUARANTEE: member i's result is bit-identical to smr_mapreduce on that member alone under option "reduce_part_kind" = 0 wherever
+ * that call's description reads "form=general lanes_per_out=TR_i split=1".  No identity is claimed for members the single planner would
+ * split (red >= 256 * TR with few outputs), members with one destination element (a single call runs REDUCE_ALL) and members with no
+ * reduced dim; their order is still the one above.
+ * smr_group_describe reads "family=group kind=reduce_part members=K grid=G lanes=<TR:members, ascending TR, comma separated>
+ * f=<ident|abs2|mul2|prog> op=<+|*|min|max|&||> jit=<0|1> bytes=<algorithmic bytes>[ independent=asserted]"; smr_group_layout reports
+ * form 5, the first workgroup, W_i and the canonical rank; smr_group_lanes reports TR_i per member (layout has no room for it).
+ * No workgroup depends on another, so the launch IS sliceable: a recorded partial reduction group is one packet per replay and is cut
+ * into block ranges under "slices" = n, like a map group.                                                                        */
 typedef struct smr_group smr_group;
 #define SMR_GROUP_INDEPENDENT 1u /* the caller asserts that no member writes an element another member reads or writes */
 #define SMR_GROUP_MEMBER_SCALARS 2u /* the values of f's constants may differ from member to member */
 #define SMR_GROUP_REDUCE 8u /* a reduction group: every member a complete reduction (REDUCTION GROUPS above; bit 4 is not a flag) */
 #define SMR_GROUP_CONTRACT_SCALARS 64u /* a contraction group whose members have constants of f of their own (bits 4, 16 and 32 are not flags) */
+#define SMR_GROUP_REDUCE_PART 256u /* with SMR_GROUP_REDUCE only: the members may keep dims (PARTIAL REDUCTION GROUPS above; bit 128 is not a flag) */
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out);
 int smr_group_prepare(smr_group* g);
 int smr_group_execute(smr_group* g, void* stream);
@@ -622,6 +654,9 @@ int smr_group_describe(const smr_group* g, char* buf, size_t buflen);
 int64_t smr_group_algorithmic_bytes(const smr_group* g);
 int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap);
 int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap);
+/* A partial reduction group: the lanes per destination element TR_i of up to `cap` members into out[]; returns the member count (0 for
+ * every other kind of group). */
+int64_t smr_group_lanes(const smr_group* g, int64_t* out, size_t cap);
 int smr_group_destroy(smr_group* g);
 
 /* Runtime compilation.  An `f` without a natively compiled functor is specialised the way

@@ -82,7 +82,7 @@ EXPORTS = [
     "smr_comm_destroy", "smr_mapreduce_sharded", "smr_mapreduce_sharded_ex", "smr_shard", "smr_shard_ex", "smr_init_reduction", "smr_set_option",
     "smr_get_option", "smr_overlap_begin", "smr_overlap_end", "smr_overlap_fence", "smr_stream_create", "smr_stream_destroy",
     "smr_seq_create", "smr_seq_add", "smr_seq_add_group", "smr_seq_run", "smr_seq_wait", "smr_seq_info", "smr_seq_components", "smr_seq_fences", "smr_seq_set", "smr_seq_destroy", "smr_debug_kernarg_layout", "smr_debug_canon_prog", "smr_debug_seq_schedule",
-    "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_split_layout", "smr_group_destroy",
+    "smr_group_create", "smr_group_prepare", "smr_group_execute", "smr_group_describe", "smr_group_algorithmic_bytes", "smr_group_layout", "smr_group_split_layout", "smr_group_lanes", "smr_group_destroy",
 ]
 
 
@@ -199,6 +199,8 @@ def load():
     lib.smr_group_layout.restype = C.c_int64
     lib.smr_group_split_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_size_t]
     lib.smr_group_split_layout.restype = C.c_int64
+    lib.smr_group_lanes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_size_t]
+    lib.smr_group_lanes.restype = C.c_int64
     lib.smr_group_destroy.argtypes = [C.c_void_p]
     if lib.smr_abi_version() != 1:
         raise ImportError("libstrided_hip.so ABI version mismatch; rebuild")
@@ -472,6 +474,7 @@ SMR_GROUP_INDEPENDENT = 1
 SMR_GROUP_MEMBER_SCALARS = 2
 SMR_GROUP_REDUCE = 8
 SMR_GROUP_CONTRACT_SCALARS = 64
+SMR_GROUP_REDUCE_PART = 256
 
 
 class Group:
@@ -497,10 +500,17 @@ class Group:
     i on min(ceil(total_i / 4096), 64) workgroups, its partials folded inside the launch through scratch the group owns (do not run
     one group on two streams at once).  Each member is bit-identical to the single call under option "reduce_blocks" = 64 where that
     call runs family REDUCE_ALL.  `member_scalars` is refused for it.
+    `reduce=True, reduce_part=True` passes SMR_GROUP_REDUCE | SMR_GROUP_REDUCE_PART: a PARTIAL reduction group, every member a
+    reduction that may keep dims (a matrix-vector product, row norms, sum(A; dims=2) per block) -- which dims is the member's own; one
+    launch of csrc/smr_k_greduce_part.hip, member i with TR_i lanes per destination element (`lanes()`) on ceil(nout_i / (256 / TR_i))
+    workgroups, its reduced range never split (no scratch).  Each member is bit-identical to the single call under option
+    "reduce_part_kind" = 0 where that call reads "form=general lanes_per_out=TR_i split=1".  A member's destination range is its whole
+    bounding range: destinations that interleave in memory (the columns of one matrix) need `independent=True`.  `reduce_part` without
+    `reduce` is refused.
     See include/strided_hip.h."""
 
     def __init__(self, problems, independent: bool = False, keepalive=(), member_scalars: bool = False, reduce: bool = False,
-                 contract_scalars: bool = False):
+                 contract_scalars: bool = False, reduce_part: bool = False):
         self._lib = load()
         self._h = C.c_void_p()
         self.count = len(problems)
@@ -510,6 +520,7 @@ class Group:
         self._keep = (arr, problems, keepalive)
         flags = (SMR_GROUP_INDEPENDENT if independent else 0) | (SMR_GROUP_MEMBER_SCALARS if member_scalars else 0) | (SMR_GROUP_REDUCE if reduce else 0)
         flags |= SMR_GROUP_CONTRACT_SCALARS if contract_scalars else 0
+        flags |= SMR_GROUP_REDUCE_PART if reduce_part else 0
         check(self._lib.smr_group_create(arr, self.count, flags, C.byref(self._h)))
 
     def execute(self, stream: int | None = None):
@@ -526,12 +537,20 @@ class Group:
 
     def layout(self):
         """Per member (form, first workgroup, workgroups, canonical rank); form 0 = linear, 1 = transposing, 2 = a member of a
-        contraction group, 3 / 4 = a member of a reduction group on the strided / the vector body."""
+        contraction group, 3 / 4 = a member of a reduction group on the strided / the vector body, 5 = a member of a partial reduction
+        group."""
         n = int(self._lib.smr_group_layout(self._h, None, 0))
         buf = (C.c_int64 * max(1, n))()
         self._lib.smr_group_layout(self._h, buf, n)
         v = list(buf)[:n]
         return [tuple(v[i:i + 4]) for i in range(0, n, 4)]
+
+    def lanes(self):
+        """Per member of a partial reduction group the lanes per destination element TR_i; [] for every other kind."""
+        n = int(self._lib.smr_group_lanes(self._h, None, 0))
+        buf = (C.c_int64 * max(1, n))()
+        self._lib.smr_group_lanes(self._h, buf, n)
+        return list(buf)[:n]
 
     def split_layout(self):
         """Per member (slices S, chunks per slice, first fold workgroup, fold workgroups) of a contraction group with at least one

@@ -1,7 +1,8 @@
 // smr_group.cpp -- grouped launches (include/strided_hip.h: smr_group_*): the C ABI and the launch path of a planned group.
 // smr_group_create checks its arguments and has the planner (smr_plan_group.cpp: plan_group) fill a GroupPlan; the device tables
 // (members, workgroup prefix sums, per-member scalars) are uploaded by smr_group_prepare or the first execution, and
-// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip, smr_k_greduce.hip)
+// smr_group_execute runs the group as ONE launch of the kernel of its kind (smr_k_group.hip, smr_k_gcontract.hip, smr_k_greduce.hip,
+// smr_k_greduce_part.hip)
 // -- a contraction group with split members (option "group_contract_split") as two, through partials the group owns.  A reduction
 // group (SMR_GROUP_REDUCE) owns partials and arrival counters too, and folds them inside its one launch.
 #include <algorithm>
@@ -27,6 +28,7 @@ namespace {
 // the launcher of the group's kind in the object of compute class CT (a bit copy, never a contraction, goes through Float32's)
 template <int CT>
 int launch_group_in(const GroupPlan& g, hipStream_t s) {
+    if (g.kind == GROUP_REDUCE_PART) return launch_group_reduce_part_ct<CT>(g, s);
     if (g.kind == GROUP_REDUCE) return launch_group_reduce_ct<CT>(g, s);
     if (g.kind == GROUP_CONTRACT && g.contract.varc)  // per-member constants of f: the bodies that read the member's row
         return g.contract.nsplit ? launch_group_contract_split_varc_ct<CT>(g, s) : launch_group_contract_varc_ct<CT>(g, s);
@@ -105,7 +107,7 @@ extern "C" {
 int smr_group_create(const smr_problem* members, int count, uint32_t flags, smr_group** out) {
     if (!members || !out) return set_error(SMR_EINVAL, "smr_group_create: null argument");
     if (count < 1 || count > 65535) return set_error(SMR_EINVAL, "smr_group_create: count must be 1..65535");
-    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS | SMR_GROUP_REDUCE | SMR_GROUP_CONTRACT_SCALARS)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
+    if (flags & ~(SMR_GROUP_INDEPENDENT | SMR_GROUP_MEMBER_SCALARS | SMR_GROUP_REDUCE | SMR_GROUP_CONTRACT_SCALARS | SMR_GROUP_REDUCE_PART)) return set_error(SMR_EINVAL, "smr_group_create: unknown flag");
     smr_group* h = new (std::nothrow) smr_group();
     if (!h) return set_error(SMR_ENOMEM, "out of host memory");
     if (int rc = plan_group(members, count, flags, h->plan)) {
@@ -157,6 +159,14 @@ int64_t smr_group_layout(const smr_group* g, int64_t* out, size_t cap) {
                 if (4 * i + j < cap) out[4 * i + j] = v[j];
         }
     return (int64_t)(4 * n);
+}
+
+int64_t smr_group_lanes(const smr_group* g, int64_t* out, size_t cap) {
+    if (!g || g->plan.kind != GROUP_REDUCE_PART) return 0;
+    const std::vector<GroupReducePartMemberD>& ms = g->plan.reduce_part.members;
+    if (out)
+        for (size_t i = 0; i < ms.size() && i < cap; ++i) out[i] = (int64_t)1 << ms[i].trlog;
+    return (int64_t)ms.size();
 }
 
 int64_t smr_group_split_layout(const smr_group* g, int64_t* out, size_t cap) {

@@ -69,12 +69,29 @@ struct GroupReduceMemberD {
     int32_t pad;
 };
 
+// One member of a PARTIAL reduction group (SMR_GROUP_REDUCE | SMR_GROUP_REDUCE_PART; smr_k_greduce_part.hip): a reduction that keeps
+// dims, as a single call of FAM_REDUCE_PART's general form carries it in its arguments with the reduced range in one piece.  Dims
+// [0, NK) are kept, [NK, N) reduced (NK == 0: one destination element; NK == N: no reduced dim, an accumulating map).  1 << trlog
+// consecutive lanes cooperate on one destination element and a workgroup owns 256 >> trlog consecutive destination elements in
+// canonical order, so the member's workgroups are ceil(nout / (256 >> trlog)).  Everything in it is wave-uniform; beta is the member's own.
+struct GroupReducePartMemberD {
+    void* base[MAXM];            // operand addresses, element offsets folded in
+    i64 strides[MAXM][MAXN];     // canonical strides (elements; the destination's are 0 along the reduced dims)
+    i64 dims[MAXN];              // canonical dims
+    i64 nout, nred;              // destination elements, reduced elements per destination element (nout * nred <= 2^31 - 1)
+    double beta[2];
+    int32_t N, NK;               // canonical rank, kept dims
+    int32_t trlog;               // log2 of the lanes per destination element (0 .. 8)
+    int32_t pad;
+};
+
 // The tables are read-only for the whole launch and every index into them is wave-uniform: read through the constant address
 // space they are fetched by scalar loads into scalar registers, not once per lane.
 typedef const GroupMemberD __attribute__((address_space(4))) GroupMemberC;
 typedef const GroupContractMemberD __attribute__((address_space(4))) GroupContractMemberC;
 typedef const GroupSplitD __attribute__((address_space(4))) GroupSplitC;
 typedef const GroupReduceMemberD __attribute__((address_space(4))) GroupReduceMemberC;
+typedef const GroupReducePartMemberD __attribute__((address_space(4))) GroupReducePartMemberC;
 typedef const uint32_t __attribute__((address_space(4))) GroupWordC;
 typedef const double __attribute__((address_space(4))) GroupConstC;
 
@@ -93,8 +110,8 @@ SMR_DEV int group_member_of(GroupWordC* first_wg, int count, uint32_t b) {
 }
 
 // what smr_group_layout reports per member: the body a map member runs (GroupMemberD::form), that it is a contraction, or the body
-// a member of a reduction group runs (GroupReduceMemberD::form)
-enum GroupForm { GROUP_FORM_LINEAR = 0, GROUP_FORM_TRANSPOSING = 1, GROUP_FORM_CONTRACT = 2, GROUP_FORM_REDUCE_STRIDED = 3, GROUP_FORM_REDUCE_VECTOR = 4 };
+// a member of a reduction group runs (GroupReduceMemberD::form), or that it is a member of a partial reduction group
+enum GroupForm { GROUP_FORM_LINEAR = 0, GROUP_FORM_TRANSPOSING = 1, GROUP_FORM_CONTRACT = 2, GROUP_FORM_REDUCE_STRIDED = 3, GROUP_FORM_REDUCE_VECTOR = 4, GROUP_FORM_REDUCE_PART = 5 };
 
 #ifndef SMR_JIT
 // every recognised functor has a natively compiled group kernel (a single call's functor code); any other f is a program, as in GENERIC
@@ -104,8 +121,9 @@ constexpr unsigned GROUP_FMASK = 0xffffffffu;
 constexpr unsigned GROUP_REDUCE_FMASK = (1u << FK_IDENT) | (1u << FK_ABS2) | (1u << FK_MUL2);
 
 // the kind is member 0's: a reduction opens a contraction group (every member an outer-product reduction on FAM_CONTRACT's tile body)
-// -- unless SMR_GROUP_REDUCE asks for a reduction group (every member a complete reduction)
-enum GroupKind { GROUP_MAP, GROUP_CONTRACT, GROUP_REDUCE };
+// -- unless SMR_GROUP_REDUCE asks for a reduction group (every member a complete reduction; with SMR_GROUP_REDUCE_PART every member
+// a reduction that may keep dims)
+enum GroupKind { GROUP_MAP, GROUP_CONTRACT, GROUP_REDUCE, GROUP_REDUCE_PART };
 
 struct GroupMapPlan {  // GROUP_MAP only
     std::vector<GroupMemberD> members;
@@ -148,6 +166,11 @@ struct GroupReducePlan {  // GROUP_REDUCE only
     mutable void* d_counters = nullptr;
 };
 
+struct GroupReducePartPlan {  // GROUP_REDUCE_PART only: no partials, no counters, no scratch -- a member's reduced range is never split
+    std::vector<GroupReducePartMemberD> members;
+    int lanes[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // members per lanes-per-output 1 << j
+};
+
 // A planned group.  `c` is the canonical problem of member 0: its compute class, flags, dtypes and f-program are those of every member
 // (the values of the program's constants too, unless `map.varc` / `contract.varc`).
 struct GroupPlan {
@@ -156,6 +179,7 @@ struct GroupPlan {
     GroupMapPlan map;
     GroupContractPlan contract;
     GroupReducePlan reduce;
+    GroupReducePartPlan reduce_part;
     std::vector<uint32_t> first_wg;   // count + 1 prefix sums of the members' workgroups
     std::vector<int> rank;            // canonical rank per member (smr_group_layout)
     bool jit = false;                 // f runs as a runtime-compiled functor
@@ -172,9 +196,13 @@ struct GroupPlan {
     // a host table as bytes; the member table of the group's kind
     template <class E> static std::pair<const void*, size_t> bytes_of(const std::vector<E>& v) { return {v.data(), v.size() * sizeof(E)}; }
     std::pair<const void*, size_t> member_table() const {
+        if (kind == GROUP_REDUCE_PART) return bytes_of(reduce_part.members);
         return kind == GROUP_CONTRACT ? bytes_of(contract.members) : (kind == GROUP_REDUCE ? bytes_of(reduce.members) : bytes_of(map.members));
     }
-    int form(size_t i) const { return kind == GROUP_CONTRACT ? GROUP_FORM_CONTRACT : (kind == GROUP_REDUCE ? reduce.members[i].form : map.members[i].form); }
+    int form(size_t i) const {
+        if (kind == GROUP_REDUCE_PART) return GROUP_FORM_REDUCE_PART;
+        return kind == GROUP_CONTRACT ? GROUP_FORM_CONTRACT : (kind == GROUP_REDUCE ? reduce.members[i].form : map.members[i].form);
+    }
 };
 
 // smr_plan_group.cpp: plans members[0..count) (count >= 1, known flags) into a fresh `g`.  Host arithmetic only, no HIP runtime call
@@ -186,6 +214,7 @@ template <int CT> int launch_group_contract_split_ct(const GroupPlan&, hipStream
 template <int CT> int launch_group_contract_varc_ct(const GroupPlan&, hipStream_t);        // ... with -DSMR_GCONTRACT_VARC (contract.varc)
 template <int CT> int launch_group_contract_split_varc_ct(const GroupPlan&, hipStream_t);  // ... (contract.varc and a split member)
 template <int CT> int launch_group_reduce_ct(const GroupPlan&, hipStream_t);    // smr_k_greduce.hip
+template <int CT> int launch_group_reduce_part_ct(const GroupPlan&, hipStream_t);  // smr_k_greduce_part.hip
 
 int ensure_device();         // smr_api.cpp
 i64& group_max_bytes();      // option "group_max_bytes" (smr_group.cpp)

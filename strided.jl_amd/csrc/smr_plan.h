@@ -27,6 +27,9 @@ constexpr i64 REDUCE_FOLD_MAX = 64;             // most partials of ONE arrival 
 // a whole number of vectors, at least REDUCE_ALL_PER_BLOCK elements, every input broadcast or unit-stride from a 16-byte aligned
 // address (`bases`: the call's base pointers, nullptr: the plan's)
 bool reduce_all_vector(const Canon& c, void* const* bases);
+// partial reductions, the general form: the lanes that cooperate on one destination element (a power of two, 1 .. 256; `red` reduced
+// elements per output) -- plan_part_general's rule, which the members of a partial reduction group (smr_plan_group.cpp) take as well
+int reduce_part_general_lanes(const Canon& c, i64 red);
 bool plan_contract(const Canon& c, ContractPlan& cp);             // smr_plan_contract.cpp (shape rules + the "contract" option's gate)
 // predicates shared by the family planners (smr_plan.cpp)
 int elem_bytes(const Canon& c);                      // bytes per element as the kernels move them

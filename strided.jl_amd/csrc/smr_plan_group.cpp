@@ -6,7 +6,8 @@
 // independence check's input and the footprint of a group recorded in a sequence.  What differs between the kinds are plain functions
 // called from that loop: a map member takes one of the kernel's two bodies and its workgroups at once, a contraction its workgroups
 // once the whole group has decided the tile, a complete reduction (SMR_GROUP_REDUCE) its body, its workgroups and -- with more than
-// one -- its run of partial slots and its arrival counter.
+// one -- its run of partial slots and its arrival counter, a partial reduction (SMR_GROUP_REDUCE | SMR_GROUP_REDUCE_PART) its lanes per
+// destination element and its workgroups.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -461,13 +462,63 @@ void reduce_describe(GroupPlan& g, uint32_t flags) {
     g.desc = buf;
 }
 
+// ---- partial reduction groups ------------------------------------------------------------------------------------------------------
+// member i, a reduction that may keep dims: the general form of REDUCE_PART with the reduced range in ONE piece.  TR lanes per
+// destination element as plan_part_general gives that canonical problem (reduce_part_general_lanes, smr_plan_reduce.cpp), a workgroup
+// owns 256 / TR consecutive destination elements, W = ceil(nout / (256 / TR)).  Never split: no partials, no counters, no scratch.
+int reduce_part_admit(int i, const Canon& c) {
+    if (c.M < 2) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " has no input: a reduction in a group reads 1 .. SMR_MAXM - 1 distinct inputs");
+    return SMR_OK;
+}
+
+int reduce_part_member(GroupPlan& g, int i, const Canon& c) {
+    GroupReducePartPlan& rp = g.reduce_part;
+    GroupReducePartMemberD& m = rp.members[(size_t)i];
+    std::memset(&m, 0, sizeof m);
+    for (int k = 0; k < c.M; ++k) {
+        m.base[k] = (char*)c.base[k] + c.offsets[k] * (i64)c.esize[k];
+        for (int d = 0; d < c.N; ++d) m.strides[k][d] = c.strides[k][d];
+    }
+    for (int d = 0; d < MAXN; ++d) m.dims[d] = d < c.N ? c.dims[d] : 1;
+    m.nout = std::max<i64>(1, c.nout);
+    m.nred = c.total / m.nout;
+    m.N = c.N;
+    m.NK = std::min(c.NK, c.N);
+    m.beta[0] = c.initarg[0];
+    m.beta[1] = c.initarg[1];
+    const int tr = reduce_part_general_lanes(c, m.nred);
+    while ((1 << m.trlog) < tr) ++m.trlog;
+    rp.lanes[m.trlog] += 1;
+    const i64 ob = 256 >> m.trlog;
+    return assign_workgroups(g, i, (m.nout + ob - 1) / ob);
+}
+
+void reduce_part_describe(GroupPlan& g, uint32_t flags) {
+    static const char* names[FK_COUNT] = {"prog", "ident", "add2", "add3", "add4", "scale", "sym", "axpy", "axpby", "abs2", "mul2", "expr5"};
+    static const char* ops[] = {"none", "+", "*", "min", "max", "&", "|"};
+    const Canon& c = g.c;
+    // launch_group_reduce_part_ct(): a functor of the mask when the operand types are the compute class's, every other f a program
+    const int fk = (!c.mixed && (GROUP_REDUCE_FMASK & fbit(c.fkind))) ? c.fkind : FK_PROG;
+    g.jit = options().jit && fk == FK_PROG;
+    std::string lanes;  // the distinct lanes per output, ascending, each with its member count
+    for (int j = 0; j <= 8; ++j)
+        if (g.reduce_part.lanes[j]) lanes += (lanes.empty() ? "" : ",") + std::to_string(1 << j) + ":" + std::to_string(g.reduce_part.lanes[j]);
+    char buf[320];
+    std::snprintf(buf, sizeof buf, "family=group kind=reduce_part members=%zu grid=%u lanes=%s f=%s op=%s jit=%d bytes=%lld%s", g.rank.size(), g.first_wg.back(),
+                  lanes.c_str(), names[fk], c.redop >= 0 && c.redop < 7 ? ops[c.redop] : "?", g.jit ? 1 : 0, (long long)g.algbytes, independent_tag(flags));
+    g.desc = buf;
+}
+
 }  // namespace
 
 int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan& g) {
     const bool contract_scalars = (flags & SMR_GROUP_CONTRACT_SCALARS) != 0;
     const bool own_scalars = (flags & SMR_GROUP_MEMBER_SCALARS) != 0, independent = (flags & SMR_GROUP_INDEPENDENT) != 0;
-    const bool reduce = (flags & SMR_GROUP_REDUCE) != 0;        // a reduction group: every member a complete reduction
+    const bool reduce = (flags & SMR_GROUP_REDUCE) != 0;        // a reduction group: every member a complete reduction ...
+    const bool part = (flags & SMR_GROUP_REDUCE_PART) != 0;     // ... or, with this flag as well, a reduction that may keep dims
     const bool contraction = !reduce && members[0].redop != SMR_RED_NONE;  // else the kind is member 0's
+    if (part && !reduce)
+        return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_REDUCE_PART without SMR_GROUP_REDUCE: the flag turns a reduction group into a partial reduction group and is valid only together with it");
     // (SMR_GROUP_CONTRACT_SCALARS first: its refusals name it, whatever else is set; the refusals of flag 2 keep their text)
     if (contract_scalars && reduce)
         return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_CONTRACT_SCALARS with a reduction group (SMR_GROUP_REDUCE): per-member constants of f are not supported there");
@@ -479,10 +530,11 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
         return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a reduction group (SMR_GROUP_REDUCE): per-member constants of f are not supported there");
     if (contraction && own_scalars)
         return set_error(SMR_EUNSUPPORTED, "smr_group_create: SMR_GROUP_MEMBER_SCALARS with a contraction group (member 0 is a reduction): per-member constants of f are not supported there");
-    g.kind = reduce ? GROUP_REDUCE : (contraction ? GROUP_CONTRACT : GROUP_MAP);
+    g.kind = part ? GROUP_REDUCE_PART : (reduce ? GROUP_REDUCE : (contraction ? GROUP_CONTRACT : GROUP_MAP));
     g.first_wg.assign((size_t)count + 1, 0);
     g.rank.resize((size_t)count);
-    if (reduce) g.reduce.members.resize((size_t)count);
+    if (part) g.reduce_part.members.resize((size_t)count);
+    else if (reduce) g.reduce.members.resize((size_t)count);
     else if (contraction) g.contract.members.resize((size_t)count);
     else g.map.members.resize((size_t)count);
     std::vector<Range> ranges;
@@ -490,7 +542,9 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
     for (int i = 0; i < count; ++i) {
         const smr_problem& p = members[i];
         // admit: a map group holds maps only, a contraction group reductions of the contraction shape only, a reduction group
-        // complete reductions only
+        // complete reductions only, a partial reduction group reductions only
+        if (part && p.redop == SMR_RED_NONE)
+            return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a map; a partial reduction group (SMR_GROUP_REDUCE | SMR_GROUP_REDUCE_PART) holds reductions only");
         if (reduce && p.redop == SMR_RED_NONE)
             return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a map; a reduction group (SMR_GROUP_REDUCE) holds complete reductions only");
         if (!reduce && (p.redop != SMR_RED_NONE) != contraction)
@@ -504,7 +558,7 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
             return set_error(SMR_EUNSUPPORTED, member_tag(i) + " is a reduction, but not of the contraction shape: two inputs that vary along different kept dims of "
                                                                 "extent > 1 and both along a reduced dim, neither on the destination's buffer; a group holds maps only, or such contractions only");
         if (reduce)
-            if (int rc = reduce_admit(i, c)) return rc;
+            if (int rc = part ? reduce_part_admit(i, c) : reduce_admit(i, c)) return rc;
         if (i > 0) {
             const std::string why = mismatch(g.c, c, own_scalars || contract_scalars);
             if (!why.empty()) return set_error(SMR_EUNSUPPORTED, member_tag(i) + " " + why);
@@ -526,7 +580,7 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
         }
         // a map member takes its workgroups here; a contraction's depend on the tile, which contract_finish picks for the whole group
         if (reduce) {
-            if (int rc = reduce_member(g, i, c)) return rc;
+            if (int rc = part ? reduce_part_member(g, i, c) : reduce_member(g, i, c)) return rc;
         } else if (contraction) {
             contract_member(g.contract.members[(size_t)i], c, di, dj);
             if (contract_scalars) contract_member_consts(g.contract, i, c);
@@ -540,7 +594,8 @@ int plan_group(const smr_problem* members, int count, uint32_t flags, GroupPlan&
     if (int rc = independent ? SMR_OK : check_independent(ranges)) return rc;
     g.rd = merged(std::move(rd));
     g.wr = merged(std::move(wr));
-    if (reduce) reduce_describe(g, flags);
+    if (part) reduce_part_describe(g, flags);
+    else if (reduce) reduce_describe(g, flags);
     else if (contraction) contract_describe(g, flags);
     else map_describe(g, flags);
     return SMR_OK;

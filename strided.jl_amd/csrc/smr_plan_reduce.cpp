@@ -147,9 +147,7 @@ static void plan_part_row(const Canon& c, const PartShape& s, ReducePlan& rp) {
 }
 
 // general form: lanes cooperating per output: more when few outputs / long reductions
-static void plan_part_general(const Canon& c, const PartShape& s, ReducePlan& rp) {
-    const i64 red = s.red;
-    rp.kind = 0;
+int reduce_part_general_lanes(const Canon& c, i64 red) {
     int tr = 1;
     // the inputs' fastest-varying dim is a reduced one -> lanes along it coalesce
     bool red_fast = false;
@@ -160,6 +158,13 @@ static void plan_part_general(const Canon& c, const PartShape& s, ReducePlan& rp
         while (tr < 256 && tr * 2 <= red && (tr < 64 || c.nout * tr < 256 * 1024)) tr <<= 1;
     }
     if (red_fast && tr < 16 && red >= 16) tr = 16;
+    return tr;
+}
+
+static void plan_part_general(const Canon& c, const PartShape& s, ReducePlan& rp) {
+    const i64 red = s.red;
+    rp.kind = 0;
+    const int tr = reduce_part_general_lanes(c, red);
     rp.tr = tr;
     // few destination elements, long reductions: cut the reduced range so that ~2048
     // workgroups are in flight, partials folded by a second launch (also keeps the

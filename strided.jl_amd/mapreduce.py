@@ -287,6 +287,8 @@ def _mapreduce_fuse_(f, op, initop, dims, arrays):
             return arrays[0]
         if op is not None and g.reduce and g.defer(f, dims, arrays, op, initop, complete=True):  # a complete reduction: S.group(reduce=True)
             return arrays[0]
+        if op is not None and g.reduce_part and g.defer(f, dims, arrays, op, initop, part=True):  # any other reduction: S.group(reduce=True, reduce_part=True)
+            return arrays[0]
         g.flush()
     if _SMR_MAPREDUCE is None:
         _SMR_MAPREDUCE = L.load().smr_mapreduce
@@ -332,7 +334,7 @@ class _GroupState(threading.local):
 
 
 _GROUP = _GroupState()
-_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars -- "contract_scalars" for a contraction bucket under that keyword --, stream, the kind: (forced contraction tile, group_contract_split), "reduce", or 0 for maps); least recently used first
+_GROUP_CACHE: "collections.OrderedDict" = collections.OrderedDict()  # built groups by (member keys, independent, member_scalars -- "contract_scalars" for a contraction bucket under that keyword --, stream, the kind: (forced contraction tile, group_contract_split), "reduce", "reduce_part", or 0 for maps); least recently used first
 
 
 def _byte_range(a):
@@ -419,7 +421,7 @@ class _Deferred:
 
 
 class group:
-    """`with S.group(independent=False, member_scalars=False, contract=False, reduce=False, contract_scalars=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
+    """`with S.group(independent=False, member_scalars=False, contract=False, reduce=False, contract_scalars=False, reduce_part=False) as g:` -- grouped launches.  Inside the block the map front ends (`copy_`, `permutedims_`,
     `map_`, broadcast `copyto_`, `axpby_`, ...) do not launch: eligible calls are deferred and, at the end of the block or at
     `g.flush()`, every bucket of calls with the same (f-program, operand dtypes, operand count, conj flags, repeated inputs, stream) becomes ONE
     kernel launch (L.Group / smr_group_*).  A block never changes results, only launch counts:
@@ -457,12 +459,24 @@ class group:
     values of f's captured scalars (always: a reduction group has one f); beta is per member.  Each result is bit-identical to the
     single call's under option "reduce_blocks" = 64 where that call runs family REDUCE_ALL (include/strided_hip.h).
     `S.mapreduce(f, op, A)` without `dims` returns a host scalar: like every host read it still flushes, and is never deferred.
+    `reduce=True, reduce_part=True` (partial reduction groups): every OTHER reduction with an op into an array destination -- one that
+    keeps dims: `mapreducedim_` into a vector of row sums, a matrix-vector product, `sum(A; dims=2)` -- within "group_max_bytes" is
+    deferred as well, after the contraction test (under `contract=True`) and the complete-reduction test, which keep their own buckets
+    and kinds; every bucket of them becomes ONE launch of csrc/smr_k_greduce_part.hip (L.Group(reduce=True, reduce_part=True)).  The
+    bucket key holds ("reduce_part", the op, the kind of initop) and the values of f's captured scalars; beta and the kept dims are per
+    member.  Each result is bit-identical to the single call's under option "reduce_part_kind" = 0 where that call reads "form=general
+    ... split=1" (include/strided_hip.h).  Destinations that interleave in memory (the columns of one matrix) have intersecting
+    bounding ranges: the block then flushes between them unless `independent=True` asserts that no element is shared.  `reduce_part`
+    without `reduce` is a ValueError; with `reduce=True` alone no partial reduction is deferred.
     `g.groups` lists the L.Group of every group launch of the block so far; `g.singles` counts calls that took the normal path."""
 
     MAX_PENDING = 4096
 
     def __init__(self, independent: bool = False, member_scalars: bool = False, contract: bool = False, reduce: bool = False,
-                 contract_scalars: bool = False):
+                 contract_scalars: bool = False, reduce_part: bool = False):
+        if reduce_part and not reduce:
+            raise ValueError("S.group(reduce_part=True) needs reduce=True: the flag turns reduction groups into partial reduction groups")
+        self.reduce_part = bool(reduce_part)
         if contract_scalars and not contract:
             raise ValueError("S.group(contract_scalars=True) needs contract=True: the flag is for contraction groups")
         self.contract_scalars = bool(contract_scalars)
@@ -507,23 +521,26 @@ class group:
                     return True
         return False
 
-    def defer(self, f, dims, arrays, op=None, initop=None, complete=False) -> bool:
+    def defer(self, f, dims, arrays, op=None, initop=None, complete=False, part=False) -> bool:
         """Takes one map call (destination first), or with `op` one reduction of the contraction shape -- with `complete` one
-        complete reduction (a reduction group's member) instead.  False: the call is not
+        complete reduction (a reduction group's member), with `part` any reduction (a partial reduction group's member) instead.  False: the call is not
         eligible (too large, too many operands, a reduction of another shape) -- the caller flushes and runs it through the normal
         path."""
         arrays = tuple(arrays)
         if len(arrays) < 2 or len(arrays) > L.SMR_MAXM or len(dims) > L.SMR_MAXN:
             return False
         if op is not None:
-            if not (_complete_reduction(dims, arrays) if complete else _contract_shaped(dims, arrays)):
+            if part:
+                if _member_bytes(arrays) > L.get_option("group_max_bytes"):
+                    return False
+            elif not (_complete_reduction(dims, arrays) if complete else _contract_shaped(dims, arrays)):
                 return False
         elif _member_bytes(arrays) > L.get_option("group_max_bytes"):
             return False
         c = _Deferred()
         c.f, c.dims, c.arrays = f, tuple(int(d) for d in dims), arrays
         c.op, c.initop = op, initop
-        c.kind = "map" if op is None else ("reduce" if complete else "contract")
+        c.kind = "map" if op is None else ("reduce_part" if part else ("reduce" if complete else "contract"))
         c.stream = _current_stream()
         dts = tuple(np.dtype(a.dtype) for a in arrays)
         code, consts = _serialized(f, len(arrays), dts)
@@ -534,7 +551,7 @@ class group:
         # what the constants contribute.  A contraction group has one f: their values, whatever member_scalars says.  Under
         # member_scalars a map contributes only what they decide in canonicalise(): count, complex or not, integer class or not
         # (contract_scalars: the same for a contraction, whose group then holds a row of constants per member)
-        if (self.member_scalars and op is None) or (self.contract_scalars and op is not None and not complete):
+        if (self.member_scalars and op is None) or (self.contract_scalars and op is not None and not complete and not part):
             ck = (len(consts), any(v.imag != 0 for v in consts), all(_integer_valued(v) for v in consts))
         else:
             ck = tuple(consts)
@@ -562,9 +579,10 @@ class group:
 
     def _launch(self, calls, stream):
         # a bucket of contractions: the library is not passed member_scalars, and plans under the forced tile and the split option
-        reduce = calls[0].kind == "reduce"
-        if reduce:  # a bucket of complete reductions: no member_scalars either; nothing an option decides at creation
-            scalars, plan_opts = False, "reduce"
+        part = calls[0].kind == "reduce_part"
+        reduce = part or calls[0].kind == "reduce"
+        if reduce:  # a bucket of complete (partial) reductions: no member_scalars either; nothing an option decides at creation
+            scalars, plan_opts = False, calls[0].kind
         elif calls[0].op is not None:
             scalars, plan_opts = False, (L.get_option("group_contract_tile"), L.get_option("group_contract_split"))
         else:
@@ -585,7 +603,7 @@ class group:
             try:
                 # (like _PROBLEM_CACHE, a cached group does not keep the operand parents alive: its key holds their addresses)
                 grp = L.Group([b[0] for b in built], self.independent, keepalive=[b[1][:2] for b in built], member_scalars=scalars,
-                              **({"reduce": True} if reduce else ({"contract_scalars": True} if cscalars else {})))   # (the other kinds are created exactly as before)
+                              **({"reduce": True, "reduce_part": True} if part else {"reduce": True} if reduce else ({"contract_scalars": True} if cscalars else {})))   # (the other kinds are created exactly as before)
             except L.UnsupportedOnDevice:
                 for c in calls:
                     self._single(c)
